@@ -13,26 +13,31 @@ Protocol: uniform random one-hot moves `[A][B][5]` that are FRESH
 device-side `mpe_reset` every 25 steps (MADDPG episode length), one `mpe_step` launch per step that reads its moves
 from HBM and writes every agent's obs / reward / done.  One "step" = every world of the batch advanced once.
 
-Timed region: barrier + synchronize, a HIP graph of up to 8000 CONSECUTIVE steps replayed back to back until the region
-holds >= 2 s of GPU work (whatever --steps is: `--steps 20` and `--steps 1000` time the same graph), synchronize +
-barrier; median of 5 repeats, max over ranks; `value` = B * timed steps * ranks / that time.  Rank 0 prints ONE JSON line
--- COMPACT (< 4096 bytes: the driver parses it; round 5's 20 KB line came back unparsed) -- and writes the full record
-(every leg, raw timings, per-rank records, the box) to --full-json (default gpurun_out/bench_full.json).
+Timed region: W warm-up steps, then barrier + synchronize, exactly K = --steps CONSECUTIVE steps (graph mode: HIP graphs of
+up to 8000 consecutive steps, captured and replayed once before the region), synchronize + barrier, max over ranks;
+`ms_per_step` = that time / K, `value` = B * K * ranks / that time.  --dump-outputs DIR: the outputs of the region's
+last step (obs<i>, rew, done, pos, vel) as float32 DIR/<name>.npy, <= 64 MB (a seeded sample of the worlds beyond that);
+the same arguments give the same inputs every run.
 
-Round 6: the SAME protocol is measured twice under the same bracket -- its steps LAUNCHED (one mpe_step per step, as
-above) and COMMANDED to the step server (include/mpe_hip.h: mpe_step_server_*; rollout.ServedRollout: per episode one
-block draw and one doorbell launch behind it on the commanding stream, the server's resident launch on a stream of its
-own; fresh moves read from HBM by every step, in-launch resets, every step's rows / rewards / dones / state written
-through to its own block) -- and the line's value is the faster (`config.mode`; --commands launched | served | auto);
-the other stays in the line (`roofline.launched`).
+The steps are issued two ways -- LAUNCHED (one mpe_step per step, as above) or COMMANDED to the step server
+(include/mpe_hip.h: mpe_step_server_*; rollout.ServedRollout: per episode one block draw and one doorbell launch behind it
+on the commanding stream, the server's resident launch on a stream of its own; fresh moves read from HBM by every step,
+in-launch resets, every step's rows / rewards / dones / state written through to its own block) -- and the line's value
+is the faster (`config.mode`; --commands launched | served | auto).  A plain run prints the contract's keys and
+`config` only: with --commands auto each way runs PROBE_STEPS steps first and the faster one is timed.
+
+--full adds everything else, as before: both ways timed over the K steps (the other stays in the line as
+`roofline.launched`), the roofline, the secondary legs below and the CPU baseline.  Rank 0 then prints ONE JSON line
+-- COMPACT (< 4096 bytes: round 5's 20 KB line came back unparsed) -- and writes the full record (every leg, raw
+timings, per-rank records, the box) to --full-json.
 
 N > 1 never measures fewer GPUs than asked for: with WORLD_SIZE unset `--gpus N` starts N ranks itself and fails when
 the node has fewer GPUs or a rank fails; with a launcher, WORLD_SIZE must equal --gpus.  The barrier travels over RCCL
 when every rank can bring it up and over gloo otherwise (`config.barrier_backend`; the step path has no collective, so
 the measured work is the same); `config.ranks` lists each rank's GPU, its own rate and kernel time; `roofline` is per
-GPU (slowest rank's kernel) and `cpu_baseline` is emitted on every line.
+GPU (slowest rank's kernel) and `cpu_baseline` is emitted on every --full line.
 
-Besides the headline the line carries (N=1 only):
+Besides the headline a --full line carries (N=1 only):
   roofline             the step kernel's HIP-event time over back-to-back launches -> algorithmic GB/s vs 8 TB/s.
                        At B=65536 the working set (27 MB/launch + the 98 MB move pool) sits in the 256 MiB Infinity
                        Cache: the limit there is launch + latency, and the line says so.
@@ -177,20 +182,37 @@ def bench_generic(args, env, dev, rank, world, rv):
         pool.append(acts)
 
     def run(n):
+        ret = None
         for k in range(n):
             if EP and k % EP == 0:
                 env.reset()
-            env.step(pool[k % len(pool)])
+            ret = env.step(pool[k % len(pool)])
+        return ret
     run(W)
     walls = []
-    for _ in range(args.repeats):
+    for _ in range(args.repeats if args.full else 1):      # (without --full: the K steps once)
         rv.barrier()
         t0 = time.perf_counter()
-        run(K)
+        ret = run(K)
         torch.cuda.synchronize()
         walls.append(time.perf_counter() - t0)
         rv.barrier()
     dt = rv.reduce_max(sorted(walls)[len(walls) // 2])
+    if args.dump_outputs:      # the last timed step's (obs_n, reward_n, done_n) as env.step returned them
+        write_outputs(_outputs(torch, ret[0], torch.stack(list(ret[1])), torch.stack(list(ret[2])), env.world.pos, env.world.vel),
+                      args.dump_outputs, "" if world == 1 else "rank%d_" % rank)
+    if not args.full:
+        if rank == 0:
+            A, Lm = len(env.world.agents), len(env.world.landmarks)
+            print(json.dumps({
+                "metric": "env steps/sec (whole node), %s N=%d, batch=%d per GPU" % (args.scenario, A, B),
+                "value": B * K * world / dt, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
+                "ms_per_step": dt * 1e3 / K, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                "dtype": "f32", "data": "synthetic", "timed_steps": K, "timed_region_s": dt,
+                "config": {"workload": "%s A=%d L=%d, %d worlds/GPU, generic path (torch callbacks + mpe_world_step), "
+                                       "random one-hot actions, reset every %d steps" % (args.scenario, A, Lm, B, EP),
+                           "batch_per_gpu": B, "global_batch": B * world, "mode": "api-generic"}}))
+        return None
     # the same step captured once into a HIP graph (GraphedStep): one replay per step instead of ~100 launches
     from multiagent_particle_envs_amd import GraphedStep
     gs = GraphedStep(env, pool[0])
@@ -601,6 +623,203 @@ def served_timed(torch, rv, roll, B, region_ms, repeats):
             "launches_in_region": len(ev)}
 
 
+PROBE_STEPS = 2000          # --commands auto without --full: steps each way runs before the faster one is timed
+DUMP_BYTES = 64 << 20       # --dump-outputs: at most this many bytes in all (a seeded sample of the worlds beyond it)
+
+
+def _outputs(torch, obs_n, rew, done, pos, vel):
+    """One step's outputs as a caller receives them, copied to the host: obs<i> [B, D_i], rew / done [A, B], pos / vel (state)."""
+    torch.cuda.synchronize()
+    d = {"obs%d" % i: o.float().cpu().numpy() for i, o in enumerate(obs_n)}
+    d.update(rew=rew.float().cpu().numpy(), done=done.float().cpu().numpy(), pos=pos.float().cpu().numpy(),
+             vel=vel.float().cpu().numpy())
+    return d
+
+
+def _concat_outputs(parts):
+    """Outputs of S sub-batches (one per stream) as one batch: worlds are axis 0 of obs, the last axis of everything else."""
+    if len(parts) == 1:
+        return parts[0]
+    import numpy as np
+    return {k: np.concatenate([p[k] for p in parts], axis=0 if k.startswith("obs") else -1) for k in parts[0]}
+
+
+def sample_outputs(d, limit=DUMP_BYTES, seed=0):
+    """The dump as written: everything when it fits in `limit` bytes, else the same fixed, seeded sample of worlds from every
+    array (sorted; their numbers in `world_index`)."""
+    import numpy as np
+    total = sum(v.nbytes for v in d.values())
+    if total <= limit:
+        return d
+    B = d["rew"].shape[-1]
+    m = max(1, int(B * (limit - 8 * B) / total))
+    idx = np.sort(np.random.RandomState(seed).choice(B, m, replace=False))
+    out = {k: (v[idx] if k.startswith("obs") else v[..., idx]) for k, v in d.items()}
+    out["world_index"] = idx.astype(np.float64)
+    return out
+
+
+def write_outputs(d, path, prefix=""):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in sample_outputs(d).items():
+        np.save(os.path.join(path, prefix + k + ".npy"), v)
+
+
+def _graph_period(roll):
+    """Steps after which a captured graph of consecutive steps repeats itself: lcm(episode_len, move pool, 2)."""
+    p = 2
+    for r in roll.rollouts:
+        for n in (r.episode_len, len(r.pool)):
+            if n:
+                p = p * n // math.gcd(p, n)
+    return p
+
+
+class LaunchedRegion(object):
+    """The headline's timed region with the steps LAUNCHED.  Built: W warm-up steps, and in graph mode the K steps captured as HIP
+    graphs of at most MAX_GRAPH_STEPS consecutive steps (a chunk of whole periods, replayed K // chunk times, and one graph for the
+    rest), each replayed once untimed.  probe(n): the chunk replayed until n steps have run -> seconds per step (which way of issuing
+    the steps is faster).  timed(): exactly K consecutive steps between barriers and synchronisations."""
+
+    def __init__(self, leg, torch, rv, mode, protocol, K, W):
+        self.leg, self.torch, self.rv, self.mode, self.K = leg, torch, rv, mode, K
+        self.roll = roll = leg.roll(protocol)
+        if mode == "fused":
+            leg.fused_steps(roll, W)
+        else:
+            roll.enqueue(W)
+        torch.cuda.synchronize()
+        self.last, self.plan, self.replays = None, [], None
+        if mode == "graph":
+            per = _graph_period(roll)
+            self.chunk = min(K, max(per, MAX_GRAPH_STEPS // per * per))
+            for steps, times in ((self.chunk, K // self.chunk), (K % self.chunk, 1)):
+                if steps and times:
+                    t0 = roll.rollouts[0].t
+                    self.plan.append((roll.capture(steps), times))
+                    self.last = t0 + steps - 1          # the global step the last replay of this graph ends on
+            for g, _ in self.plan:
+                g.replay()
+            torch.cuda.synchronize()
+            self.replays = sum(times for _, times in self.plan)
+        else:
+            self.body = leg.body(mode, protocol, K)
+
+    def _run(self):
+        if self.mode != "graph":
+            return self.body()
+        for g, times in self.plan:
+            for _ in range(times):
+                g.replay()
+
+    def probe(self, n):
+        assert self.mode == "graph"
+        reps = max(1, int(math.ceil(n / float(self.chunk))))
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            self.plan[0][0].replay()
+        self.torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / (reps * self.chunk)
+
+    def timed(self, dump=False):
+        """-> dict(dt: seconds, max over ranks; wall: this rank's; ev_ms: HIP-event ms; replays; out: the last step's outputs)."""
+        torch, leg, rv = self.torch, self.leg, self.rv
+        rv.barrier()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        self._run()
+        e1.record()
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        rv.barrier()
+        out = None
+        if dump and self.mode in ("api", "host"):
+            raise SystemExit("bench.py: --dump-outputs takes --mode graph, eager or fused (or the step server)")
+        if dump and self.mode == "fused":
+            k = (self.K - 1) % (leg.EP or 25)       # fused_steps: launches of up to episode_len steps, step j of a launch in block j
+            out = _concat_outputs([_outputs(torch, tr.obs[k], tr.rew[k], tr.done[k], e.world.pos, e.world.vel)
+                                   for tr, e in zip(leg.trajs, leg.envs)])
+        elif dump:
+            last = self.roll.rollouts[0].t - 1 if self.last is None else self.last
+            out = _concat_outputs([_outputs(torch, r.env._sets[last & 1].obs_n, r.env._sets[last & 1].rew, r.env._sets[last & 1].done,
+                                            r.world.pos, r.world.vel) for r in self.roll.rollouts])
+        return {"dt": rv.reduce_max(wall), "wall": wall, "ev_ms": e0.elapsed_time(e1), "replays": self.replays, "out": out}
+
+
+def _served_tail(torch, roll, r):
+    """The last r < episode_len steps of a served timed region that is not whole episodes (ServedRollout.enqueue serves whole
+    ones): one more server launch of r steps, the episode's block draw (at the graph protocol's frozen step numbers, as the
+    captured halves draw it) and ONE doorbell for its r steps, all on the commanding stream."""
+    from multiagent_particle_envs_amd import _abi
+    import ctypes as C
+    dev, EP, srv = roll.world.device, roll.EP, roll.srv
+    caller = torch.cuda.current_stream(dev)
+    roll.cmd.wait_stream(caller)
+    with torch.cuda.stream(roll.cmd):
+        srv.start(r)
+        h = (roll.t // EP) & 1
+        if roll.t >= 2 * EP:
+            srv.wait(roll.t - EP)      # the episode that read this half is complete
+        t = h * EP if roll._graphs is not None else roll.t
+        _abi.check(roll._L.mpe_random_actions_block(roll.moves[h * EP].data_ptr(), None, roll.A, roll.B, roll.seed, int(t), EP,
+                                                    int(roll.world.world_offset), _abi.raw_stream(dev)), "mpe_random_actions_block")
+        _abi.check(roll._L.mpe_step_server_ring(C.byref(srv._srv), int(r), _abi.raw_stream(dev)), "mpe_step_server_ring")
+        srv.commanded += int(r)
+        roll.t += int(r)
+        srv.join()
+    caller.wait_stream(roll.cmd)
+
+
+class ServedRegion(object):
+    """The headline's timed region with the steps COMMANDED to the step server (a brought-up ServedRollout).  Built: W warm-up
+    steps (whole episodes).  probe(n): n steps (whole episodes) -> seconds per step.  timed(): exactly K steps between barriers and
+    synchronisations -- whole episodes through ServedRollout.enqueue, the rest as one more launch (_served_tail)."""
+
+    def __init__(self, torch, rv, roll, W):
+        self.torch, self.rv, self.roll = torch, rv, roll
+        roll.enqueue(max(1, -(-W // roll.EP)) * roll.EP)
+        torch.cuda.synchronize()
+        roll.srv.check()
+
+    def probe(self, n):
+        n = max(1, n // self.roll.EP) * self.roll.EP
+        t0 = time.perf_counter()
+        self.roll.enqueue(n)
+        self.torch.cuda.synchronize()
+        self.roll.srv.check()
+        return (time.perf_counter() - t0) / n
+
+    def timed(self, K, events=False, dump=False):
+        """events: the server launches' HIP-event durations (the roofline of --full).
+        -> dict(dt, n, rate, launch_us, steps_per_launch, launches_in_region, out) -- served_timed's keys."""
+        torch, rv, roll = self.torch, self.rv, self.roll
+        EP = roll.EP
+        roll.srv.launch_events = [] if events else None
+        rv.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if K - K % EP:
+            roll.enqueue(K - K % EP)
+        if K % EP:
+            _served_tail(torch, roll, K % EP)
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        rv.barrier()
+        roll.srv.check()
+        ev = [(e0.elapsed_time(e1) * 1e3, T) for e0, e1, T in roll.srv.launch_events] if events else []
+        roll.srv.launch_events = None
+        out = None
+        if dump:
+            obs_n, rew, done = roll.srv.outputs(roll.srv.served_to - 1)
+            out = _outputs(torch, obs_n, rew, done, roll.world.pos, roll.world.vel)
+        return {"dt": rv.reduce_max(wall), "wall": wall, "n": K, "rate": [roll.B * K / wall] * 3,
+                "launch_us": sum(u for u, _ in ev) / len(ev) if ev else None,
+                "steps_per_launch": sum(T for _, T in ev) / float(len(ev)) if ev else None,
+                "launches_in_region": len(ev) if ev else None, "out": out}
+
+
 def served_leg(torch, mpe, scenario, agents, B, EP, seed, region_ms, repeats=3, kw=None, per_step_doorbells=True, rv=None):
     """The headline protocol through the STEP SERVER (rollout.ServedRollout; include/mpe_hip.h: mpe_step_server_*): fresh moves
     for every step (one block draw per episode), a reset every EP steps (the server's in-launch reset), every step's rows /
@@ -927,9 +1146,8 @@ def compact_line(out, full_path=None):
     if out.get("n_gpus", 1) > 1:
         line["config"]["sharding"] = cfg.get("sharding")
     line["config"]["workload"] = str(cfg.get("workload_short") or cfg.get("workload", ""))[:150]
-    line["config"]["timed_region"] = ("ms_per_step = timed_region_s / timed_steps; >= %.1f s of back-to-back steps, median of %s repeats, "
-                                      "max over ranks (--steps / --warmup do not size it)"
-                                      % (cfg.get("region_ms", MIN_REGION_MS) * 1e-3, cfg.get("repeats")))
+    line["config"]["timed_region"] = ("ms_per_step = timed_region_s / timed_steps; --steps consecutive steps after --warmup ones, "
+                                      "max over ranks")
     if cfg.get("scaling_diagnostic"):
         line["config"]["value_over_n_times_rank0_solo"] = sig(cfg["scaling_diagnostic"]["value_over_n_times_rank0_solo"], 4)
     if out.get("per_gpu_value") and out.get("n_gpus", 1) > 1:
@@ -1062,6 +1280,13 @@ def parse_args(argv=None):
                          "line is its compact form (< %d bytes)" % LINE_BUDGET)
     ap.add_argument("--streams", type=int, default=1,
                     help="cut the per-GPU batch into this many independent sub-batches, one HIP stream each")
+    ap.add_argument("--full", action="store_true",
+                    help="the whole record: both ways of issuing the headline's steps timed, roofline, secondary legs, other "
+                         "configs, CPU baseline, the full record in --full-json (without it: the headline alone)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: what the timed path computed in its last step (obs<i>, rew, done, pos, vel), "
+                         "one float32 DIR/<name>.npy each, at most %d MB in all (a seeded sample of the worlds beyond that)"
+                         % (DUMP_BYTES >> 20))
     return ap.parse_args(argv)
 
 
@@ -1101,6 +1326,65 @@ def launch_ranks(args):
         sys.stderr.write("bench.py: ranks reported n_gpus=%r for --gpus %d\n" % (line.get("n_gpus"), n))
         return 1
     print(lines[0])
+    return 0
+
+
+def plain_run(args, torch, mpe, leg, rv, rank, world, kname):
+    """The headline alone (no --full): set up, warm up, time exactly --steps steps, write --dump-outputs, print the line.  With
+    --commands auto both ways of issuing the steps are set up and probed (PROBE_STEPS each, untimed for the line) and the faster
+    one is timed: the line's value is the faster, as in the full record.  -> exit status."""
+    B, K, W, EP = args.batch, args.steps, args.warmup, args.episode_len
+    serve = args.commands != "launched" and args.mode == "graph" and args.protocol == "fresh" and args.streams == 1 and EP and \
+        kname == "mpe::k_split" and leg.env._comm is None
+    region_s, served_err = None, None
+    if serve:
+        try:
+            from multiagent_particle_envs_amd.rollout import ServedRollout
+            env_s = mpe.make_env(args.scenario, batch_size=B, seed=args.seed, **leg.kw)
+            env_s.world.world_offset = rank * B
+            roll_s = ServedRollout(env_s, episode_len=EP, timeout_s=4.0, graphs=True, ring_ahead=True)
+            roll_s.enqueue(2 * EP * 4)
+            torch.cuda.synchronize()
+            roll_s.srv.check()
+            region_s = ServedRegion(torch, rv, roll_s, W)
+        except Exception as e:
+            served_err = "%s: %s" % (type(e).__name__, str(e)[:300])
+            region_s = None
+            torch.cuda.synchronize()
+        if rv.reduce_max(1.0 if region_s is None else 0.0) > 0:      # any rank without a server: nobody uses one
+            region_s = None
+            served_err = served_err or "another rank could not bring its step server up"
+    region_l = None
+    if region_s is None or args.commands == "auto":
+        region_l = LaunchedRegion(leg, torch, rv, args.mode, args.protocol, K, W)
+    use_served = region_s is not None
+    if region_s is not None and region_l is not None:
+        slower = region_s.probe(PROBE_STEPS) >= region_l.probe(PROBE_STEPS)
+        use_served = rv.reduce_max(1.0 if slower else 0.0) == 0
+    dump = bool(args.dump_outputs)
+    r = region_s.timed(K, dump=dump) if use_served else region_l.timed(dump=dump)
+    if dump:
+        write_outputs(r["out"], args.dump_outputs, "" if world == 1 else "rank%d_" % rank)
+    if rank == 0:
+        dt = r["dt"]
+        line = {"metric": "env steps/sec (whole node), %s N=%d, batch=%d per GPU" % (args.scenario, leg.A, B),
+                "value": sig(B * K * world / dt), "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
+                "ms_per_step": sig(dt * 1e3 / K), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                "dtype": "f32", "data": "synthetic", "timed_steps": K, "timed_region_s": sig(dt, 4)}
+        line["config"] = {
+            "workload": "%s A=%d L=%d, %d worlds/GPU, %s one-hot moves, reset every %d steps; %s"
+                        % (args.scenario, leg.A, leg.Lm, B, "fresh" if args.protocol == "fresh" else "resident", EP,
+                           "steps commanded to the step server" if use_served else "one mpe_step launch per step"),
+            "protocol": "fresh, step-server (one doorbell per episode)" if use_served else args.protocol,
+            "batch_per_gpu": B, "global_batch": B * world, "mode": "step-server" if use_served else args.mode,
+            "commands": args.commands, "timed_region": "ms_per_step = timed_region_s / timed_steps; --steps consecutive steps after "
+                                                      "--warmup ones, max over ranks; --full for the whole record",
+            "barrier_backend": rv.backend}
+        if region_l is not None and region_l.replays is not None and not use_served:
+            line["config"]["graph_replays_in_timed_region"] = region_l.replays
+        if served_err:
+            line["config"]["step_server_error"] = served_err[:200]
+        print(json.dumps(line, separators=(",", ":")))
     return 0
 
 
@@ -1186,16 +1470,20 @@ def main():
             sys.stderr.write("bench.py: --gpus %d but ranks share a GPU (%s) -- a mis-mapped job would print n_gpus=%d for fewer "
                              "GPUs; refusing (use --all-ranks-on-gpu0 for the one-GPU rehearsal)\n" % (world, dup, world))
         return leave(3)
+    if not args.full:
+        return leave(plain_run(args, torch, mpe, leg, rv, rank, world, kname))
+    Ks = min(K, MAX_GRAPH_STEPS)      # the secondary legs' graphs (replayed to fill their regions, whatever --steps is)
     solo_rate = None
     if world > 1:
         # rank 0 runs one repeat of the SAME timed region alone (the others wait at a barrier): what one GPU of this node
         # does when its neighbours are idle -- the reference point of the N-GPU line (config.scaling_diagnostic)
         lone = sharding.Rendezvous(0, 1, dev)
-        if rank == 0:
-            d1, R1, _, _ = leg.timed(torch, lone, dev, args.mode, args.protocol, K, W, 1, min(args.region_ms, 1000.0))
-            solo_rate = B * K * R1 / d1
+        if rank == 0:      # (>= --region-ms of the headline's steps, capped at 1 s)
+            d1, R1, _, _ = leg.timed(torch, lone, dev, args.mode, args.protocol, Ks, W, 1, min(args.region_ms, 1000.0))
+            solo_rate = B * Ks * R1 / d1
         rv.barrier()
-    dt, R, ev_ms, rate = leg.timed(torch, rv, dev, args.mode, args.protocol, K, W, args.repeats, args.region_ms)
+    head = LaunchedRegion(leg, torch, rv, args.mode, args.protocol, K, W).timed(dump=bool(args.dump_outputs))
+    dt, R, ev_ms, rate = head["dt"], 1, head["ev_ms"], [B * K / head["wall"]] * 3
     done_at("headline_timed_region")
     k_us = leg.kernel_time_us(torch, args.mode)
     head_timing = leg.last_kernel_timing
@@ -1232,7 +1520,7 @@ def main():
                         served_err = "%s: %s" % (type(e).__name__, str(e)[:300])
                 rv.barrier()
             try:
-                served = served_timed(torch, rv, roll_s, B, args.region_ms, args.repeats)
+                served = ServedRegion(torch, rv, roll_s, W).timed(K, events=True, dump=bool(args.dump_outputs))
                 served["probe"] = roll_s.srv.stream_probe
             except Exception as e:
                 served_err = "%s: %s" % (type(e).__name__, str(e)[:300])
@@ -1242,17 +1530,21 @@ def main():
             served = None
         done_at("headline_step_server")
     use_served = served is not None and (args.commands == "served" or served["dt"] / served["n"] < dt / (K * R))
+    if args.dump_outputs:
+        write_outputs((served if use_served else head)["out"], args.dump_outputs, "" if world == 1 else "rank%d_" % rank)
+    for rec in (head, served):
+        (rec or {}).pop("out", None)
     extra = {}
     solo = world == 1 and not args.no_extra and args.streams == 1
     SR = SIDE_REGION_MS
 
     if solo and can_fuse and args.mode != "fused":
-        dtf, Rf, _, rf = leg.timed(torch, rv, dev, "fused", "resident", K, W, 3, SR)
+        dtf, Rf, _, rf = leg.timed(torch, rv, dev, "fused", "resident", Ks, W, 3, SR)
         kf = leg.kernel_time_us(torch, "fused")
         extra["fused_rollout"] = {
             "what": "mpe_rollout_random: one launch per %d-step episode, state kept on chip (registers / LDS), moves drawn "
                     "in-kernel, every step's obs/rew/done written to its own trajectory block" % (EP or 25),
-            "value": B * K * Rf / dtf, "unit": "env-steps/s", "ms_per_step": dtf * 1e3 / (K * Rf), "repeats": stats(rf),
+            "value": B * Ks * Rf / dtf, "unit": "env-steps/s", "ms_per_step": dtf * 1e3 / (Ks * Rf), "repeats": stats(rf),
             "kernel_us_per_step": kf,
             "compulsory_bytes_per_env_step": compulsory_roll,
             "achieved_GBps_compulsory": compulsory_roll * B / (kf * 1e-6) / 1e9,
@@ -1260,21 +1552,21 @@ def main():
             "achieved_GBps_at_per_step_convention": bytes_step * B / (kf * 1e-6) / 1e9,
             "per_step_convention_bytes": bytes_step}
     if solo and args.mode == "graph" and args.protocol == "fresh":
-        dtr, Rr, _, rr = leg.timed(torch, rv, dev, "graph", "resident", K, W, 3, SR)
+        dtr, Rr, _, rr = leg.timed(torch, rv, dev, "graph", "resident", Ks, W, 3, SR)
         extra["moves_resident"] = {
             "what": "the same K-step graph with the moves read from a resident ring of 16 tensors drawn once (no redraw "
                     "launches in the timed region): the step as a policy-driven caller sees it",
-            "value": B * K * Rr / dtr, "unit": "env-steps/s", "ms_per_step": dtr * 1e3 / (K * Rr), "repeats": stats(rr)}
+            "value": B * Ks * Rr / dtr, "unit": "env-steps/s", "ms_per_step": dtr * 1e3 / (Ks * Rr), "repeats": stats(rr)}
 
     if solo and args.mode == "graph" and args.protocol == "fresh" and leg.roll("resident").rollouts[0].pool_c is None:
         # the reference's other action format (`discrete_action_input`, environment.py:161-167): int32 ids, 4 bytes per agent
-        dti, Ri, _, ri = leg.timed(torch, rv, dev, "graph", "fresh_ids", K, W, 3, SR)
+        dti, Ri, _, ri = leg.timed(torch, rv, dev, "graph", "fresh_ids", Ks, W, 3, SR)
         ki = leg.kernel_time_us(torch, "graph", protocol="resident_ids")
         bytes_ids = bytes_step - 4 * A * (_abi_action_dim() - 1)
         extra["int_action_ids"] = {
             "what": "the headline protocol with the moves handed over as int32 ids [A][B] (discrete_action_input; SURVEY 8d: "
                     "subtract 5A*4 B, add A*4 B) instead of one-hot fp32 rows: fresh ids for every step, reset every %d" % EP,
-            "value": B * K * Ri / dti, "unit": "env-steps/s", "ms_per_step": dti * 1e3 / (K * Ri), "repeats": stats(ri),
+            "value": B * Ks * Ri / dti, "unit": "env-steps/s", "ms_per_step": dti * 1e3 / (Ks * Ri), "repeats": stats(ri),
             "kernel_us_per_launch": ki, "algorithmic_bytes_per_env_step": bytes_ids,
             "achieved_GBps": B * bytes_ids / ki / 1e3, "frac": B * bytes_ids / ki / 1e3 / HBM_PEAK_GBS}
         leg.rolls.pop("fresh_ids", None)
@@ -1282,7 +1574,7 @@ def main():
 
     if solo and args.mode == "graph":
         # the drop-in API itself: env.reset() / env.step() called from Python, one launch per call, moves from a resident ring
-        na = max(K, 20000)
+        na = max(Ks, 20000)
         dta, _, _, ra = leg.timed(torch, rv, dev, "api", "resident", na, W, 3)
         extra["python_api"] = {
             "what": "MultiAgentEnv.step() / reset() called from Python (the drop-in API; host in the loop, no graph): "
@@ -1429,8 +1721,8 @@ def main():
                        "workload_short": "%s A=%d L=%d, %d worlds/GPU, %s one-hot moves, reset every %d steps; one mpe_step launch per step"
                                          % (args.scenario, A, Lm, B, "fresh" if args.protocol == "fresh" else "resident", EP),
                        "protocol": args.protocol, "batch_per_gpu": B, "global_batch": B * world, "mode": args.mode,
-                       "graph_replays_in_timed_region": R, "timed_steps": K * R,
-                       "timed_region_s": dt, "repeats": args.repeats, "region_ms": args.region_ms, "streams_per_gpu": args.streams,
+                       "graph_replays_in_timed_region": head["replays"], "timed_steps": K * R,
+                       "timed_region_s": dt, "repeats": 1, "streams_per_gpu": args.streams,
                        "sharding": "worlds by batch index, no collective on the step path",
                        "barrier_backend": rv.backend, "barrier_note": rv.note,
                        "launcher": "torch.distributed.run / env" if world > 1 and not os.environ.get("MPE_SELF_SPAWNED") else

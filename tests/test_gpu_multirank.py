@@ -101,7 +101,8 @@ def test_bench_two_ranks_one_gpu(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--batch", str(B),
-           "--backend", "gloo", "--all-ranks-on-gpu0", "--no-cpu-baseline", "--region-ms", "50", "--dump-state", str(tmp_path), "--full-json", str(tmp_path / "full.json")]
+           "--backend", "gloo", "--all-ranks-on-gpu0", "--no-cpu-baseline", "--region-ms", "50", "--dump-state", str(tmp_path), "--full-json", str(tmp_path / "full.json"),
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=_bench_env(), timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -118,7 +119,8 @@ def test_bench_gpus_2_without_a_launcher_starts_its_own_ranks(tmp_path):
     every rank, carry the barrier over gloo and still produce the line -- with the CPU baseline and the per-GPU roofline."""
     B = 4096
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--batch", str(B),
-           "--all-ranks-on-gpu0", "--cpu-seconds", "1", "--region-ms", "50", "--dump-state", str(tmp_path), "--full-json", str(tmp_path / "full.json")]
+           "--all-ranks-on-gpu0", "--cpu-seconds", "1", "--region-ms", "50", "--dump-state", str(tmp_path), "--full-json", str(tmp_path / "full.json"),
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=_bench_env(), timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -139,7 +141,8 @@ def test_bench_eight_ranks_rehearsal_on_one_gpu(tmp_path):
     import time
     B = 4096
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--batch", str(B),
-           "--all-ranks-on-gpu0", "--backend", "gloo", "--no-cpu-baseline", "--region-ms", "50", "--dump-state", str(tmp_path), "--full-json", str(tmp_path / "full.json")]
+           "--all-ranks-on-gpu0", "--backend", "gloo", "--no-cpu-baseline", "--region-ms", "50", "--dump-state", str(tmp_path), "--full-json", str(tmp_path / "full.json"),
+           "--full"]
     t0 = time.time()
     r = subprocess.run(cmd, capture_output=True, text=True, env=_bench_env(), timeout=900, cwd=ROOT)
     wall = time.time() - t0
@@ -170,11 +173,11 @@ def test_bench_more_gpus_than_the_box_has_is_an_error():
 
 
 def test_bench_single_gpu_line_carries_the_contract():
-    """`python bench.py --steps K --warmup W` (N = 1, as the driver runs it): ONE JSON line with the contract's keys, the
-    HBM roofline object and the CPU baseline object; value == worlds x steps / time."""
+    """`python bench.py --full --steps K --warmup W` (N = 1): ONE JSON line with the contract's keys, the HBM roofline object
+    and the CPU baseline object; value == worlds x steps / time."""
     env = dict(os.environ)
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--no-extra",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20000", "--warmup", "3", "--no-extra",
                         "--cpu-seconds", "1", "--repeats", "3", "--region-ms", "100"], capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -183,7 +186,8 @@ def test_bench_single_gpu_line_carries_the_contract():
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in out, k
-    assert out["n_gpus"] == 1 and out["steps"] == 10 and out["warmup"] == 3 and out["higher_is_better"] is True
+    assert out["n_gpus"] == 1 and out["steps"] == 20000 and out["warmup"] == 3 and out["higher_is_better"] is True
+    assert out["timed_steps"] == 20000
     assert out["unit"] == "env-steps/s" and out["dtype"] == "f32" and out["data"] == "synthetic" and out["vs_baseline"] is None
     assert "workload" in out["config"] and "model" not in out["config"] and out["config"]["batch_per_gpu"] == 65536
     assert abs(out["value"] - 65536 / (out["ms_per_step"] * 1e-3)) <= 1e-4 * out["value"]
@@ -200,3 +204,42 @@ def test_bench_single_gpu_line_carries_the_contract():
     assert roof["algorithmic_bytes_per_env_step"] == 411 and (roof["traffic"] is None or roof["traffic"] > 2e7)
     cpu = out["cpu_baseline"]
     assert cpu["kind"] in ("port", "reference") and cpu["value"] > 0 and cpu["cores"] >= 1 and cpu["unit"] == "env-steps/s" and cpu["sample"]
+
+
+def _plain(tmp_path, tag, *extra):
+    env = dict(os.environ)
+    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
+    d = tmp_path / tag
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3010", "--warmup", "7",
+                        "--dump-outputs", str(d)] + list(extra), capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0]), {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+
+
+def test_bench_plain_run_times_exactly_the_steps_and_dumps_its_last_step(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (no --full): the headline alone -- exactly K timed
+    steps, ms_per_step their time / K, no roofline / CPU baseline legs -- and the last timed step's outputs as float32 .npy
+    files (<= 64 MB); the same arguments compute the same outputs again, whichever way the steps were issued."""
+    out, d = _plain(tmp_path, "a")
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "timed_steps", "timed_region_s"):
+        assert k in out, k
+    assert "roofline" not in out and "cpu_baseline" not in out and "full_record" not in out
+    assert out["steps"] == out["timed_steps"] == 3010 and out["warmup"] == 7 and out["n_gpus"] == 1 and out["unit"] == "env-steps/s"
+    assert out["dtype"] == "f32" and out["higher_is_better"] is True and out["config"]["batch_per_gpu"] == 65536
+    assert out["config"]["mode"] in ("graph", "step-server")
+    assert abs(out["value"] - 65536 / (out["ms_per_step"] * 1e-3)) <= 1e-4 * out["value"]
+    assert abs(3010 * out["ms_per_step"] * 1e-3 / out["timed_region_s"] - 1) < 1e-3
+    assert sorted(d) == ["done", "obs0", "obs1", "obs2", "pos", "rew", "vel"]
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in d.values())
+    assert sum(v.nbytes for v in d.values()) <= 64 << 20
+    assert d["rew"].shape == (3, 65536) and d["obs0"].shape == (65536, 18) and d["done"].shape == (3, 65536)
+    assert d["obs0"].std() > 0 and d["rew"].std() > 0
+    for mode in ("launched", "served"):      # each way on its own: the same steps twice give the same outputs, bit for bit
+        o1, d1 = _plain(tmp_path, mode + "1", "--commands", mode)
+        o2, d2 = _plain(tmp_path, mode + "2", "--commands", mode)
+        assert o1["config"]["mode"] == o2["config"]["mode"] == ("graph" if mode == "launched" else "step-server")
+        assert all(np.array_equal(d1[k], d2[k]) for k in d1), mode
+

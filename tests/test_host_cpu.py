@@ -298,6 +298,29 @@ def test_bench_two_point_slope_rejects_a_bad_point():
     assert ok and -0.05 < fixed < 0.0
 
 
+def test_bench_dump_outputs_is_capped_by_a_fixed_sample_of_worlds(tmp_path):
+    """--dump-outputs writes every array whole while they fit in 64 MB, else the SAME seeded sample of worlds from each (their
+    numbers in world_index) -- float32 / float64 files only; --full is off by default."""
+    import bench
+    assert not bench.parse_args([]).full and bench.parse_args(["--full"]).full
+    assert bench.parse_args(["--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path)
+    rs = np.random.RandomState(0)
+    small = {"obs0": rs.rand(64, 18).astype(np.float32), "rew": rs.rand(3, 64).astype(np.float32),
+             "pos": rs.rand(6, 2, 64).astype(np.float32)}
+    assert bench.sample_outputs(small) is small
+    B = 1 << 20
+    big = {"obs0": np.arange(B, dtype=np.float32)[:, None] * np.ones((1, 18), np.float32), "rew": np.tile(np.arange(B, dtype=np.float32), (3, 1)),
+           "pos": np.tile(np.arange(B, dtype=np.float32), (6, 2, 1))}
+    a, b = bench.sample_outputs(big), bench.sample_outputs(big)
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BYTES and a["world_index"].dtype == np.float64
+    w = a["world_index"]
+    assert np.array_equal(w, b["world_index"]) and np.all(np.diff(w) > 0) and 0 < len(w) < B
+    assert np.array_equal(a["obs0"][:, 5], w) and np.array_equal(a["rew"][2], w) and np.array_equal(a["pos"][4, 1], w)
+    bench.write_outputs(small, str(tmp_path / "d"))
+    assert sorted(os.listdir(str(tmp_path / "d"))) == ["obs0.npy", "pos.npy", "rew.npy"]
+    assert np.array_equal(np.load(str(tmp_path / "d" / "rew.npy")), small["rew"])
+
+
 def test_bench_refuses_ranks_that_share_a_gpu():
     """bench.py --gpus N checks, before measuring, that the N ranks drive N different GPUs (UUID, else PCI address): a
     mis-mapped job must not print n_gpus = N for fewer GPUs."""

@@ -1,15 +1,11 @@
-"""Build container only: the oracle against the reference RUN LIVE, on seeds and actions the committed fixtures do not hold.
+"""The oracle against the reference on worlds the other fixtures do not hold.
 
-tests/golden/*.npz pin the oracle to recordings; this test closes the remaining gap ("the oracle fits the fixtures") by
-recording fresh worlds from the unmodified /root/reference in a subprocess (tests/golden/gen_golden.py's `record`, the same
-recorder that made the fixtures, with the shape-only gym stub) -- seeds derived from the run's date, so every day tests
-new worlds -- and replaying them through the fp64 batched oracle and the per-object loop port.  /root/reference does not
-exist on the GPU box: there the test is skipped (nothing on the GPU side reads the reference).
+tests/golden/*.npz pin the oracle to recordings; this test closes the remaining gap ("the oracle fits the fixtures") with worlds
+recorded from the unmodified reference on seeds of their own (tests/golden/live_*.npz, written by tests/golden/gen_golden_live.py
+with the recorders that made the other fixtures and the shape-only gym stub), replayed through the fp64 batched oracle, the C
+restatement, the per-object loop port and the host callbacks of the six other scenarios.
 """
-import datetime
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,53 +14,31 @@ from oracle import spec as ospec
 from oracle.mpe_batched import BatchedOracle, seeded_initial_state
 from oracle.mpe_loop import LoopEnv
 
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "multiagent", "core.py")),
-                                reason="the reference tree exists in the build container only")
-
-RECORDER = r"""
-import sys, numpy as np
-sys.path.insert(0, %(golden)r)
-import gen_golden as gg
-base = int(sys.argv[1])
-jobs = {
-    "simple": gg.record("simple", gg.make_env("simple"), [base + k for k in range(6)], 30),
-    "simple_spread": gg.record("simple_spread", gg.make_env("simple_spread", benchmark=True), [base + 10 + k for k in range(9)], 20,
-                               squeeze_every=3, arng=np.random.RandomState(base)),
-    "simple_tag": gg.record("simple_tag", gg.make_env("simple_tag", benchmark=True), [base + 30 + k for k in range(9)], 20,
-                            squeeze_every=3, squeeze=0.25, arng=np.random.RandomState(base + 1)),
-    "simple_spread_n7": gg.record("simple_spread_n7", gg.spread_n(7), [base + 50 + k for k in range(4)], 8, squeeze_every=2,
-                                  squeeze=0.4, arng=np.random.RandomState(base + 2)),
-}
-for name, data in jobs.items():
-    np.savez(sys.argv[2] + "/" + name + ".npz", **data)
-"""
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 TOL = 1e-12
 
 
+def _live(name):
+    return dict(np.load(os.path.join(GOLDEN, "live_" + name + ".npz")))
+
+
 def _base_seed():
-    """The day's seed (yymmdd), or MPE_LIVE_SEED=<yymmdd> to replay the worlds of the day a failure was seen on."""
-    return int(os.environ.get("MPE_LIVE_SEED") or datetime.date.today().strftime("%y%m%d"))
+    """The day stamp the recorded worlds were drawn for (tests/golden/gen_golden_live.py)."""
+    return int(_live("simple")["live_seed"])
 
 
 def _close(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     assert a.shape == b.shape
     scale = np.maximum(1.0, np.abs(b))
-    assert np.all(np.abs(a - b) <= TOL * scale), "max scaled err %.3e (replay these worlds with MPE_LIVE_SEED=%d)" % (
+    assert np.all(np.abs(a - b) <= TOL * scale), "max scaled err %.3e (worlds of day stamp %d)" % (
         float(np.max(np.abs(a - b) / scale)), _base_seed())
 
 
 @pytest.fixture(scope="module")
-def fresh(tmp_path_factory):
-    out = tmp_path_factory.mktemp("live_reference")
-    base = _base_seed() * 100     # new worlds every day, reproducible within one (and replayable: MPE_LIVE_SEED)
-    env = dict(os.environ, SUPPRESS_MA_PROMPT="1", PYTHONDONTWRITEBYTECODE="1", PYTHONWARNINGS="ignore")
-    r = subprocess.run([sys.executable, "-c", RECORDER % {"golden": os.path.join(ROOT, "tests", "golden")}, str(base), str(out)],
-                       capture_output=True, text=True, env=env, timeout=600, cwd=str(out))
-    assert r.returncode == 0, r.stderr[-3000:]
-    return lambda name: dict(np.load(os.path.join(str(out), name + ".npz")))
+def fresh():
+    return _live
 
 
 CASES = [("simple", ospec.simple(), False), ("simple_spread", ospec.simple_spread(3), True), ("simple_tag", ospec.simple_tag(), True),
@@ -139,33 +113,10 @@ def test_loop_port_replays_fresh_reference_worlds(fresh):
 
 
 # ---- the six other scenarios: the product's own reset_world / observation / reward (torch, on the CPU) against the
-#      reference run live -- the check tests/test_f3_scenarios.py makes against the committed f3_*.npz, on fresh seeds ----------
-RECORDER_F3 = r"""
-import sys, numpy as np
-sys.path.insert(0, %(golden)r)
-import gen_golden_scenarios as gs
-base = int(sys.argv[1])
-for k, (name, sq) in enumerate([("simple_adversary", 0), ("simple_push", 0), ("simple_speaker_listener", 0), ("simple_reference", 0),
-                                ("simple_crypto", 0), ("simple_world_comm", 8)]):
-    data = gs.record(name, [base + 100 * k + j for j in range(64)], 6, squeeze_every=sq, stage=True)
-    np.savez(sys.argv[2] + "/f3_" + name + ".npz", **data)
-import gen_golden_shapes as gsh      # other team sizes: the reference's callbacks on resized agent lists
-for k, (name, A, nadv) in enumerate(gsh.SHAPES):
-    data = gs.record(name, [base + 1000 + 100 * k + j for j in range(32)], 4, squeeze_every=8 if name == "simple_world_comm" else 0,
-                     stage=True, env_factory=gsh.factory(name, A, nadv))
-    np.savez(sys.argv[2] + "/shape_" + name + "_" + str(A) + "_" + str(nadv) + ".npz", **data)
-"""
-
-
+#      reference on the recorded worlds -- the check tests/test_f3_scenarios.py makes against the committed f3_*.npz, on other seeds ---
 @pytest.fixture(scope="module")
-def fresh_f3(tmp_path_factory):
-    out = tmp_path_factory.mktemp("live_reference_f3")
-    base = _base_seed() * 1000 + 7
-    env = dict(os.environ, SUPPRESS_MA_PROMPT="1", PYTHONDONTWRITEBYTECODE="1", PYTHONWARNINGS="ignore")
-    r = subprocess.run([sys.executable, "-c", RECORDER_F3 % {"golden": os.path.join(ROOT, "tests", "golden")}, str(base), str(out)],
-                       capture_output=True, text=True, env=env, timeout=900, cwd=str(out))
-    assert r.returncode == 0, r.stderr[-3000:]
-    return lambda name: dict(np.load(os.path.join(str(out), name + ".npz")))
+def fresh_f3():
+    return _live
 
 
 def test_host_callbacks_of_the_other_six_scenarios_on_fresh_reference_worlds(fresh_f3):
@@ -176,7 +127,7 @@ def test_host_callbacks_of_the_other_six_scenarios_on_fresh_reference_worlds(fre
 
 def test_f3_oracle_replays_fresh_reference_worlds(fresh_f3):
     """oracle/mpe_f3.py (the fp64 restatement the GPU tests compare the six other scenarios' fused kernels with) against
-    the reference run live: 64 fresh worlds per scenario, staged like the fixtures, whole trajectories at 1e-12, and
+    the reference on 64 recorded worlds per scenario, staged like the fixtures, whole trajectories at 1e-12, and
     the seeded resets (np.random.choice picks, then agents, then landmarks)."""
     import test_oracle_golden as tg
     from oracle.mpe_f3 import seeded_initial_state_f3
@@ -186,8 +137,8 @@ def test_f3_oracle_replays_fresh_reference_worlds(fresh_f3):
         tg._replay_f3(spec, g)
         plain = np.flatnonzero(~g["staged"])
         pos, vel, choice = seeded_initial_state_f3(spec, g["seeds"])
-        assert np.array_equal(choice, g["choice"]), "MPE_LIVE_SEED=%d" % _base_seed()
-        assert np.array_equal(pos[plain], g["pos0"][plain]), "MPE_LIVE_SEED=%d" % _base_seed()
+        assert np.array_equal(choice, g["choice"]), "day stamp %d" % _base_seed()
+        assert np.array_equal(pos[plain], g["pos0"][plain]), "day stamp %d" % _base_seed()
 
 
 def test_f3_oracle_at_other_team_sizes_replays_fresh_reference_worlds(fresh_f3):
@@ -200,5 +151,5 @@ def test_f3_oracle_at_other_team_sizes_replays_fresh_reference_worlds(fresh_f3):
         tg._replay_f3(spec, g)
         plain = np.flatnonzero(~g["staged"])
         pos, vel, choice = seeded_initial_state_f3(spec, g["seeds"])
-        assert np.array_equal(choice, g["choice"]), "MPE_LIVE_SEED=%d" % _base_seed()
-        assert np.array_equal(pos[plain], g["pos0"][plain]), "MPE_LIVE_SEED=%d" % _base_seed()
+        assert np.array_equal(choice, g["choice"]), "day stamp %d" % _base_seed()
+        assert np.array_equal(pos[plain], g["pos0"][plain]), "day stamp %d" % _base_seed()

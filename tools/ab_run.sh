@@ -9,7 +9,7 @@ O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 for rep in $(seq 1 $REPS); do
   for v in "$@"; do
     if [ $v == base ]; then unset MPE_HIP_LIB; else export MPE_HIP_LIB=$R/multiagent_particle_envs_amd/lib/libmpe_hip_ab_$v.so; fi
-    timeout 300 python bench.py --no-cpu-baseline --no-extra --repeats 3 $ARGS > $O/${v}_$rep.json 2> $O/${v}_$rep.err
+    timeout 300 python bench.py --full --no-cpu-baseline --no-extra --repeats 3 $ARGS > $O/${v}_$rep.json 2> $O/${v}_$rep.err
     python - <<PY
 import json
 try:

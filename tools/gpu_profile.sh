@@ -11,7 +11,7 @@ run() {  # name, bench args...
   local name=$1; shift
   cd /tmp
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/$name -o x -- \
-      python $R/bench.py --no-cpu-baseline --no-extra --repeats 2 "$@" > $O/$name.bench.json 2> $O/$name.err
+      python $R/bench.py --full --no-cpu-baseline --no-extra --repeats 2 "$@" > $O/$name.bench.json 2> $O/$name.err
   cp $(find $O/$name -name "x_kernel_stats.csv" | head -1) $O/$name.kernel_stats.csv
   cd $R
   tools/pmc.sh ${TAG}_$name "$@" > /dev/null 2>&1

@@ -13,7 +13,7 @@ has() { [[ " $STEPS " == *" $1 "* ]]; }
 trace() {  # name, bench args...
   local name=$1; shift
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$name -o x -- \
-      python $R/bench.py --no-cpu-baseline --no-extra --repeats 2 "$@" > $O/trace_$name.bench.json 2> $O/trace_$name.err)
+      python $R/bench.py --full --no-cpu-baseline --no-extra --repeats 2 "$@" > $O/trace_$name.bench.json 2> $O/trace_$name.err)
   cp $(find $O/trace_$name -name "x_kernel_stats.csv" | head -1) $O/${name}_kernel_stats.csv 2>/dev/null
   rm -rf $O/trace_$name
   head -5 $O/${name}_kernel_stats.csv
@@ -23,7 +23,7 @@ if has test; then
   tail -15 $O/pytest.log
 fi
 if has bench; then
-  timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_20.json 2> $O/bench_20.err; echo "bench20 rc=$?"; tail -c 1500 $O/bench_20.err
+  timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_20.json 2> $O/bench_20.err; echo "bench20 rc=$?"; tail -c 1500 $O/bench_20.err
   python - <<PY
 import json
 try:
@@ -39,7 +39,7 @@ except Exception as e: print("parse failed", e)
 PY
 fi
 if has bench1000; then
-  timeout 600 python bench.py --steps 1000 --warmup 50 --no-extra --no-cpu-baseline > $O/bench_1000.json 2> $O/bench_1000.err; echo "bench1000 rc=$?"
+  timeout 600 python bench.py --full --steps 1000 --warmup 50 --no-extra --no-cpu-baseline > $O/bench_1000.json 2> $O/bench_1000.err; echo "bench1000 rc=$?"
   python -c "
 import json; d=json.loads(open('$O/bench_1000.json').read().strip().splitlines()[-1]); print('steps1000: value %.3f G ms/step %.5f' % (d['value']/1e9, d['ms_per_step']))"
 fi

@@ -7,7 +7,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o x -- python $R/bench.py --no-cpu-baseline --no-extra --repeats 2 "$@" > $O/bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o x -- python $R/bench.py --full --no-cpu-baseline --no-extra --repeats 2 "$@" > $O/bench.json 2> $O/bench.err
 find $O/prof -name "*.csv" | head; 
 python - <<PY
 import csv,glob,collections

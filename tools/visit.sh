@@ -20,13 +20,13 @@ for step in "$@"; do
            echo "pytest rc=$?"; tail -14 $O/pytest.log | cut -c1-250; grep real $O/pytest.time ;;
     testk) ( time timeout 1500 python -m pytest tests -m gpu -x -q -k "$rest" > $O/pytest_k.log 2>&1 ) 2> $O/pytest_k.time
            echo "pytest -k rc=$?"; tail -12 $O/pytest_k.log | cut -c1-250 ;;
-    bench) ( time timeout 900 python bench.py --steps 20 --warmup 5 --full-json $O/bench_full.json > $O/bench_line.json 2> $O/bench.err ) 2> $O/bench.time
+    bench) ( time timeout 900 python bench.py --full --steps 20 --warmup 5 --full-json $O/bench_full.json > $O/bench_line.json 2> $O/bench.err ) 2> $O/bench.time
            echo "bench rc=$? line bytes: $(wc -c < $O/bench_line.json)"; cat $O/bench_line.json; grep real $O/bench.time ;;
     trace) name=${rest%%:*}; a=${rest#*:}; [ "$a" = "$rest" ] && a=""; a=${a//,/ }
            (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$name -o x -- \
-              python $R/bench.py --no-cpu-baseline --no-extra --repeats 2 --region-ms 40 --steps 200 $a > $O/trace_$name.line 2> $O/trace_$name.err)
+              python $R/bench.py --full --no-cpu-baseline --no-extra --repeats 2 --region-ms 40 --steps 200 $a > $O/trace_$name.line 2> $O/trace_$name.err)
            f=$(find $O/trace_$name -name "x_kernel_trace.csv" | head -1)
-           python tools/trace_summary.py $f "rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-extra --repeats 2 --region-ms 40 --steps 200 $a" > $O/${name}_kernel_trace_summary.txt
+           python tools/trace_summary.py $f "rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-extra --repeats 2 --region-ms 40 --steps 200 $a" > $O/${name}_kernel_trace_summary.txt
            cp $(find $O/trace_$name -name "x_kernel_stats.csv" | head -1) $O/${name}_kernel_stats.csv 2>/dev/null
            rm -rf $O/trace_$name; head -8 $O/${name}_kernel_trace_summary.txt | cut -c1-200; tail -3 $O/${name}_kernel_trace_summary.txt ;;
     pmc)   name=${rest%%:*}; a=${rest#*:}; [ "$a" = "$rest" ] && a=""; a=${a//,/ }
