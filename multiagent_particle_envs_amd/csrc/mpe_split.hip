@@ -496,6 +496,11 @@ __device__ __forceinline__ void store_state(const MpeBuffers &b, size_t B, int i
 // is AHEAD of its commander (closed loop: the next doorbell rings only after the consumer saw this step) must not wait for
 // that barrier: a wave that finds its next doorbell unrung drains its stores and counts itself in LDS; the reward wave,
 // spinning on the same doorbell, publishes as soon as all agent waves are counted.
+//
+// Giving up is workgroup-wide: a wave whose wait times out raises an abort word in LDS and meets its siblings at the barrier
+// they are all headed for (every wait sits in front of the next barrier of every role); behind each barrier every wave --
+// the dual-role rows waves, which never wait, included -- reads the word and leaves before any further store.  A launch that
+// times out leaves the outputs and the state of the steps it served and touches nothing of the steps it was not commanded.
 struct ServeArgs {
   unsigned long long *door;     // commanded steps (absolute count): step g may run when *door > g
   unsigned long long *flag;     // [grid] completed steps per workgroup (absolute count)
@@ -580,14 +585,15 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
   const size_t obs_stride = (ra.trajectory || SERVE) ? (size_t)d.obs_off[A] * B : 0;
   const size_t row_stride = (ra.trajectory || SERVE) ? (size_t)A * B : 0;
   // served steps: output block g % slots and move tensor g % ring of global step g, as counters (a 64-bit modulo per step
-  // costs ~130 instructions); `seen` = this wave's last look at the doorbell; cnt[parity] = agent waves drained while idle
+  // costs ~130 instructions); `seen` = this wave's last look at the doorbell; idle_cnt[parity] = agent waves drained while
+  // idle, idle_cnt[2] = the abort word (some wave gave up)
   int blk0 = 0, mvt0 = 0;
   unsigned long long seen = 0;
   int *const idle_cnt = reinterpret_cast<int *>(smem + SplitShape<KIND, A, L, NADV>::lds_bytes(true) / sizeof(float));
   if constexpr (SERVE) {
     blk0 = (int)(ra.step0 % (uint64_t)sv.slots);
     mvt0 = (int)(ra.step0 % (uint64_t)sv.ring);
-    if (threadIdx.x < 2) idle_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < 3) idle_cnt[threadIdx.x] = 0;
     __syncthreads();
   }
   auto block_of = [&](const int t) { return SERVE ? (blk0 + t) % sv.slots : t; };   // (32-bit; t < T)
@@ -622,10 +628,18 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
       seen = door_load(sv.door);
       if (seen > g) return true;
       if ((unsigned long long)wall_clock64() - t_begin > sv.timeout_ticks) {
-        if (lane == 0) __hip_atomic_store(sv.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (lane == 0) {
+          __hip_atomic_store(sv.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_store(&idle_cnt[2], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
         return false;
       }
     }
+  };
+  // behind a barrier: did some wave of this workgroup give up?  (then this one leaves before any further store)
+  auto aborted = [&]() -> bool {
+    if constexpr (!SERVE) return false;
+    return __builtin_amdgcn_readfirstlane(__hip_atomic_load(&idle_cnt[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) != 0;
   };
 
   if (!is_agent) {
@@ -656,7 +670,10 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
     }
     for (int t = 0; t < T; ++t) {
       MPE_STAMP(0);
-      if (SERVE && !wait_door(t, true)) return;
+      if (SERVE && !wait_door(t, true)) {   // gave up: to barrier t with the abort word raised, then out
+        __syncthreads();
+        return;
+      }
       if (TRACK && cd >= 0) {
         if (cd == 0) {
           if (KIND == MPE_SCN_CRYPTO) goal_r = choice_draw(ra.seed, gw_r, ep_r, 0, d.choice_pop[0]);
@@ -688,6 +705,7 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
       if (SERVE) {                 // ... and so are every agent wave's (they drain in front of this barrier too): step t - 1 is complete
         if (t > 0 && lane == 0) __hip_atomic_store(sv.flag + blockIdx.x, ra.step0 + (unsigned long long)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         if (lane == 0) idle_cnt[t & 1] = 0;      // (next used by step t + 2's waiters, who are behind step t + 1's barrier)
+        if (aborted()) return;                   // (steps < t are complete: the flag above stands)
       }
       MPE_STAMP(2);
       if (!(MPE_SPLIT_ABLATE & 2))
@@ -1176,6 +1194,7 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
         if (HAS_GOAL || KIND == MPE_SCN_SPEAKER_LISTENER) goal_pos<A, L>(px, py, goal, gx, gy);
         MPE_STAMP(2);
         __syncthreads();
+        if (SERVE && aborted()) return;   // (step t was never commanded: its exchange block is stale)
         MPE_STAMP(3);
         const float *const X = xch + (t & 1) * A * XW * kWave;
         mx = X[(i * XW + 0) * kWave + lane];
@@ -1209,7 +1228,10 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
     // ---- PHYSICS wave of agent i: World.step of step t+1 behind barrier t, from the siblings' state of step t -----------
     float fx, fy;
     { [[maybe_unused]] const int t = 0; MPE_STAMP(0); }
-    if (SERVE && !wait_door(0, false)) return;
+    if (SERVE && !wait_door(0, false)) {
+      __syncthreads();   // (barrier 0 of the loop below, with the abort word raised)
+      return;
+    }
     step_forces(0, fx, fy);
     step_integrate(0, fx, fy);
     { [[maybe_unused]] const int t = 0; MPE_STAMP(1); }
@@ -1218,11 +1240,15 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
       MPE_STAMP(2);
       if (SERVE) drain_stores();   // step t - 1's state is acknowledged
       __syncthreads();
+      if (SERVE && aborted()) return;
       MPE_STAMP(3);
       behind_barrier(t);
       MPE_STAMP(4);
       if (t + 1 < T) {
-        if (SERVE && !wait_door(t + 1, false)) return;
+        if (SERVE && !wait_door(t + 1, false)) {
+          __syncthreads();   // (barrier t + 1, with the abort word raised)
+          return;
+        }
         step_forces(t + 1, fx, fy);
         step_integrate(t + 1, fx, fy);
         MPE_STAMP(5);
@@ -1239,7 +1265,10 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
     for (int t = 0; t < T; ++t) {
       float fx, fy;
       MPE_STAMP(0);
-      if (SERVE && !wait_door(t, false)) return;
+      if (SERVE && !wait_door(t, false)) {
+        __syncthreads();   // (barrier t, with the abort word raised)
+        return;
+      }
       step_forces(t, fx, fy);
       step_integrate(t, fx, fy);
       MPE_STAMP(1);
@@ -1247,6 +1276,7 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
       MPE_STAMP(2);
       if (SERVE) drain_stores();   // step t - 1's rows and state are acknowledged: the reward wave says so behind this barrier
       __syncthreads();
+      if (SERVE && aborted()) return;
       MPE_STAMP(3);
       behind_barrier(t);
       MPE_STAMP(4);
@@ -1429,7 +1459,7 @@ int launch_split_serve(int kind, int A, int L, int nadv, const NarrowDesc &d, co
   sv.ring = h.ring;
   sv.slots = h.slots;
   sv.timeout_ticks = h.timeout_ticks;
-  const size_t lds = e->lds_roll + 16;   // + the two idle counters
+  const size_t lds = e->lds_roll + 16;   // + the two idle counters and the abort word
   const unsigned grid = serve_grid(B);
   int per_cu = 0, dev = 0, n_cu = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {

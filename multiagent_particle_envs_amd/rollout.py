@@ -480,11 +480,15 @@ class StepServer(object):
     def run(self, T):
         """T steps whose moves ALREADY EXIST (moves[g % ring] of the next T global steps): the doorbell first, then the launch, both
         on the CURRENT stream -- every command precedes the launch, so nothing has to overtake anything: no second stream, no
-        probe, nothing resident that waits.  The caller's `for t in range(T): env.step(actions[t])` loop (bin/interactive.py:27-36)
-        with the caller's own actions, as ONE launch.  Outputs: outputs(g) per step, the state in world.pos / vel."""
-        self.served_to += int(T)      # (ring() checks the commands against the launches: this one is about to start)
-        self.ring(T)
-        self.served_to -= int(T)
+        probe, nothing resident that waits, and any stream may issue them (nothing was probed against the commanding one).
+        The caller's `for t in range(T): env.step(actions[t])` loop (bin/interactive.py:27-36) with the caller's own actions, as ONE
+        launch.  Outputs: outputs(g) per step, the state in world.pos / vel."""
+        T = int(T)
+        self.served_to += T      # (the commands are checked against the launches: this one is about to start)
+        try:
+            self._command(T)
+        finally:
+            self.served_to -= T
         self.start(T, on_current_stream=True)
         return self
 
@@ -519,10 +523,16 @@ class StepServer(object):
         if _abi.raw_stream(self.world.device).value != self._commander:
             raise _abi.MpeError("ring(): command from the stream that was current when the StepServer was built (the one its server "
                                 "stream was probed against)")
-        self.commanded += int(n)
-        if self.commanded > self.served_to:
-            raise _abi.MpeError("ring(): %d steps commanded, the launches started so far serve %d -- start() first" % (self.commanded, self.served_to))
-        _abi.check(self._L.mpe_step_server_ring(C.byref(self._srv), int(n), _abi.raw_stream(self.world.device)), "mpe_step_server_ring")
+        self._command(n)
+
+    def _command(self, n):
+        """The doorbell launch on the current stream; a refused command changes no count."""
+        n = int(n)
+        if self.commanded + n > self.served_to:
+            raise _abi.MpeError("ring(): %d steps commanded, the launches started so far serve %d -- start() first"
+                                % (self.commanded + n, self.served_to))
+        _abi.check(self._L.mpe_step_server_ring(C.byref(self._srv), n, _abi.raw_stream(self.world.device)), "mpe_step_server_ring")
+        self.commanded += n
 
     def wait(self, completed=None):
         """The current stream continues when `completed` steps (default: all commanded so far) have their outputs in memory."""
@@ -677,24 +687,53 @@ class ServedRollout(object):
             left -= n
 
 
+def _step_many_env_check(env):
+    """What env.step would do differently from the served / rolled-out steps, refused by name -- on EVERY step_many call (a
+    cached server or rollout state is no licence: the flags may have been flipped since).  Constants assigned since the last
+    step are re-read first, as env.step does (a noise constant switches env.fused off there)."""
+    if env._constants_seen != env.world._constants_version:
+        env.refresh_constants()
+    if not env.fused:
+        raise _abi.MpeError("step_many: env.fused is False (action / communication noise, scripted agents or Python callbacks: "
+                            "env.step runs the generic path) -- use env.step")
+    if env._py_obs or env._py_reward or env._py_done or env._py_info:
+        raise _abi.MpeError("step_many evaluates the device-side callbacks only")
+    if env.force_discrete_action:
+        raise _abi.MpeError("step_many: force_discrete_action is set (env.step turns every move row into a one-hot row first) -- "
+                            "hand over one-hot rows and clear it, or use env.step")
+    if not env.discrete_action_space:
+        raise _abi.MpeError("step_many: discrete_action_space is False (env.step reads continuous moves) -- use env.step")
+    if env.discrete_action_input:
+        raise _abi.MpeError("step_many: discrete_action_input is set (env.step reads integer action ids) -- use env.step")
+    if env.max_episode_steps:
+        raise _abi.MpeError("step_many: max_episode_steps is set (env.step counts and ends the episodes%s) -- use env.step, or "
+                            "step_many(episode_len=...) on an env without it" % (" and restarts them: auto_reset" if env.auto_reset else ""))
+
+
 def step_many(env, moves, episode_len=0, seed=None, comm=None):
     """`for t in range(T): obs_n, reward_n, done_n, _ = env.step(moves[t])` as ONE launch: moves [T, A, B, 5] one-hot rows on the
     env's device (the reference's action format, environment.py:174-181, stacked over the steps).  -> a list of T tuples
     (obs_n, rew [A, B], done [A, B]) of views into the server's T output blocks (valid until the next call with the same T);
     world.pos / vel hold the state after the last step.  Bit-identical to the T env.step calls (tests/test_gpu_server.py).
-    episode_len > 0: the worlds restart (world.reset_uniform's device draws) every episode_len steps, counted over the calls.
-    comm: [T, A, B, dim_c] utterance rows for the communication scenarios."""
+    episode_len > 0: the worlds restart (world.reset_uniform's device draws of `seed`, default world.seed) every episode_len
+    steps, counted over the calls with the same T, episode_len and seed.  comm: [T, A, B, dim_c] utterance rows for the
+    communication scenarios.  The env's flags and constants are read at every call (_step_many_env_check); the launches go
+    to the current stream, whichever it is."""
+    _step_many_env_check(env)
     T = int(moves.shape[0])
-    key = (T, int(episode_len))
+    w = env.world
+    key = (T, int(episode_len), int(w.seed if seed is None else seed) & (2 ** 64 - 1))
     cache = env.__dict__.setdefault("_step_many_servers", {})
     prog = getattr(env, "_prog", None)
-    if prog is not None or _abi.lib().mpe_step_server_supported(C.byref(env._desc), env.world.batch_size) != 1:
-        return _rollout_actions(env, moves, int(episode_len), seed, comm, cache, key)
+    if prog is not None or _abi.lib().mpe_step_server_supported(C.byref(env._desc), w.batch_size) != 1:
+        return _rollout_actions(env, moves, int(episode_len), key[2], comm, cache, key)
     srv = cache.get(key)
     if srv is None or srv.moves.data_ptr() != moves.data_ptr() or tuple(srv.moves.shape) != tuple(moves.shape) or \
-            (comm is not None and (srv.comm is None or srv.comm.data_ptr() != comm.data_ptr())):
+            (comm is not None and (srv.comm is None or srv.comm.data_ptr() != comm.data_ptr())) or \
+            srv.constants_seen != env._constants_seen:      # (a server snapshots the descriptor and the entity table)
         t0 = 0 if srv is None else srv.served_to
-        srv = StepServer(env, moves, slots=T, episode_len=episode_len, seed=seed, probe=False, ahead=True, comm=comm)
+        srv = StepServer(env, moves, slots=T, episode_len=episode_len, seed=key[2], probe=False, ahead=True, comm=comm)
+        srv.constants_seen = env._constants_seen
         srv.served_to = srv.commanded = t0 - t0 % T      # (blocks and move tensors are indexed by the global step modulo T)
         if t0 % T:
             raise _abi.MpeError("step_many: a new move tensor mid-way through a block of %d steps" % T)
@@ -709,11 +748,7 @@ def step_many(env, moves, episode_len=0, seed=None, comm=None):
 def _rollout_actions(env, moves, episode_len, seed, comm, cache, key):
     """step_many for the envs the step server does not serve: row-program envs (user scenarios, traced reference-style files:
     mpe_rollout_rows_actions) and simple_spread / simple_tag beyond 16 entities (mpe_rollout_actions) -- their fused T-step rollout
-    with the CALLER's moves (RollArgs.act_seq) instead of moves drawn in the kernel."""
-    if not env.fused:
-        raise _abi.MpeError("step_many: this env steps through Python callbacks (use env.step / GraphedStep)")
-    if env._py_obs or env._py_reward or env._py_done or env._py_info:
-        raise _abi.MpeError("step_many evaluates the device-side callbacks only")
+    with the CALLER's moves (RollArgs.act_seq) instead of moves drawn in the kernel.  (step_many checked the env's flags.)"""
     w = env.world
     env._ensure_buffers()
     A, B, T = len(w.agents), w.batch_size, int(moves.shape[0])
@@ -729,7 +764,9 @@ def _rollout_actions(env, moves, episode_len, seed, comm, cache, key):
         raise _abi.MpeError("step_many(episode_len > 0): the in-launch resets are world.reset_uniform's device draws; this env's reset_world is not that")
     st = cache.get(key)
     if st is None or not isinstance(st, dict):
-        st = cache[key] = {"traj": Trajectory(env, T), "t": 0, "desc": _copy_struct(env._desc)}
+        st = cache[key] = {"traj": Trajectory(env, T), "t": 0, "desc": _copy_struct(env._desc), "seen": env._constants_seen}
+    elif st["seen"] != env._constants_seen:      # constants re-read since: the descriptor and the entity table again, same step count
+        st.update(traj=Trajectory(env, T), desc=_copy_struct(env._desc), seen=env._constants_seen)
     traj = st["traj"]
     b = traj.bufs
     b.act = b.ids = b.u = None

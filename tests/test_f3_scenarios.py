@@ -17,32 +17,7 @@ import multiagent_particle_envs_amd as mpe
 
 NAMES = ["simple_adversary", "simple_push", "simple_speaker_listener", "simple_reference", "simple_crypto",
          "simple_world_comm"]
-TOL = 1e-5
-
-
-def close(a, b, tol=TOL, what=""):
-    a = np.asarray(a, dtype=np.float64)
-    b = np.asarray(b, dtype=np.float64)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    err = np.abs(a - b) / np.maximum(1.0, np.abs(b))
-    assert np.all(err <= tol), "%s: max scaled err %.3e at %s" % (what, err.max(), np.unravel_index(err.argmax(), err.shape))
-    return float(err.max()) if err.size else 0.0
-
-
-def np_(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def set_choices(env, choice):
-    sc = env.scenario
-    if choice.shape[1] == 0:
-        return
-    if hasattr(sc, "set_choices"):
-        sc.set_choices(env.world, torch.as_tensor(choice))
-    elif choice.shape[1] == 1:
-        sc.set_goal(env.world, torch.as_tensor(choice[:, 0]))
-    else:
-        sc.set_goal(env.world, torch.as_tensor(choice))
+from _parity_util import TOL, close, np_, set_choices, set_comm  # noqa: E402,F401  (shared with the served-step tests)
 
 
 def get_choices(env):
@@ -52,12 +27,6 @@ def get_choices(env):
             v = np_(getattr(sc, attr))
             return v.reshape(v.shape[0], -1)
     return np.zeros((env.batch_size, 0), np.int64)
-
-
-def set_comm(env, g, t):
-    for i, agent in enumerate(env.world.agents):
-        c = g["c%d" % i][t] if t >= 0 else np.zeros_like(g["c%d" % i][0])
-        agent.state.c = torch.as_tensor(c, dtype=torch.float32, device=env.world.device)
 
 
 def rewards(env):

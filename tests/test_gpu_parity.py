@@ -21,20 +21,7 @@ from oracle.mpe_batched import BatchedOracle, seeded_initial_state
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-5
-
-
-def close(a, b, tol=TOL, what=""):
-    a = np.asarray(a, dtype=np.float64)
-    b = np.asarray(b, dtype=np.float64)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    err = np.abs(a - b) / np.maximum(1.0, np.abs(b))
-    assert np.all(err <= tol), "%s: max scaled err %.3e at %s" % (what, err.max(), np.unravel_index(err.argmax(), err.shape))
-    return float(err.max()) if err.size else 0.0
-
-
-def np_(t):
-    return t.detach().cpu().numpy()
+from _parity_util import MASKED, TOL, _guard_ok, close, guard_ok, np_  # noqa: E402,F401  (shared with the served-step tests)
 
 
 SCN = {
@@ -48,42 +35,6 @@ SCN = {
 
 def scenario_name(name):
     return "simple_spread" if name.startswith("simple_spread") else name
-
-
-MASKED = {}   # test -> most worlds the guard band masked (asserted <= 1 % wherever it is used)
-
-
-def guard_ok(spec, pos64, margin=1e-6, max_frac=0.01):
-    """True per world where no counted pair is within `margin` of its collision threshold.  Fails when the band masks
-    more than `max_frac` of the worlds (min. one world): a check that masks everything would pass vacuously."""
-    ok = _guard_ok(spec, pos64, margin)
-    n_masked = int((~ok).sum())
-    assert n_masked <= max(1, max_frac * len(ok)), "guard band masks %d of %d worlds" % (n_masked, len(ok))
-    import os
-    key = os.environ.get("PYTEST_CURRENT_TEST", "?").split(" ")[0].split("::")[-1]
-    MASKED[key] = max(MASKED.get(key, 0), n_masked)
-    return ok
-
-
-def _guard_ok(spec, pos64, margin):
-    A = spec.n_agents
-    size = np.asarray(spec.size)
-    ok = np.ones(pos64.shape[0], bool)
-
-    def near(i_idx, j_idx, thr):
-        d = pos64[:, i_idx, None, :] - pos64[:, None, j_idx, :]
-        dist = np.sqrt((d ** 2).sum(-1))
-        return (np.abs(dist - thr[None]) < margin).any(axis=(1, 2))
-    ag = list(range(A))
-    if spec.name == "simple_spread":
-        ok &= ~near(ag, ag, size[ag][:, None] + size[ag][None, :])
-        lm = list(range(A, spec.n_entities))
-        ok &= ~near(ag, lm, np.full((A, len(lm)), 0.1))
-    if spec.name == "simple_tag":
-        good = [j for j in ag if not spec.adversary[j]]
-        adv = [j for j in ag if spec.adversary[j]]
-        ok &= ~near(good, adv, size[good][:, None] + size[adv][None, :])
-    return ok
 
 
 # ------------------------------------------------------------------------------------------------

@@ -120,17 +120,48 @@ def test_bursts_and_two_launches():
     assert torch.equal(env.world.pos, ref[-1][3])
 
 
-def test_a_server_nobody_commands_gives_up():
-    env = mpe.make_env("simple_spread", batch_size=512, seed=3)
-    moves = torch.zeros((2, 3, 512, _abi.MPE_ACTION_DIM), device="cuda")
-    srv = StepServer(env, moves, slots=2, timeout_s=0.2)
-    srv.start(3)
+def dual_max_workgroups():
+    """launch_split_serve takes the dual-role server up to n_cu * 3 / 2 workgroups of 64 worlds."""
+    return torch.cuda.get_device_properties(0).multi_processor_count * 3 // 2
+
+
+@pytest.mark.parametrize("role", ["dual", "single"])
+def test_a_server_nobody_commands_gives_up(role):
+    """A launch of 4 steps, 2 of them commanded: after the timeout the server says so (status 1, every workgroup's flag at 2) and
+    has touched nothing of the 2 steps nobody commanded -- their output blocks are still what the caller left there (NaN rows,
+    True dones) and the state in HBM is the state after 2 steps, as 2 env.step calls leave it.  The dual-role server's rows waves
+    never wait for a doorbell themselves: they leave with the others (the workgroup's abort word)."""
+    B = 512 if role == "dual" else 64 * dual_max_workgroups() + 37
+    assert ((B + 63) // 64 <= dual_max_workgroups()) == (role == "dual")
+    T = 4
+    ref = mpe.make_env("simple_spread", batch_size=B, seed=3)
+    env = mpe.make_env("simple_spread", batch_size=B, seed=3)
+    ref.reset()
+    env.world.set_state(*ref.world.get_state())
+    g = torch.Generator(device="cpu").manual_seed(8)
+    moves = torch.nn.functional.one_hot(torch.randint(0, 5, (T, 3, B), generator=g), 5).float().cuda()
+    srv = StepServer(env, moves, slots=T, timeout_s=0.2)
+    srv.blocks.obs_flat.fill_(float("nan"))
+    srv.blocks.rew.fill_(float("nan"))
+    srv.blocks.done.fill_(True)
+    torch.cuda.synchronize()
+    srv.start(T)
     srv.ring(2)
     t0 = time.time()
     srv.join()
     torch.cuda.synchronize()
     assert time.time() - t0 < 5.0
-    assert int(srv.status.item()) == 1 and int(srv.flag.min()) == 2      # two steps served, then the timeout
+    assert int(srv.status.item()) == 1 and int(srv.flag.min()) == 2 and int(srv.flag.max()) == 2    # two steps served, then the timeout
+    for t in range(2):
+        obs_n, rew_n, done_n, _ = ref.step(moves[t])
+        o_s, r_s, d_s = srv.outputs(t)
+        for i in range(3):
+            assert torch.equal(o_s[i], obs_n[i]) and torch.equal(r_s[i], rew_n[i]) and torch.equal(d_s[i], done_n[i]), (t, i)
+    for t in (2, 3):
+        o_s, r_s, d_s = srv.outputs(t)
+        assert all(bool(torch.isnan(o).all()) for o in o_s), "block %d: rows written for a step nobody commanded" % t
+        assert bool(torch.isnan(r_s).all()) and bool(d_s.all()), "block %d: rewards / dones written" % t
+    assert torch.equal(env.world.pos, ref.world.pos) and torch.equal(env.world.vel, ref.world.vel)
     with pytest.raises(_abi.MpeError, match="timed out"):
         srv.check()
     with pytest.raises(_abi.MpeError, match="start"):
@@ -268,3 +299,149 @@ def test_step_many_beyond_the_server(what):
                 assert torch.equal(o_s[i], obs_n[i]), (rnd, t, i)
                 assert torch.equal(r_s[i], rew_n[i]) and torch.equal(d_s[i], done_n[i])
         assert torch.equal(env.world.pos, ref.world.pos) and torch.equal(env.world.vel, ref.world.vel)
+
+
+# ---- step_many keeps env.step's contract: constants, flags, seeds, streams (tests/test_gpu_server_oracle.py: against the reference)
+PATHS = {"spread3": ("simple_spread", {}, 3000),                       # the step server
+         "spread10": ("simple_spread", {"num_agents": 10}, 1500),      # mpe_rollout_actions
+         "corral": ("corral", {}, 2048)}                                # a row program: mpe_rollout_rows_actions
+
+
+def twin_envs(what, **kw):
+    import os
+    name, skw, B = PATHS[what]
+    if name == "corral":
+        name = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "corral.py")
+    ref = mpe.make_env(name, batch_size=B, seed=11, **dict(skw, **kw))
+    env = mpe.make_env(name, batch_size=B, seed=11, **dict(skw, **kw))
+    ref.reset()
+    env.reset()
+    assert torch.equal(env.world.pos, ref.world.pos)
+    return ref, env
+
+
+def random_moves(moves, seed):
+    T, A, B, _ = moves.shape
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    moves.copy_(torch.nn.functional.one_hot(torch.randint(0, 5, (T, A, B), generator=g), 5).float())
+    return moves
+
+
+def same_as_env_step(outs, ref, moves, what):
+    torch.cuda.synchronize()
+    for t in range(moves.shape[0]):
+        obs_n, rew_n, done_n, _ = ref.step(moves[t])
+        o_s, r_s, d_s = outs[t]
+        for i in range(ref.n):
+            assert torch.equal(o_s[i], obs_n[i]), (what, t, i)
+            assert torch.equal(r_s[i], rew_n[i]) and torch.equal(d_s[i], done_n[i]), (what, t, i)
+
+
+CONSTANTS = {"max_speed": lambda w: [setattr(a, "max_speed", 0.35) for a in w.agents],
+             "size": lambda w: [setattr(e, "size", e.size * 1.8) for e in w.entities],
+             "damping": lambda w: setattr(w, "damping", 0.6),
+             "contact_margin": lambda w: setattr(w, "contact_margin", 0.02)}
+
+
+@pytest.mark.parametrize("const", list(CONSTANTS))
+@pytest.mark.parametrize("what", list(PATHS))
+def test_step_many_rereads_constants_assigned_between_calls(what, const):
+    """A constant assigned between two step_many calls with the SAME move tensor (a cached server / rollout state) is honoured
+    as env.step honours it (the descriptor and the entity table re-read)."""
+    ref, env = twin_envs(what)
+    moves = torch.empty((6, ref.n, ref.batch_size, _abi.MPE_ACTION_DIM), device="cuda")
+    same_as_env_step(env.step_many(random_moves(moves, 1)), ref, moves, "before")
+    for e in (ref, env):
+        CONSTANTS[const](e.world)
+    same_as_env_step(env.step_many(random_moves(moves, 2)), ref, moves, "after " + const)
+    assert torch.equal(env.world.pos, ref.world.pos) and torch.equal(env.world.vel, ref.world.vel)
+
+
+@pytest.mark.parametrize("what", list(PATHS))
+def test_step_many_refuses_noise_set_after_a_cached_call(what):
+    ref, env = twin_envs(what)
+    moves = random_moves(torch.empty((4, env.n, env.batch_size, _abi.MPE_ACTION_DIM), device="cuda"), 3)
+    env.step_many(moves)
+    env.world.agents[0].u_noise = 0.1          # env.step: the generic path, which draws the noise
+    with pytest.raises(_abi.MpeError, match="fused"):
+        env.step_many(moves)
+
+
+FLAGS = {"force_discrete_action": lambda e: setattr(e, "force_discrete_action", True),
+         "discrete_action_space": lambda e: setattr(e, "discrete_action_space", False),
+         "discrete_action_input": lambda e: setattr(e, "discrete_action_input", True)}
+
+
+@pytest.mark.parametrize("flag", list(FLAGS) + ["max_episode_steps", "max_episode_steps+auto_reset"])
+@pytest.mark.parametrize("what", list(PATHS))
+def test_step_many_refuses_what_env_step_does_differently(what, flag):
+    """Each flag env.step honours and step_many does not is refused by name: set on a live env after a cached call, or (the
+    episode horizon) given to make_env."""
+    if flag.startswith("max_episode_steps"):
+        _, env = twin_envs(what, max_episode_steps=10, auto_reset=flag.endswith("auto_reset"))
+    else:
+        _, env = twin_envs(what)
+    moves = random_moves(torch.empty((4, env.n, env.batch_size, _abi.MPE_ACTION_DIM), device="cuda"), 4)
+    if flag in FLAGS:
+        env.step_many(moves)
+        FLAGS[flag](env)
+    with pytest.raises(_abi.MpeError, match=flag.split("+")[0]):
+        env.step_many(moves)
+
+
+@pytest.mark.parametrize("what", ["spread3", "spread10"])
+def test_step_many_restarts_with_the_seed_it_is_given(what):
+    """episode_len = T = 5: every call is one episode that starts with mpe_reset's draws of its seed, counted per seed -- seed 1
+    (episode 0), seed 2 (episode 0), seed 1 again (episode 1).  The landmarks never move: their positions are the draws."""
+    from oracle import philox
+    _, env = twin_envs(what)
+    w = env.world
+    A, L, B = len(w.agents), len(w.landmarks), w.batch_size
+    moves = random_moves(torch.empty((5, A, B, _abi.MPE_ACTION_DIM), device="cuda"), 5)
+    for seed, episode in ((1, 0), (2, 0), (1, 1)):
+        env.step_many(moves, episode_len=5, seed=seed)
+        torch.cuda.synchronize()
+        pos, _ = w.get_state()
+        want = philox.reset_positions(seed, B, episode, A, L, float(env._scenario.landmark_range), int(w.world_offset))
+        assert np.array_equal(pos[:, A:], want[:, A:]), (seed, episode)
+
+
+@pytest.mark.parametrize("what", list(PATHS))
+def test_step_many_on_another_stream(what):
+    """A call under another torch.cuda.Stream than the cached server's first call: stepped there, the env.step loop's result."""
+    ref, env = twin_envs(what)
+    moves = torch.empty((5, ref.n, ref.batch_size, _abi.MPE_ACTION_DIM), device="cuda")
+    same_as_env_step(env.step_many(random_moves(moves, 6)), ref, moves, "current stream")
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        outs = env.step_many(random_moves(moves, 7))
+    torch.cuda.current_stream().wait_stream(s)
+    same_as_env_step(outs, ref, moves, "side stream")
+    assert torch.equal(env.world.pos, ref.world.pos) and torch.equal(env.world.vel, ref.world.vel)
+
+
+def test_refused_commands_change_no_count():
+    """A refused ring() -- from a stream the server was not probed against, or beyond the launches -- and a refused run() leave
+    `commanded` and `served_to` as they were; the server then serves on as commanded."""
+    env = mpe.make_env("simple_spread", batch_size=512, seed=3)
+    moves = torch.zeros((4, 3, 512, _abi.MPE_ACTION_DIM), device="cuda")
+    srv = StepServer(env, moves, slots=4, timeout_s=5.0)
+    srv.start(2)
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        with pytest.raises(_abi.MpeError, match="stream"):
+            srv.ring()
+    assert (srv.commanded, srv.served_to) == (0, 2)
+    with pytest.raises(_abi.MpeError, match="start"):
+        srv.ring(3)
+    assert (srv.commanded, srv.served_to) == (0, 2)
+    srv.ring(2)
+    srv.join()
+    torch.cuda.synchronize()
+    srv.check()
+    assert int(srv.flag.min()) == 2
+    srv.commanded += 1          # (a count the commands cannot have reached: run()'s doorbell is refused)
+    with pytest.raises(_abi.MpeError, match="start"):
+        srv.run(2)
+    assert (srv.commanded, srv.served_to) == (3, 2)
