@@ -481,6 +481,30 @@ int mpe_rows_unload_image(MpeRowProgram *prog); /* 0; a program without an image
 /* 1 if the next mpe_rows / mpe_step_rows call with this descriptor would launch the compiled image, else 0.              */
 int mpe_rows_image_active(const MpeScenarioDesc *desc, const MpeRowProgram *prog);
 
+/* ---- rendering: MultiAgentEnv.render(mode='rgb_array') for many worlds in ONE launch -- environment.py:200-263 ----------------
+ * The reference's scene (every entity a 30-gon of its size, filled, then a 1-px outline; agents at alpha 0.5; a square view of
+ * +-1 world unit around the origin or around one agent) drawn by the deterministic rule of DESIGN.md section 2 ("Rendering"):
+ * output [n_viewers][K][size][size][3] uint8, row 0 the top of the view, image (v, k) = viewer v of world worlds[k].  Reads
+ * positions from pos ([E][2][B], the world's own buffer) and sizes from desc; no host copy of state, no synchronisation.     */
+typedef struct MpeRenderArgs {
+  const float *pos;         /* device [E][2][B]                                                                           */
+  int64_t B;                /* worlds in pos                                                                               */
+  const int32_t *worlds;    /* device [K] world indices in [0, B) (an index outside draws an empty frame); NULL = 0 .. K-1   */
+  int32_t K;                /* frames per viewer                                                                           */
+  int32_t n_entities;       /* E: must equal desc->n_agents + desc->n_landmarks                                            */
+  const float *rgba;        /* device fp32: entity e's colour in frame k at rgba + 4 * (e * K + k) (rgba_world_stride = 4), or
+                               at rgba + 4 * e for every frame (rgba_world_stride = 0); r, g, b are clamped to [0, 1], a is
+                               the fill's alpha (the reference: 0.5 for agents, 1 otherwise)                              */
+  int32_t rgba_world_stride;/* 4 or 0                                                                                      */
+  int32_t n_viewers;        /* V, 1 .. MPE_MAX_ENTITIES                                                                    */
+  const int32_t *camera;    /* HOST [V]: the entity viewer v centres on, -1 = the origin; NULL = every viewer at the origin   */
+  int32_t size;             /* frame side in pixels, 8 .. 4096 (the reference: 700)                                        */
+  int32_t reserved_;
+  uint8_t *out;             /* device, V * K * size * size * 3 bytes, 16-byte aligned                                      */
+} MpeRenderArgs;
+int mpe_render(const MpeScenarioDesc *desc, const MpeRenderArgs *args, void *stream);
+size_t mpe_sizeof_render_args(void);
+
 #ifdef __cplusplus
 }
 #endif

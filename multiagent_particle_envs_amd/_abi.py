@@ -51,6 +51,12 @@ class MpeStepServer(C.Structure):      # include/mpe_hip.h: the step server's de
                 ("ahead", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class MpeRenderArgs(C.Structure):      # include/mpe_hip.h: one mpe_render call
+    _fields_ = [("pos", C.c_void_p), ("B", C.c_int64), ("worlds", C.c_void_p), ("K", C.c_int32), ("n_entities", C.c_int32),
+                ("rgba", C.c_void_p), ("rgba_world_stride", C.c_int32), ("n_viewers", C.c_int32), ("camera", C.POINTER(C.c_int32)),
+                ("size", C.c_int32), ("reserved_", C.c_int32), ("out", C.c_void_p)]
+
+
 class MpeBuffers(C.Structure):
     _fields_ = [
         ("pos", C.c_void_p), ("vel", C.c_void_p), ("act", C.c_void_p), ("ids", C.c_void_p), ("u", C.c_void_p),
@@ -134,6 +140,8 @@ EXPORTS = {
                                         C.c_float, C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(MpeStepServer), C.c_void_p]),
     "mpe_step_server_ring": (C.c_int, [C.POINTER(MpeStepServer), C.c_uint64, C.c_void_p]),
     "mpe_step_server_wait": (C.c_int, [C.POINTER(MpeStepServer), C.c_int64, C.c_uint64, C.c_void_p]),
+    "mpe_render": (C.c_int, [C.POINTER(MpeScenarioDesc), C.POINTER(MpeRenderArgs), C.c_void_p]),
+    "mpe_sizeof_render_args": (C.c_size_t, []),
 }
 
 _lib = None
@@ -162,7 +170,8 @@ def lib():
     if handle.mpe_abi_version() != MPE_ABI_VERSION:
         raise MpeError("ABI version mismatch: library %d, binding %d" % (handle.mpe_abi_version(), MPE_ABI_VERSION))
     if handle.mpe_sizeof_desc() != C.sizeof(MpeScenarioDesc) or handle.mpe_sizeof_buffers() != C.sizeof(MpeBuffers) or \
-            handle.mpe_sizeof_row_program() != C.sizeof(MpeRowProgram) or handle.mpe_sizeof_step_server() != C.sizeof(MpeStepServer):
+            handle.mpe_sizeof_row_program() != C.sizeof(MpeRowProgram) or handle.mpe_sizeof_step_server() != C.sizeof(MpeStepServer) or \
+            handle.mpe_sizeof_render_args() != C.sizeof(MpeRenderArgs):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")
     _lib = handle
     return _lib

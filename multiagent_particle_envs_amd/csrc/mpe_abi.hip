@@ -1081,4 +1081,32 @@ int mpe_rows_image_active(const MpeScenarioDesc *d, const MpeRowProgram *p) {
   return image_matches(p, h, tables_hash(tabs)) ? 1 : 0;
 }
 
+size_t mpe_sizeof_render_args(void) { return sizeof(MpeRenderArgs); }
+
+int mpe_render(const MpeScenarioDesc *d, const MpeRenderArgs *a, void *stream) {
+  const char *what = "mpe_render";
+  if (!d) return fail(MPE_EINVAL, "%s: desc is NULL", what);
+  if (!a) return fail(MPE_EINVAL, "%s: args is NULL", what);
+  const int E = d->n_agents + d->n_landmarks;
+  if (d->n_agents < 1 || d->n_landmarks < 0 || E > MPE_MAX_ENTITIES)
+    return fail(MPE_EINVAL, "%s: need 1 <= A, 0 <= L, A+L <= %d (got A=%d L=%d)", what, MPE_MAX_ENTITIES, d->n_agents, d->n_landmarks);
+  if (a->n_entities != E) return fail(MPE_EINVAL, "%s: args->n_entities = %d, the descriptor has %d entities", what, a->n_entities, E);
+  if (!a->pos || !a->rgba || !a->out) return fail(MPE_EINVAL, "%s: args->pos, rgba and out must be device pointers", what);
+  if (a->B < 1) return fail(MPE_EINVAL, "%s: B = %lld (need >= 1)", what, (long long)a->B);
+  if (a->K < 1) return fail(MPE_EINVAL, "%s: K = %d (need >= 1 frame per viewer)", what, a->K);
+  if (!a->worlds && a->K > a->B) return fail(MPE_EINVAL, "%s: K = %d frames of worlds 0 .. K-1 but B = %lld", what, a->K, (long long)a->B);
+  if (a->size < 8 || a->size > 4096) return fail(MPE_EINVAL, "%s: size = %d, need 8 .. 4096", what, a->size);
+  if (a->n_viewers < 1 || a->n_viewers > MPE_MAX_ENTITIES)
+    return fail(MPE_EINVAL, "%s: n_viewers = %d, need 1 .. %d", what, a->n_viewers, MPE_MAX_ENTITIES);
+  if (a->rgba_world_stride != 0 && a->rgba_world_stride != 4)
+    return fail(MPE_EINVAL, "%s: rgba_world_stride = %d, need 4 (per-frame colours) or 0 (shared)", what, a->rgba_world_stride);
+  if (reinterpret_cast<uintptr_t>(a->out) % 16 != 0) return fail(MPE_EINVAL, "%s: out must be 16-byte aligned", what);
+  for (int v = 0; a->camera && v < a->n_viewers; ++v)
+    if (a->camera[v] < -1 || a->camera[v] >= E)
+      return fail(MPE_EINVAL, "%s: camera[%d] = %d, need -1 (the origin) or an entity index < %d", what, v, a->camera[v], E);
+  const int rc = mpe::launch_render(*d, *a, static_cast<hipStream_t>(stream));
+  if (rc != 0) return fail(MPE_EUNSUPPORTED, "%s: launch failed: %s", what, hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
 }  // extern "C"

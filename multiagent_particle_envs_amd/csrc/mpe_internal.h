@@ -143,4 +143,7 @@ int rows_geometry(const RowDims &dims, bool phys, int *waves, size_t *lds_bytes,
 int launch_rows_image(void *const fns[5], const MpeBuffers &b, const RowDims &dims, const RowTables &host, bool phys, int vec4,
                       const RowEpisode &ep, size_t B, hipStream_t stream, const RollArgs *roll = nullptr);
 
+// rendering (mpe_render.hip): MpeRenderArgs checked by the caller
+int launch_render(const MpeScenarioDesc &d, const MpeRenderArgs &a, hipStream_t stream);
+
 }  // namespace mpe

@@ -98,7 +98,7 @@ class _OutputSet(object):
 
 
 class MultiAgentEnv(object):
-    metadata = {'render.modes': []}
+    metadata = {'render.modes': ['rgb_array']}
 
     def __init__(self, world, reset_callback=None, reward_callback=None, observation_callback=None,
                  info_callback=None, done_callback=None, shared_viewer=True,
@@ -1046,9 +1046,112 @@ class MultiAgentEnv(object):
             done_n = [done[i] for i in range(len(done_n))]
         return self._deliver(obs_n, reward_n, done_n, info_n)
 
-    # rendering is a GUI concern of the reference (environment.py:200-263) and is not provided
-    def render(self, mode='human'):
-        raise NotImplementedError("rendering is out of scope of the MI355X hot-path build (see DESIGN.md)")
+    # ---- rendering (environment.py:200-263): the reference's scene drawn on the device, many worlds per launch ----------------
+    def render(self, mode='human', *, worlds=None, size=700):
+        """mode='rgb_array': one entry per viewer (one shared viewer centred on the origin, or with shared_viewer=False one per
+        policy agent, centred on it), as the reference returns them.  Single-world NumPy mode: uint8 [size, size, 3] arrays.
+        Batched: device uint8 [K, size, size, 3] tensors, views of one [V, K, size, size, 3] allocation filled by ONE `mpe_render`
+        launch on the env's stream; `worlds` (keyword: None = all, an int, a sequence, a slice or a 1-D integer tensor) picks
+        the K worlds.  The picture follows DESIGN.md section 2 ("Rendering").  mode='human' needs a display: not provided."""
+        if mode == 'human':
+            raise NotImplementedError("render(mode='human') needs a display window; use mode='rgb_array' for frames")
+        if mode != 'rgb_array':
+            raise ValueError("render: unknown mode %r (supported: %r)" % (mode, self.metadata['render.modes']))
+        if getattr(self, "ref_scenario", None) is not None:
+            raise NotImplementedError("render: a reference-style scenario file runs on shadow worlds that carry no colours "
+                                      "(refstyle.py mirrors the physics constants only), so there is nothing to draw from")
+        w = self.world
+        if w.pos is None or not w.pos.is_cuda:
+            raise _abi.MpeError("render runs on a HIP device only (world tensors are on %s); there is no CPU fallback"
+                                % (None if w.pos is None else w.pos.device))
+        desc, args, out, _keep = self._render_args(worlds, int(size))
+        _abi.check(_abi.lib().mpe_render(C.byref(desc), C.byref(args), self._stream()), "mpe_render")
+        V = out.shape[0]
+        if self.numpy_io:
+            return [out[v, 0].cpu().numpy() for v in range(V)]
+        return [out[v] for v in range(V)]
+
+    def _render_args(self, worlds, size):
+        """(descriptor, MpeRenderArgs, output [V, K, size, size, 3], what the arguments point into) of one mpe_render call."""
+        w = self.world
+        B, E, dev = self.batch_size, len(w.entities), w.device
+        sel = self._render_worlds(worlds)            # None = all B worlds, else an int32 [K] device tensor
+        K = B if sel is None else int(sel.shape[0])
+        if self._scenario_state_stale:               # device-side resets: goal-dependent colours come from the picks
+            self.sync_from_device()
+        rgba, per_world = self._render_colours(sel)
+        if self.shared_viewer:
+            cams = [-1]
+        else:
+            index = {id(e): i for i, e in enumerate(w.entities)}
+            cams = [index[id(a)] for a in self.agents]
+        V = len(cams)
+        out = torch.empty((V, K, size, size, 3), dtype=torch.uint8, device=dev)
+        cam = (C.c_int32 * V)(*cams)
+        args = _abi.MpeRenderArgs()
+        args.pos, args.B, args.K, args.n_entities = w.pos.data_ptr(), B, K, E
+        args.worlds = None if sel is None else sel.data_ptr()
+        args.rgba, args.rgba_world_stride = rgba.data_ptr(), 4 if per_world else 0
+        args.n_viewers, args.camera, args.size, args.out = V, cam, size, out.data_ptr()
+        return w.scenario_desc(_abi.MPE_SCN_GENERIC), args, out, (sel, rgba, cam)
+
+    def _render_worlds(self, worlds):
+        B = self.batch_size
+        if worlds is None:
+            return None
+        if isinstance(worlds, slice):
+            idx = list(range(B))[worlds]
+        elif torch.is_tensor(worlds):
+            if worlds.dim() != 1 or worlds.dtype.is_floating_point or worlds.dtype == torch.bool:
+                raise TypeError("render: worlds as a tensor is a 1-D integer tensor of world indices")
+            t = worlds.to(self.world.device, torch.int64)
+            if t.numel() and bool(((t < -B) | (t >= B)).any()):
+                raise IndexError("render: a world index is outside [-%d, %d)" % (B, B))
+            t = torch.where(t < 0, t + B, t)
+            idx = None
+        else:
+            seq = [worlds] if isinstance(worlds, (int, np.integer)) else list(worlds)
+            idx = []
+            for i in seq:
+                if isinstance(i, bool) or not isinstance(i, (int, np.integer)):
+                    raise TypeError("render: world indices are integers (got %r)" % (i,))
+                if not -B <= int(i) < B:
+                    raise IndexError("render: world %d is outside [-%d, %d)" % (int(i), B, B))
+                idx.append(int(i) % B)
+        if idx is not None:
+            t = torch.tensor(idx, dtype=torch.int64, device=self.world.device)
+        if t.numel() == 0:
+            raise IndexError("render: no worlds selected")
+        return t.to(torch.int32).contiguous()
+
+    def _render_colours(self, sel):
+        """rgba of every entity for the selected worlds (entity.color, alpha 0.5 for agents: environment.py:231-234) -> (fp32
+        [E, K, 4] when some colour differs between worlds, else [E, 4]; per_world)."""
+        w = self.world
+        rows, per_world = [], False
+        for ent in w.entities:
+            c = ent.color
+            if c is None:
+                raise ValueError("render: entity %r has no color (the reference's geom.set_color(*entity.color) needs one)"
+                                 % ent.name)
+            t = c.to(w.device, torch.float32) if torch.is_tensor(c) else w.constant(np.asarray(c, dtype=np.float32))
+            if t.shape[-1] < 3:
+                raise ValueError("render: entity %r has a color of %d channels" % (ent.name, t.shape[-1]))
+            t = t[..., :3]      # (simple_crypto's landmark colours are dim_c wide: the first three channels are drawn)
+            if t.dim() == 2 and t.stride(0) == 0:
+                t = t[0]
+            per_world = per_world or t.dim() == 2
+            rows.append((t, 0.5 if 'agent' in ent.name else 1.0))
+        if not per_world:
+            return torch.stack([torch.cat([t, t.new_full((1,), a)]) for t, a in rows]).contiguous(), False
+        K = self.batch_size if sel is None else int(sel.shape[0])
+        ix = None if sel is None else sel.long()
+        cols = []
+        for t, a in rows:
+            t = t.expand(self.batch_size, 3) if t.dim() == 1 else t
+            t = t if ix is None else t[ix]
+            cols.append(torch.cat([t, t.new_full((K, 1), a)], dim=1))
+        return torch.stack(cols).contiguous(), True
 
 
 class GraphedStep(object):

@@ -18,11 +18,14 @@ class Scenario(BaseScenario):
             agent.name = 'agent %d' % i
             agent.collide = False
             agent.silent = True
+            agent.color = [0.25, 0.25, 0.25]       # simple.py:26-31 (rendering only)
         world.landmarks = [Landmark() for _ in range(1)]
         for i, landmark in enumerate(world.landmarks):
             landmark.name = 'landmark %d' % i
             landmark.collide = False
             landmark.movable = False
+            landmark.color = [0.75, 0.75, 0.75]
+        world.landmarks[0].color = [0.75, 0.25, 0.25]
         world.allocate()
         return world
 

@@ -23,11 +23,13 @@ class Scenario(BaseScenario):
             agent.collide = True
             agent.silent = True
             agent.size = 0.15
+            agent.color = [0.35, 0.35, 0.85]       # simple_spread.py:33-37 (rendering only)
         world.landmarks = [Landmark() for _ in range(num_landmarks)]
         for i, landmark in enumerate(world.landmarks):
             landmark.name = 'landmark %d' % i
             landmark.collide = False
             landmark.movable = False
+            landmark.color = [0.25, 0.25, 0.25]
         world.allocate()
         return world
 

@@ -26,6 +26,7 @@ class Scenario(BaseScenario):
             agent.size = 0.075 if agent.adversary else 0.05
             agent.accel = 3.0 if agent.adversary else 4.0
             agent.max_speed = 1.0 if agent.adversary else 1.3
+            agent.color = [0.85, 0.35, 0.35] if agent.adversary else [0.35, 0.85, 0.35]   # simple_tag.py:41-45 (rendering only)
         world.landmarks = [Landmark() for _ in range(num_landmarks)]
         for i, landmark in enumerate(world.landmarks):
             landmark.name = 'landmark %d' % i
@@ -33,6 +34,7 @@ class Scenario(BaseScenario):
             landmark.movable = False
             landmark.size = 0.2
             landmark.boundary = False
+            landmark.color = [0.25, 0.25, 0.25]
         world.allocate()
         return world
 
