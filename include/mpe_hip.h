@@ -293,6 +293,52 @@ int mpe_step_server_start(const MpeScenarioDesc *desc, const MpeBuffers *bufs, i
 int mpe_step_server_ring(const MpeStepServer *srv, uint64_t n_steps /* door += n_steps */, void *caller_stream);
 int mpe_step_server_wait(const MpeStepServer *srv, int64_t B, uint64_t steps_completed, void *caller_stream);
 
+/* ---- policy rollouts: a per-agent MLP actor evaluated inside the fused rollout ---------------------------------------------
+ * The loop of the reference's bin/interactive.py (act_n = [policy.action(obs_n[i])]; env.step(act_n)) as ONE launch of T steps:
+ * at global step g (step0 <= g < step0 + T) the worlds first restart if episode_len > 0 and g % episode_len == 0 (mpe_reset's
+ * draws of `seed` for episode g / episode_len), then agent i's actor maps the observation of the state the step starts from to
+ * five fp32 logits z, the logits become agent i's action row (mode below), and the step runs with those rows -- its obs / rew /
+ * done go to block t (trajectory) or block 0 of bufs, exactly as mpe_rollout_random writes them.
+ * Modes: GREEDY a one-hot row at argmax z (ties: the lowest index, np.argmax); SOFTMAX the row softmax(z) itself (the env
+ * applies it as u = (p1 - p2, p3 - p4) * accel); SAMPLE a one-hot row at an inverse-CDF draw from softmax(z) with the 24-bit
+ * uniform u = (bits >> 8) * 2^-24 of Philox4x32-10, key = policy->seed, counter = (world lo, world hi ^ step hi, agent >> 2,
+ * 0x504F4C49 ("POLI") ^ step lo), bits = word (agent & 3) -- world = world_offset + w, step = g.
+ * An actor is 1..3 Linear layers (fp32, hidden widths <= 64) with one activation (ReLU / Tanh) between them; its input width is
+ * agent i's observation width and its output width is 5.  PACKED layout of one actor, at weights + offset[i] (floats, offset a
+ * multiple of 16): for each layer l, W_l as [in_l][out_l'] row-major (W_l[k][j] = Linear.weight[j][k]) followed by bias[out_l'],
+ * where in_0 = the observation width, in_l = 64 for l > 0, out_l' = 64 for a hidden layer and 8 for the last; every padding
+ * entry is zero.  Agents may share one packed actor (equal offsets).
+ * Scope: simple, simple_spread with up to 3 agents, simple_adversary (3 agents, 1 adversary) and simple_push.  Not served:
+ * simple_tag, larger simple_spread shapes, the communication scenarios, row programs.  mpe_rollout_policy_supported says
+ * whether a (descriptor, policy) has a kernel.                                                                               */
+#define MPE_POLICY_MAX_AGENTS 16
+#define MPE_POLICY_MAX_LAYERS 3
+#define MPE_POLICY_MAX_WIDTH 64
+#define MPE_POLICY_MAX_LAUNCH_WORK (1LL << 25) /* T * B * A of one mpe_rollout_policy launch (~0.1 s of kernel time)   */
+enum { MPE_POLICY_GREEDY = 0, MPE_POLICY_SAMPLE = 1, MPE_POLICY_SOFTMAX = 2 };
+enum { MPE_POLICY_RELU = 0, MPE_POLICY_TANH = 1 };
+typedef struct MpePolicy {
+  int32_t n_layers[MPE_POLICY_MAX_AGENTS];        /* Linear layers of agent i's actor, 1..3                                */
+  int32_t width[MPE_POLICY_MAX_AGENTS][4];        /* width[i][0] = input (obs width), width[i][l + 1] = output of layer l   */
+  int32_t activation[MPE_POLICY_MAX_AGENTS];      /* MPE_POLICY_RELU / TANH (between the layers)                           */
+  int64_t offset[MPE_POLICY_MAX_AGENTS];          /* floats from `weights` to agent i's packed actor                       */
+  const float *weights;                           /* device memory, the packed actors                                      */
+  int32_t mode;                                   /* MPE_POLICY_GREEDY / SAMPLE / SOFTMAX                                  */
+  int32_t reserved_;
+  uint64_t seed;                                  /* key of the SAMPLE draws                                               */
+} MpePolicy;
+/* 1 if (desc, policy, B) has a kernel, 0 if not (unsupported scenario or shape), < 0 for an invalid descriptor or policy. */
+int mpe_rollout_policy_supported(const MpeScenarioDesc *desc, const MpePolicy *policy, int64_t B);
+size_t mpe_sizeof_policy(void);
+/* act_out: T consecutive [A][B][5] tensors, the rows applied at each step (required).  obs_in_out: NULL, or T consecutive blocks
+ * of obs_off[A] * B floats laid out as bufs->obs, the decision observations.  logp_out: NULL, or T consecutive [A][B] tensors,
+ * log softmax(z)[chosen] (GREEDY / SAMPLE).  1 <= T <= 65535 and T * B * A <= MPE_POLICY_MAX_LAUNCH_WORK per launch (no launch
+ * runs unbounded: longer rollouts are several launches with step0 advanced).  world.pos / vel hold the state after the last step; the landmarks and picks of the last
+ * in-launch reset are written back as mpe_rollout_random does. */
+int mpe_rollout_policy(const MpeScenarioDesc *desc, const MpeBuffers *bufs, const MpePolicy *policy, int64_t B, int32_t T,
+                       int32_t episode_len, float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset,
+                       int32_t trajectory, float *act_out, float *obs_in_out, float *logp_out, void *stream);
+
 /* ---- composable output stage: a USER scenario's observation / reward as a row program ---------------------------------
  * The reference's plug-in promise (README "Creating new environments", scenario.py:4-10) is that new scenarios are the
  * normal use; every shipped observation is a concatenation of a few segment kinds and every shipped reward an ordered

@@ -5,5 +5,7 @@ from .make_env import make_env  # noqa: F401
 from .environment import MultiAgentEnv, BatchMultiAgentEnv, GraphedStep  # noqa: F401
 from .scenario import BaseScenario  # noqa: F401
 from . import core, scenarios  # noqa: F401
+from .rollout import MlpPolicy, PolicyRollout, PolicyTrajectory  # noqa: F401
 
-__all__ = ["make_env", "MultiAgentEnv", "BatchMultiAgentEnv", "GraphedStep", "BaseScenario", "core", "scenarios"]
+__all__ = ["make_env", "MultiAgentEnv", "BatchMultiAgentEnv", "GraphedStep", "BaseScenario", "core", "scenarios", "MlpPolicy", "PolicyRollout",
+           "PolicyTrajectory"]

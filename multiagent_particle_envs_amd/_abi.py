@@ -57,6 +57,18 @@ class MpeRenderArgs(C.Structure):      # include/mpe_hip.h: one mpe_render call
                 ("size", C.c_int32), ("reserved_", C.c_int32), ("out", C.c_void_p)]
 
 
+MPE_POLICY_MAX_AGENTS, MPE_POLICY_MAX_LAYERS, MPE_POLICY_MAX_WIDTH = 16, 3, 64
+MPE_POLICY_MAX_LAUNCH_WORK = 1 << 25      # T * B * A of one mpe_rollout_policy launch
+MPE_POLICY_GREEDY, MPE_POLICY_SAMPLE, MPE_POLICY_SOFTMAX = 0, 1, 2
+MPE_POLICY_RELU, MPE_POLICY_TANH = 0, 1
+
+
+class MpePolicy(C.Structure):          # include/mpe_hip.h: per-agent MLP actors of mpe_rollout_policy
+    _fields_ = [("n_layers", C.c_int32 * MPE_POLICY_MAX_AGENTS), ("width", (C.c_int32 * 4) * MPE_POLICY_MAX_AGENTS),
+                ("activation", C.c_int32 * MPE_POLICY_MAX_AGENTS), ("offset", C.c_int64 * MPE_POLICY_MAX_AGENTS),
+                ("weights", C.c_void_p), ("mode", C.c_int32), ("reserved_", C.c_int32), ("seed", C.c_uint64)]
+
+
 class MpeBuffers(C.Structure):
     _fields_ = [
         ("pos", C.c_void_p), ("vel", C.c_void_p), ("act", C.c_void_p), ("ids", C.c_void_p), ("u", C.c_void_p),
@@ -142,6 +154,11 @@ EXPORTS = {
     "mpe_step_server_wait": (C.c_int, [C.POINTER(MpeStepServer), C.c_int64, C.c_uint64, C.c_void_p]),
     "mpe_render": (C.c_int, [C.POINTER(MpeScenarioDesc), C.POINTER(MpeRenderArgs), C.c_void_p]),
     "mpe_sizeof_render_args": (C.c_size_t, []),
+    "mpe_sizeof_policy": (C.c_size_t, []),
+    "mpe_rollout_policy_supported": (C.c_int, [C.POINTER(MpeScenarioDesc), C.POINTER(MpePolicy), C.c_int64]),
+    "mpe_rollout_policy": (C.c_int, [C.POINTER(MpeScenarioDesc), C.POINTER(MpeBuffers), C.POINTER(MpePolicy), C.c_int64, C.c_int32,
+                                     C.c_int32, C.c_float, C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -171,7 +188,7 @@ def lib():
         raise MpeError("ABI version mismatch: library %d, binding %d" % (handle.mpe_abi_version(), MPE_ABI_VERSION))
     if handle.mpe_sizeof_desc() != C.sizeof(MpeScenarioDesc) or handle.mpe_sizeof_buffers() != C.sizeof(MpeBuffers) or \
             handle.mpe_sizeof_row_program() != C.sizeof(MpeRowProgram) or handle.mpe_sizeof_step_server() != C.sizeof(MpeStepServer) or \
-            handle.mpe_sizeof_render_args() != C.sizeof(MpeRenderArgs):
+            handle.mpe_sizeof_render_args() != C.sizeof(MpeRenderArgs) or handle.mpe_sizeof_policy() != C.sizeof(MpePolicy):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")
     _lib = handle
     return _lib

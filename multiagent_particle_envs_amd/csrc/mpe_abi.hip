@@ -172,6 +172,7 @@ size_t mpe_sizeof_desc(void) { return sizeof(MpeScenarioDesc); }
 size_t mpe_sizeof_buffers(void) { return sizeof(MpeBuffers); }
 size_t mpe_sizeof_row_program(void) { return sizeof(MpeRowProgram); }
 size_t mpe_sizeof_step_server(void) { return sizeof(MpeStepServer); }
+size_t mpe_sizeof_policy(void) { return sizeof(MpePolicy); }
 
 int mpe_fill_obs_layout(MpeScenarioDesc *d) {
   if (int rc = check_desc(d, "mpe_fill_obs_layout")) return rc;
@@ -485,6 +486,91 @@ static int rollout_fused(const char *what, const float *act_seq, const MpeScenar
   const mpe::NarrowDesc n = make_narrow(d, b, (size_t)B);
   return hip_result(mpe::launch_split(true, d->kind, d->n_agents, d->n_landmarks, d->n_adversaries, n, *b, (size_t)B,
                                       ra, s), what);
+}
+
+// ---- policy rollouts (mpe_split.hip, POL) --------------------------------------------------------------------------------
+static int check_policy(const MpeScenarioDesc *d, const MpePolicy *p, const char *what) {
+  if (!p) return fail(MPE_EINVAL, "%s: policy is NULL", what);
+  if (p->mode < MPE_POLICY_GREEDY || p->mode > MPE_POLICY_SOFTMAX) return fail(MPE_EINVAL, "%s: bad policy mode %d", what, p->mode);
+  const int A = d->n_agents;
+  if (A > MPE_POLICY_MAX_AGENTS) return fail(MPE_EUNSUPPORTED, "%s: more than %d agents", what, MPE_POLICY_MAX_AGENTS);
+  for (int i = 0; i < A; ++i) {
+    const int nl = p->n_layers[i];
+    if (nl < 1 || nl > MPE_POLICY_MAX_LAYERS) return fail(MPE_EINVAL, "%s: agent %d: %d Linear layers (1..%d)", what, i, nl, MPE_POLICY_MAX_LAYERS);
+    const int D = d->obs_off[i + 1] - d->obs_off[i];
+    if (p->width[i][0] != D) return fail(MPE_EINVAL, "%s: agent %d: actor input width %d, observation width %d", what, i, p->width[i][0], D);
+    for (int l = 1; l < nl; ++l)
+      if (p->width[i][l] < 1 || p->width[i][l] > MPE_POLICY_MAX_WIDTH)
+        return fail(MPE_EINVAL, "%s: agent %d: hidden width %d (1..%d)", what, i, p->width[i][l], MPE_POLICY_MAX_WIDTH);
+    if (p->width[i][nl] != MPE_ACTION_DIM) return fail(MPE_EINVAL, "%s: agent %d: actor output width %d (need %d)", what, i, p->width[i][nl], MPE_ACTION_DIM);
+    if (p->activation[i] != MPE_POLICY_RELU && p->activation[i] != MPE_POLICY_TANH)
+      return fail(MPE_EINVAL, "%s: agent %d: bad activation %d", what, i, p->activation[i]);
+    if (p->offset[i] < 0 || p->offset[i] % 16 != 0 || p->offset[i] > INT32_MAX - 8192)
+      return fail(MPE_EINVAL, "%s: agent %d: offset %lld (a multiple of 16 floats)", what, i, (long long)p->offset[i]);
+  }
+  return 0;
+}
+static int policy_shape(const MpeScenarioDesc *d) {
+  const bool kind_ok = d->kind == MPE_SCN_SIMPLE || d->kind == MPE_SCN_SPREAD || d->kind == MPE_SCN_TAG || d->kind == MPE_SCN_ADVERSARY ||
+                       d->kind == MPE_SCN_PUSH;
+  return kind_ok && d->n_agents + d->n_landmarks <= mpe::kNarrowMaxE &&
+         mpe::split_policy_supports(d->kind, d->n_agents, d->n_landmarks, d->n_adversaries);
+}
+int mpe_rollout_policy_supported(const MpeScenarioDesc *d, const MpePolicy *p, int64_t B) {
+  const char *what = "mpe_rollout_policy_supported";
+  if (int rc = check_desc(d, what)) return rc;
+  if (int rc = check_policy(d, p, what)) return rc == MPE_EUNSUPPORTED ? 0 : rc;
+  return B > 0 && policy_shape(d) ? 1 : 0;
+}
+int mpe_rollout_policy(const MpeScenarioDesc *d, const MpeBuffers *b, const MpePolicy *p, int64_t B, int32_t T, int32_t episode_len,
+                       float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset, int32_t trajectory, float *act_out,
+                       float *obs_in_out, float *logp_out, void *stream) {
+  const char *what = "mpe_rollout_policy";
+  if (int rc = check_desc(d, what)) return rc;
+  if (int rc = check_state(b, B, what)) return rc;
+  if (int rc = need(b->obs, what, "obs")) return rc;
+  if (int rc = check_info(d, b, what)) return rc;
+  if (int rc = check_policy(d, p, what)) return rc;
+  if (d->n_choices > 0 && d->kind >= MPE_SCN_ADVERSARY)
+    if (int rc = need(b->choice, what, "choice (the per-world picks of reset_world)")) return rc;
+  if (!p->weights) return fail(MPE_EINVAL, "%s: policy->weights is NULL", what);
+  if (!act_out) return fail(MPE_EINVAL, "%s: act_out is NULL", what);
+  if (logp_out && p->mode == MPE_POLICY_SOFTMAX) return fail(MPE_EINVAL, "%s: logp_out needs a chosen index (GREEDY / SAMPLE)", what);
+  if (T < 1 || T > 65535 || episode_len < 0) return fail(MPE_EINVAL, "%s: 1 <= T <= 65535 and episode_len >= 0 (got T=%d)", what, T);
+  if (!policy_shape(d))
+    return fail(MPE_EUNSUPPORTED, "%s: policy rollouts exist for simple, simple_spread with up to 3 agents, simple_adversary "
+                "(3 agents, 1 adversary) and simple_push (kind=%d A=%d L=%d n_adv=%d)", what, d->kind,
+                d->n_agents, d->n_landmarks, d->n_adversaries);
+  if (B == 0) return 0;
+  // every launch is bounded by its WORK, not by its step count: an actor step costs ~100x a random-move step
+  if ((int64_t)T * B * d->n_agents > MPE_POLICY_MAX_LAUNCH_WORK)
+    return fail(MPE_EINVAL, "%s: T * B * A = %lld agent-world-steps in one launch (at most %lld: split the rollout into launches "
+                "with step0 advanced)", what, (long long)T * B * d->n_agents, (long long)MPE_POLICY_MAX_LAUNCH_WORK);
+  mpe::RollArgs ra;
+  std::memset(&ra, 0, sizeof(ra));
+  ra.T = T;
+  ra.episode_len = episode_len;
+  ra.trajectory = trajectory ? 1 : 0;
+  ra.landmark_range = landmark_range;
+  ra.seed = seed;
+  ra.step0 = step0;
+  ra.world_offset = (uint64_t)world_offset;
+  mpe::PolArgs pa;
+  std::memset(&pa, 0, sizeof(pa));
+  pa.w = p->weights;
+  pa.act_out = act_out;
+  pa.obs_in = obs_in_out;
+  pa.logp = logp_out;
+  pa.seed = p->seed;
+  pa.mode = p->mode;
+  for (int i = 0; i < d->n_agents; ++i) {
+    pa.nl[i] = p->n_layers[i];
+    pa.act[i] = p->activation[i];
+    pa.off[i] = (int32_t)p->offset[i];
+  }
+  const mpe::NarrowDesc n = make_narrow(d, b, (size_t)B);
+  return hip_result(mpe::launch_split_policy(d->kind, d->n_agents, d->n_landmarks, d->n_adversaries, n, *b, (size_t)B, ra, pa,
+                                             static_cast<hipStream_t>(stream)), what);
 }
 
 // ---- the step server (mpe_split.hip, SERVE) ------------------------------------------------------------------------------

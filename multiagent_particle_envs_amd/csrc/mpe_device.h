@@ -350,6 +350,19 @@ __host__ __device__ inline int comm_draw(uint64_t seed, uint64_t b, uint64_t t, 
   return (int)(((uint64_t)w * (uint32_t)n) >> 32);
 }
 
+// The 32 random bits of agent i's SAMPLE draw in world b at global step `t` (mpe_rollout_policy): action_block's counter layout
+// on a stream of its own, keyed by the policy seed.
+constexpr uint32_t kStreamPolicy = 0x504f4c49u;  // "POLI"
+__host__ __device__ inline uint32_t policy_bits(uint64_t seed, uint64_t b, uint64_t t, int i) {
+  U4 c;
+  c.x = (uint32_t)b;
+  c.y = (uint32_t)(b >> 32) ^ (uint32_t)(t >> 32);
+  c.z = (uint32_t)(i >> 2);
+  c.w = kStreamPolicy ^ (uint32_t)t;
+  const U4 o = philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return (i & 3) == 0 ? o.x : (i & 3) == 1 ? o.y : (i & 3) == 2 ? o.z : o.w;
+}
+
 // ---- wave-private LDS transpose: 64 per-lane rows of D floats -> one contiguous 64*D-float run ----
 // The drop-in obs layout is row-major [B][D] per agent (72-byte rows at D=18): a thread-per-world
 // store would be stride-D scattered.  Each wave parks its 64 rows in its own LDS tile and streams

@@ -81,6 +81,21 @@ int launch_split_serve(int kind, int A, int L, int nadv, const NarrowDesc &d, co
                        const ServeHandles &h, hipStream_t stream);
 int launch_split(bool roll, int kind, int A, int L, int nadv, const NarrowDesc &d, const MpeBuffers &b, size_t B,
                  const RollArgs &ra, hipStream_t stream);
+// the policy rollout (mpe_split.hip, POL): the fused rollout whose moves come from a per-agent MLP evaluated on the observation
+// tile inside the kernel (mpe_rollout_policy).  Actors packed as include/mpe_hip.h describes (MpePolicy); checked by the caller.
+constexpr int kPolMaxAgents = MPE_POLICY_MAX_AGENTS;
+struct PolArgs {
+  const float *w;        // packed actors (device)
+  float *act_out;        // T x [A][B][5]: the rows applied at each step
+  float *obs_in;         // T x obs_off[A] * B: the decision observations, or nullptr
+  float *logp;           // T x [A][B]: log softmax(z)[chosen] (greedy / sample), or nullptr
+  uint64_t seed;         // key of the sample draws (kStreamPolicy)
+  int32_t mode;          // MPE_POLICY_GREEDY / SAMPLE / SOFTMAX
+  int32_t nl[kPolMaxAgents], act[kPolMaxAgents], off[kPolMaxAgents];   // per agent: Linear layers, activation, float offset
+};
+bool split_policy_supports(int kind, int A, int L, int nadv);
+int launch_split_policy(int kind, int A, int L, int nadv, const NarrowDesc &d, const MpeBuffers &b, size_t B, const RollArgs &ra,
+                        const PolArgs &pol, hipStream_t stream);
 
 // the composable output stage (mpe_rows.hip): kernel-side header of an MpeRowProgram
 constexpr int kRowSlots = 8;

@@ -468,6 +468,98 @@ __device__ __forceinline__ void reward_wave(const NarrowDesc &d, const float *co
   }
 }
 
+// ---- the policy rollout (POL): agent i's MLP actor on its observation tile, one lane = one world -------------------------
+// The actor's weights are WAVE-UNIFORM (one agent per wave): read through the constant address space they are scalar loads
+// (s_load_dwordx8 / x16 into SGPRs) and every multiply-add is one v_pk_fma_f32 -- two hidden units of one lane -- with the
+// weight pair as its scalar operand and the input broadcast from one VGPR.  Nothing of the actor passes through LDS or HBM
+// except the weights themselves and the observation row the wave has already assembled in its tile.
+// Order of the fp32 arithmetic (what the tests restate): h_j = bias_j, then h_j = fma(W[k][j], x_k, h_j) for k ascending, then
+// the activation; hidden units are computed 64 at a time (zero padding: a padded unit stays 0 under ReLU and Tanh, and its
+// outgoing weights are zero).  Tanh is 1 - 2 / (exp(2x) + 1) on v_exp_f32 (absolute error < 2e-7).
+typedef float vf2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(4))) const vf2 cvf2;
+__device__ __forceinline__ float pol_act(float x, bool tnh) {
+  if (tnh) return 1.f - __fdividef(2.f, __builtin_amdgcn_exp2f(x * 2.88539008177792681f) + 1.f);
+  return fmaxf(x, 0.f);
+}
+__device__ __forceinline__ vf2 pol_act2(vf2 x, bool tnh) { return vf2{pol_act(x.x, tnh), pol_act(x.y, tnh)}; }
+// layer 0: NO2 unit pairs from the D inputs of this lane's tile row (element k at row[4 * ((k >> 2) ^ sw) + (k & 3)]: the
+// tile's own layout, swizzled or not); with `rec`, the inputs are also stored as this lane's decision observation
+template <int NO2>
+__device__ __forceinline__ void pol_layer0(const cvf2 *W, const float *row, int sw, int D, float *rec, vf2 (&h)[NO2]) {
+#pragma unroll
+  for (int j = 0; j < NO2; ++j) h[j] = W[D * NO2 + j];
+  for (int k = 0; k < D; ++k) {
+    const float x = row[(((k >> 2) ^ sw) << 2) | (k & 3)];
+    if (rec) rec[k] = x;
+    const vf2 xx = {x, x};
+#pragma unroll
+    for (int j = 0; j < NO2; ++j) h[j] = __builtin_elementwise_fma(W[k * NO2 + j], xx, h[j]);
+  }
+}
+// a later layer: NO2 unit pairs from the 64 activations h (W: [64][2 * NO2], then the bias)
+template <int NO2>
+__device__ __forceinline__ void pol_layer(const cvf2 *W, const vf2 (&h)[32], vf2 (&o)[NO2]) {
+#pragma unroll
+  for (int j = 0; j < NO2; ++j) o[j] = W[64 * NO2 + j];
+#pragma unroll
+  for (int k = 0; k < 64; ++k) {
+    const float x = (k & 1) ? h[k >> 1].y : h[k >> 1].x;
+    const vf2 xx = {x, x};
+#pragma unroll
+    for (int j = 0; j < NO2; ++j) o[j] = __builtin_elementwise_fma(W[k * NO2 + j], xx, o[j]);
+    // (the scheduler may not hoist the scalar weight loads of later inputs above this point: left to itself it issues them
+    //  all up front, runs out of SGPRs and spills them through VGPR lanes to scratch)
+    if ((k & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+  }
+}
+// z = actor(x): nl Linear layers; W points at the packed actor (include/mpe_hip.h, MpePolicy)
+__device__ __forceinline__ void pol_logits(const float *Wg, int nl, bool tnh, const float *row, int sw, int D, float *rec,
+                                           float (&z)[5]) {
+  const cvf2 *W = (const cvf2 *)(uintptr_t)Wg;
+  vf2 o[4];
+  if (nl == 1) {
+    pol_layer0<4>(W, row, sw, D, rec, o);
+  } else {
+    vf2 h[32];
+    pol_layer0<32>(W, row, sw, D, rec, h);
+#pragma unroll
+    for (int j = 0; j < 32; ++j) h[j] = pol_act2(h[j], tnh);
+    const cvf2 *W1 = W + (size_t)(D + 1) * 32;
+    if (nl == 2) {
+      pol_layer<4>(W1, h, o);
+    } else {
+      // the second hidden layer 16 units at a time, each group folded into the logits at once (ascending unit order, as
+      // one pass would): 64 + 16 live accumulators instead of 128
+      const cvf2 *W2 = W1 + 65 * 32;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = W2[64 * 4 + j];
+#pragma unroll 1
+      for (int c = 0; c < 4; ++c) {
+        vf2 g[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) g[j] = W1[64 * 32 + 8 * c + j];
+#pragma unroll
+        for (int k = 0; k < 64; ++k) {
+          const float x = (k & 1) ? h[k >> 1].y : h[k >> 1].x;
+          const vf2 xx = {x, x};
+#pragma unroll
+          for (int j = 0; j < 8; ++j) g[j] = __builtin_elementwise_fma(W1[k * 32 + 8 * c + j], xx, g[j]);
+          if ((k & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+          const float x = pol_act((u & 1) ? g[u >> 1].y : g[u >> 1].x, tnh);
+          const vf2 xx = {x, x};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) o[j] = __builtin_elementwise_fma(W2[(16 * c + u) * 4 + j], xx, o[j]);
+        }
+      }
+    }
+  }
+  z[0] = o[0].x; z[1] = o[0].y; z[2] = o[1].x; z[3] = o[1].y; z[4] = o[2].x;
+}
+
 template <int AUX>
 __device__ __forceinline__ void store_state(const MpeBuffers &b, size_t B, int i, size_t w0, unsigned ln, float mx,
                                             float my, float mvx, float mvy) {
@@ -521,12 +613,16 @@ __device__ __forceinline__ void drain_stores() { asm volatile("s_waitcnt vmcnt(0
 
 template <int KIND, int A, int L, int NADV, bool ROLL, int RP /* row-store policy: kRowsNt / kRowsSc1 (mpe_device.h) */,
           bool DUALP = false /* the dual-role rollout: physics + rows waves per agent */,
-          bool SERVE = false /* the step server: ROLL commanded step by step (above) */>
-__global__ void __launch_bounds__((SplitShape<KIND, A, L, NADV>::waves(DUALP) * kWave))
-k_split(float *const g_pos, float *const g_vel, const float *const g_act, const int32_t *const g_ids, const size_t B,
-        const int g_wpw, const int g_observe_only, const unsigned g_movable, const NarrowDesc d, const MpeBuffers b_in,
-        const RollArgs ra, const ServeArgs sv) {
+          bool SERVE = false /* the step server: ROLL commanded step by step (above) */,
+          bool POL = false /* the policy rollout: ROLL with the moves from the agents' actors (mpe_rollout_policy) */>
+__device__ __forceinline__ void split_body(float *const g_pos, float *const g_vel, const float *const g_act, const int32_t *const g_ids,
+                                           const size_t B, const int g_wpw, const int g_observe_only, const unsigned g_movable,
+                                           const NarrowDesc &d, const MpeBuffers &b_in, const RollArgs &ra, const ServeArgs &sv,
+                                           const PolArgs &pol) {
   static_assert(!SERVE || (ROLL && RP == kRowsSc1), "the step server: a rollout instantiation, write-through stores");
+  static_assert(!POL || (ROLL && !SERVE && !DUALP), "the policy rollout: a single-role rollout instantiation");
+  static_assert(!POL || KIND == MPE_SCN_SIMPLE || KIND == MPE_SCN_SPREAD || KIND == MPE_SCN_ADVERSARY || KIND == MPE_SCN_PUSH,
+                "the policy rollout: scenarios whose observation rows read no other agent's velocity");
   // the agents' utterances: the caller's rows (a launched step), drawn in the kernel (the rollout), or the caller's rows of THIS step
   // out of the utterance ring, read at system scope (the step server)
   constexpr int WM = SERVE ? kWordRowSys : (ROLL ? kWordDrawn : kWordRow);
@@ -687,7 +783,7 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
           --cd;
         }
       }
-      if (ROLL && !SERVE && !OWN_DRAW && t + 1 < T) {   // the moves of step t + 1: read by the agent waves behind this step's barrier
+      if (ROLL && !SERVE && !OWN_DRAW && !POL && t + 1 < T) {   // the moves of step t + 1: read by the agent waves behind this step's barrier
         const uint64_t gt1 = ra.step0 + (uint64_t)t + 1;
 #pragma unroll
         for (int q = 0; q < (A + 3) / 4; ++q) {
@@ -781,25 +877,33 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
   [[maybe_unused]] bool did_reset = false;   // served steps: an in-launch reset moved the landmarks / picks -> behind_barrier stores them
   // step_forces: [in-kernel reset,] this step's move, the action force and the contacts with every other entity in
   // ascending order (Q9) -- everything of World.step (core.py:117-155) up to the force on agent i
+  // roll_reset: the in-kernel reset at the head of a rollout step (reset_world, as mpe_reset does it for episode ep = gt /
+  // episode_len) when the step is an episode start -> whether it was
+  auto roll_reset = [&]() -> bool {
+    const bool reset_now = countdown == 0;
+    if (countdown >= 0) countdown = reset_now ? ra.episode_len - 1 : countdown - 1;
+    if (reset_now) {
+#pragma unroll
+      for (int e = 0; e < E; ++e) reset_draw(ra.seed, gw, ep, e, e < A ? 1.0f : ra.landmark_range, px[e], py[e]);
+#pragma unroll
+      for (int a = 0; a < A; ++a)
+        if (a == i) { mx = px[a]; my = py[a]; }
+      mvx = 0.f;
+      mvy = 0.f;
+      if (NCH >= 1) goal = choice_draw(ra.seed, gw, ep, 0, d.choice_pop[0]);
+      if (NCH >= 2) pick1 = choice_draw(ra.seed, gw, ep, 1, d.choice_pop[1]);
+      ++ep;
+      if (SERVE) did_reset = true;
+    }
+    return reset_now;
+  };
+  // POL: the action row this agent's actor chose for the current step (floats 1..4: what the step decodes)
+  [[maybe_unused]] float pa1 = 0.f, pa2 = 0.f, pa3 = 0.f, pa4 = 0.f;
   auto step_forces = [&](const int t, float &fx, float &fy) {
     float ux, uy;
     const uint64_t gt = ra.step0 + (uint64_t)t;   // global step: indexes the move / word streams of the rollout
     if (ROLL) {
-      const bool reset_now = countdown == 0;
-      if (countdown >= 0) countdown = reset_now ? ra.episode_len - 1 : countdown - 1;
-      if (reset_now) {  // reset_world, as mpe_reset does it for episode ep = gt / episode_len
-#pragma unroll
-        for (int e = 0; e < E; ++e) reset_draw(ra.seed, gw, ep, e, e < A ? 1.0f : ra.landmark_range, px[e], py[e]);
-#pragma unroll
-        for (int a = 0; a < A; ++a)
-          if (a == i) { mx = px[a]; my = py[a]; }
-        mvx = 0.f;
-        mvy = 0.f;
-        if (NCH >= 1) goal = choice_draw(ra.seed, gw, ep, 0, d.choice_pop[0]);
-        if (NCH >= 2) pick1 = choice_draw(ra.seed, gw, ep, 1, d.choice_pop[1]);
-        ++ep;
-        if (SERVE) did_reset = true;
-      }
+      if constexpr (!POL) roll_reset();   // (the policy rollout resets in front of its decision, below)
       // the one-hot row mpe_random_actions would write: drawn here at the first step, by the reward wave afterwards
       // (dual-role rollout of the kinds in MPE_SPLIT_DUAL_OWN_DRAW: always drawn here)
       if constexpr (SERVE) {
@@ -820,6 +924,10 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
           ux = 0.f;
           uy = 0.f;
         }
+      } else if constexpr (POL) {
+        // the actor's row, decoded as the step server decodes a caller's row (environment.py:174-181)
+        ux = (pa1 - pa2) * accel_i;
+        uy = (pa3 - pa4) * accel_i;
       } else {
       const int m = (t == 0 || OWN_DRAW) ? action_draw(ra.seed, gw, gt, i) : mv[((t & 1) * A + i) * kWave + lane];
       ux = ((m == 1 ? 1.f : 0.f) - (m == 2 ? 1.f : 0.f)) * accel_i;
@@ -935,8 +1043,23 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
     for (int a = 0; a < A; ++a) asm volatile("" ::"v"(px[a]), "v"(py[a]));   // the siblings' positions have arrived
 #endif
   };
-  // rows: agent i's observation row of step t -- the 64 rows of the wave assembled in its LDS tile, streamed out
-  auto rows = [&](const int t) {
+  // POL: where the decision observation sits in the tile -- row width, row stride and this lane's piece swizzle (flush_rows'
+  // layouts)
+  [[maybe_unused]] int pol_D = 0, pol_S = 0, pol_sw = 0;
+  auto note_tile = [&](auto dc, auto pc) {
+    if constexpr (POL) {
+      constexpr int D = decltype(dc)::value;
+      constexpr bool P = decltype(pc)::value;
+      constexpr int NS = (P && row_vec4<D>()) ? D / 4 : 0;
+      pol_D = D;
+      pol_S = P ? pair_stride<D>() : tile_stride<D>();
+      pol_sw = NS ? swz4<NS>(lane) : 0;
+    }
+  };
+  // rows: agent i's observation row of step t -- the 64 rows of the wave assembled in its LDS tile, streamed out.
+  // pre (the policy rollout): the row of the state a step STARTS from (its first step, an episode start) is assembled in the
+  // tile for the actor and not stored
+  auto rows = [&](const int t, const bool pre) {
     if (MPE_SPLIT_ABLATE & 4) return;   // (no observation rows)
     const float *const X = xch + (ROLL ? (t & 1) * A * XW * kWave : 0);
     const uint64_t gt = ra.step0 + (uint64_t)t;   // global step (the word stream of the rollout)
@@ -950,7 +1073,8 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
 #pragma unroll
         for (int l = 0; l < L; ++l) r.put(2 + 2 * l, px[A + l] - mx, py[A + l] - my);
       }
-      flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
+      note_tile(std::integral_constant<int, D>{}, std::bool_constant<true>{});
+        if (!pre) flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
     }
     if (KIND == MPE_SCN_SPREAD) {  // simple_spread.py:84-100
       constexpr int D = 4 + 2 * L + 4 * (A - 1);
@@ -970,7 +1094,8 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
 #pragma unroll
         for (int z = 0; z < 2 * (A - 1); z += 2) r.put(k + z, 0.f, 0.f);  // silent agents' comm
       }
-      flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
+      note_tile(std::integral_constant<int, D>{}, std::bool_constant<true>{});
+        if (!pre) flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
     }
     if (KIND == MPE_SCN_TAG) {  // simple_tag.py:131-147
       constexpr int NG = A - NADV;
@@ -998,7 +1123,8 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
             k += 2;
           }
         }
-        flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
+        note_tile(std::integral_constant<int, D>{}, std::bool_constant<true>{});
+        if (!pre) flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
       };
       if (adv) row(std::integral_constant<int, DA>{});
       else     row(std::integral_constant<int, DG>{});
@@ -1021,7 +1147,8 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
             k += 2;
           }
         }
-        flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
+        note_tile(std::integral_constant<int, D>{}, std::bool_constant<true>{});
+        if (!pre) flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
       };
       if (adv) row(std::integral_constant<int, DA>{}, std::false_type{});
       else     row(std::integral_constant<int, DG>{}, std::true_type{});
@@ -1063,7 +1190,8 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
           else put2<RS>(tile, lane, k, px[j] - mx, py[j] - my);
           k += 2;
         }
-        flush_rows<D, false, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
+        note_tile(std::integral_constant<int, D>{}, std::bool_constant<false>{});
+        if (!pre) flush_rows<D, false, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
       };
       if (adv) row(std::integral_constant<int, DA>{}, std::false_type{});
       else     row(std::integral_constant<int, DG>{}, std::true_type{});
@@ -1073,7 +1201,8 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
         constexpr int D = 3, RS = tile_stride<D>();
 #pragma unroll
         for (int c = 0; c < 3; ++c) put1<RS>(tile, lane, c, goal == c ? 0.65f : 0.15f);
-        flush_rows<D, false, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
+        note_tile(std::integral_constant<int, D>{}, std::bool_constant<false>{});
+        if (!pre) flush_rows<D, false, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
       } else {        // listener: vel, landmarks, what the speaker says
         constexpr int D = 2 + 2 * L + DC, RS = tile_stride<D>();
         put1<RS>(tile, lane, 0, mvx); put1<RS>(tile, lane, 1, mvy);
@@ -1082,7 +1211,8 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
         const Word<WM> c0 = word_of<DC, WM>(bw, B, w0, ln, 0, ra.seed, gw, gt);
 #pragma unroll
         for (int c = 0; c < DC; ++c) put1<RS>(tile, lane, 2 + 2 * L + c, c0[c]);
-        flush_rows<D, false, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
+        note_tile(std::integral_constant<int, D>{}, std::bool_constant<false>{});
+        if (!pre) flush_rows<D, false, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
       }
     }
     if constexpr (KIND == MPE_SCN_REFERENCE) {  // simple_reference.py:63-83
@@ -1096,7 +1226,8 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
       const Word<WM> co = word_of<DC, WM>(bw, B, w0, ln, 1 - i, ra.seed, gw, gt);
 #pragma unroll
       for (int c = 0; c < DC; ++c) put1<RS>(tile, lane, 5 + 2 * L + c, co[c]);
-      flush_rows<D, false, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
+      note_tile(std::integral_constant<int, D>{}, std::bool_constant<false>{});
+        if (!pre) flush_rows<D, false, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
     }
     if constexpr (KIND == MPE_SCN_CRYPTO) {  // simple_crypto.py:127-169 (goal = pick 0, key = pick 1; colours are one-hots of width dim_c)
       const Word<WM> cs = word_of<DC, WM>(bw, B, w0, ln, 2, ra.seed, gw, gt);   // the speaker's utterance
@@ -1106,7 +1237,8 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
         RowPairs<D> r(tile, lane);
 #pragma unroll
         for (int c = 0; c < DC; c += 2) r.put(c, cs[c], cs[c + 1]);
-        flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
+        note_tile(std::integral_constant<int, D>{}, std::bool_constant<true>{});
+        if (!pre) flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
       } else {
         constexpr int D = 2 * DC;
         RowPairs<D> r(tile, lane);
@@ -1118,7 +1250,8 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
           if (i == 1) r.put(DC + c, cs[c], cs[c + 1]);
           else        r.put(DC + c, pick1 == c ? 1.f : 0.f, pick1 == c + 1 ? 1.f : 0.f);
         }
-        flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
+        note_tile(std::integral_constant<int, D>{}, std::bool_constant<true>{});
+        if (!pre) flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
       }
     }
     if constexpr (KIND == MPE_SCN_WORLD_COMM) {  // simple_world_comm.py:231-289
@@ -1176,6 +1309,77 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
       else          row(std::integral_constant<int, DGd>{}, std::false_type{});
     }
   };
+  // decide (the policy rollout): step t's episode restart, then agent i's action row of step t from its actor.  The observation
+  // of the state step t starts from is the tile's content -- the rows of step t - 1, still there -- except at the launch's first
+  // step and at an episode start, where the wave assembles it first (rows(t, true): from its own registers; no other wave's
+  // state is needed -- the rows of the policy scenarios read every entity's position, which each wave loaded at the first step
+  // and drew itself at a restart, and the agent's own velocity; simple_tag's rows, which read the others' velocities, have no
+  // policy kernel).  Nothing here waits for a sibling:
+  // the decision is on every agent wave's own chain in front of World.step, and the reward wave never sees it.
+  [[maybe_unused]] auto decide = [&](const int t) {
+    const uint64_t gt = ra.step0 + (uint64_t)t;
+    const bool rs = roll_reset();
+    if (t == 0 || rs) {
+      if (HAS_GOAL) goal_pos<A, L>(px, py, goal, gx, gy);
+      rows(t, true);
+    }
+    float *const rec = (pol.obs_in && live) ? pol.obs_in + wave_off((size_t)t * (size_t)d.obs_off[A] * B + B * (size_t)obs_off_i + w0 * (size_t)pol_D) +
+                                                  ln * pol_D
+                                            : nullptr;
+    float z[5];
+    pol_logits(pol.w + pol.off[i], pol.nl[i], pol.act[i] != 0, tile + lane * pol_S, pol_sw, pol_D, rec, z);
+    // argmax (ties: the lowest index, np.argmax), then softmax in fp32: e_j = exp(z_j - max z), s = (((e_0 + e_1) + e_2) + e_3) + e_4,
+    // p_j = e_j / s.  SAMPLE picks the first j <= 3 with u < c_j, c_0 = p_0, c_j = c_{j-1} + p_j (fp32, in that order), else 4.
+    float zm = z[0];
+    int am = 0;
+#pragma unroll
+    for (int j = 1; j < 5; ++j)
+      if (z[j] > zm) { zm = z[j]; am = j; }
+    float e[5], sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      e[j] = __expf(z[j] - zm);
+      sum += e[j];
+    }
+    float r[5];
+    int m = am;
+    if (pol.mode == MPE_POLICY_SOFTMAX) {
+#pragma unroll
+      for (int j = 0; j < 5; ++j) r[j] = e[j] / sum;
+    } else {
+      if (pol.mode == MPE_POLICY_SAMPLE) {
+        const float u = (float)(policy_bits(pol.seed, gw, gt, i) >> 8) * (1.0f / 16777216.0f);
+        float c = 0.f;
+        m = 4;
+        float cj[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          c += e[j] / sum;
+          cj[j] = c;
+        }
+#pragma unroll
+        for (int j = 3; j >= 0; --j)   // (descending: the last hit is the first j with u < c_j)
+          if (u < cj[j]) m = j;
+      }
+#pragma unroll
+      for (int j = 0; j < 5; ++j) r[j] = j == m ? 1.f : 0.f;
+    }
+    if (live) {
+      float *const ar = pol.act_out + wave_off((((size_t)t * A + i) * B + w0) * MPE_ACTION_DIM) + ln * MPE_ACTION_DIM;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) ar[j] = r[j];
+      if (pol.logp) {
+        float zsel = z[0];
+#pragma unroll
+        for (int j = 1; j < 5; ++j) zsel = m == j ? z[j] : zsel;
+        (pol.logp + wave_off(((size_t)t * A + i) * B + w0))[ln] = (zsel - zm) - __logf(sum);
+      }
+    }
+    pa1 = r[1];
+    pa2 = r[2];
+    pa3 = r[3];
+    pa4 = r[4];
+  };
   if constexpr (DUAL) {
     if (is_rows) {
       // ---- ROWS wave of agent i: behind barrier t, step t's state of every agent out of the exchange block -> rows ------
@@ -1212,7 +1416,7 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
         for (int a = 0; a < A; ++a) asm volatile("" ::"v"(px[a]), "v"(py[a]));
 #endif
         MPE_STAMP(4);
-        rows(t);
+        rows(t, false);
         MPE_STAMP(5);
         if constexpr (SERVE) {
           // served: this wave has nothing to do before the next barrier but wait -- it drains its rows and counts itself (the
@@ -1269,6 +1473,7 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
         __syncthreads();   // (barrier t, with the abort word raised)
         return;
       }
+      if constexpr (POL) decide(t);
       step_forces(t, fx, fy);
       step_integrate(t, fx, fy);
       MPE_STAMP(1);
@@ -1280,7 +1485,7 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
       MPE_STAMP(3);
       behind_barrier(t);
       MPE_STAMP(4);
-      rows(t);
+      rows(t, false);
       MPE_STAMP(5);   // this step's rows are on their way
     }
     if (SERVE) {
@@ -1317,6 +1522,25 @@ k_split(float *const g_pos, float *const g_vel, const float *const g_act, const 
     }
   }
   MPE_SPAN_END();
+}
+
+// The kernels: the fused step, rollout and step server (k_split), and the policy rollout (k_split_policy, which alone carries the
+// actors' arguments -- the other kernels' argument block is what it was before policy rollouts existed)
+template <int KIND, int A, int L, int NADV, bool ROLL, int RP, bool DUALP = false, bool SERVE = false>
+__global__ void __launch_bounds__((SplitShape<KIND, A, L, NADV>::waves(DUALP) * kWave))
+k_split(float *const g_pos, float *const g_vel, const float *const g_act, const int32_t *const g_ids, const size_t B,
+        const int g_wpw, const int g_observe_only, const unsigned g_movable, const NarrowDesc d, const MpeBuffers b_in,
+        const RollArgs ra, const ServeArgs sv) {
+  split_body<KIND, A, L, NADV, ROLL, RP, DUALP, SERVE, false>(g_pos, g_vel, g_act, g_ids, B, g_wpw, g_observe_only, g_movable, d, b_in,
+                                                              ra, sv, PolArgs{});
+}
+template <int KIND, int A, int L, int NADV>
+__global__ void __launch_bounds__((SplitShape<KIND, A, L, NADV>::waves(false) * kWave))
+k_split_policy(float *const g_pos, float *const g_vel, const float *const g_act, const int32_t *const g_ids, const size_t B,
+               const int g_wpw, const int g_observe_only, const unsigned g_movable, const NarrowDesc d, const MpeBuffers b_in,
+               const RollArgs ra, const PolArgs pol) {
+  split_body<KIND, A, L, NADV, true, kRowsNt, false, false, true>(g_pos, g_vel, g_act, g_ids, B, g_wpw, g_observe_only, g_movable, d,
+                                                                  b_in, ra, ServeArgs{}, pol);
 }
 
 // ---- dispatch -----------------------------------------------------------------------------------
@@ -1432,6 +1656,46 @@ int launch_split(bool roll, int kind, int A, int L, int nadv, const NarrowDesc &
   }
   hipLaunchKernelGGL(fn, dim3(grid), dim3(waves * kWave), roll ? e->lds_roll : e->lds_step, stream,
                      b.pos, b.vel, b.act, b.ids, B, (int)r2.wpw, (int)r2.observe_only, (unsigned)d.movable, d, b, r2, ServeArgs{});
+  return (int)hipGetLastError();
+}
+
+// ---- the policy rollout (mpe_rollout_policy) -------------------------------------------------------------------------------
+// Single-role only: step t + 1's World.step now depends on step t's rows through the actor, which is exactly the independence
+// the dual-role split lives on.  simple_spread stops at 3 agents: from 4 on the actor's accumulators next to the world state
+// exceed the register file and the kernel spills to scratch.
+using PolicyFn = void (*)(float *, float *, const float *, const int32_t *, const size_t, const int, const int, const unsigned,
+                         const NarrowDesc, const MpeBuffers, const RollArgs, const PolArgs);
+struct PolicyEntry {
+  int kind, A, L, nadv;
+  PolicyFn fn;
+  size_t lds;
+};
+#define MPE_POLICY_ENTRY(KIND, A, L, NADV) \
+  { KIND, A, L, NADV, k_split_policy<KIND, A, L, NADV>, SplitShape<KIND, A, L, NADV>::lds_bytes(true) }
+static const PolicyEntry kPolicyTable[] = {
+    MPE_POLICY_ENTRY(MPE_SCN_SIMPLE, 1, 1, 0),
+    MPE_POLICY_ENTRY(MPE_SCN_SPREAD, 1, 1, 0), MPE_POLICY_ENTRY(MPE_SCN_SPREAD, 2, 2, 0), MPE_POLICY_ENTRY(MPE_SCN_SPREAD, 3, 3, 0),
+    MPE_POLICY_ENTRY(MPE_SCN_ADVERSARY, 3, 2, 1), MPE_POLICY_ENTRY(MPE_SCN_PUSH, 2, 2, 1),
+};
+static const PolicyEntry *find_policy(int kind, int A, int L, int nadv) {
+  for (const PolicyEntry &e : kPolicyTable)
+    if (e.kind == kind && e.A == A && e.L == L && (kind < MPE_SCN_TAG || e.nadv == nadv)) return &e;
+  return nullptr;
+}
+bool split_policy_supports(int kind, int A, int L, int nadv) { return find_policy(kind, A, L, nadv) != nullptr; }
+int launch_split_policy(int kind, int A, int L, int nadv, const NarrowDesc &d, const MpeBuffers &b, size_t B, const RollArgs &ra,
+                        const PolArgs &pol, hipStream_t stream) {
+  const PolicyEntry *e = find_policy(kind, A, L, nadv);
+  if (!e) return MPE_EUNSUPPORTED;
+  RollArgs r2 = ra;
+  r2.wpw = kWave;
+  const unsigned grid = (unsigned)((B + kWave - 1) / kWave);
+  if (e->lds > 64 * 1024) {
+    const hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(e->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds);
+    if (rc != hipSuccess) return (int)rc;
+  }
+  hipLaunchKernelGGL(e->fn, dim3(grid), dim3((A + 1) * kWave), e->lds, stream, b.pos, b.vel, b.act, b.ids, B, (int)r2.wpw, 0,
+                     (unsigned)d.movable, d, b, r2, pol);
   return (int)hipGetLastError();
 }
 

@@ -783,3 +783,242 @@ def _rollout_actions(env, moves, episode_len, seed, comm, cache, key):
     env._scenario_state_stale = True
     env._fast_acts.clear()
     return [(traj.obs[t], traj.rew[t], traj.done[t]) for t in range(T)]
+
+
+# ---- policy rollouts: an MLP actor per agent evaluated inside the fused rollout (mpe_rollout_policy) ----------------------------
+_POLICY_MODES = {"greedy": _abi.MPE_POLICY_GREEDY, "sample": _abi.MPE_POLICY_SAMPLE, "softmax": _abi.MPE_POLICY_SOFTMAX}
+
+
+def _actor_layers(module):
+    """nn.Sequential (or a lone nn.Linear) -> ([Linear, ...], activation name); refuses anything the kernel does not evaluate."""
+    import torch.nn as nn
+    mods = [module] if isinstance(module, nn.Linear) else list(module.children()) if isinstance(module, nn.Sequential) else None
+    if mods is None:
+        raise _abi.MpeError("MlpPolicy: an actor is an nn.Sequential of Linear layers with ReLU / Tanh between them (got %s)"
+                            % type(module).__name__)
+    lins, acts = [], []
+    for k, m in enumerate(mods):
+        want_linear = k % 2 == 0
+        if want_linear and isinstance(m, nn.Linear):
+            lins.append(m)
+        elif not want_linear and isinstance(m, (nn.ReLU, nn.Tanh)):
+            acts.append(type(m).__name__.lower())
+        else:
+            raise _abi.MpeError("MlpPolicy: unsupported layer %d (%s): an actor alternates Linear and ReLU / Tanh and ends with a Linear"
+                                % (k, type(m).__name__))
+    if not lins or len(mods) % 2 == 0:
+        raise _abi.MpeError("MlpPolicy: an actor ends with a Linear layer")
+    if len(lins) > _abi.MPE_POLICY_MAX_LAYERS:
+        raise _abi.MpeError("MlpPolicy: %d Linear layers (at most %d)" % (len(lins), _abi.MPE_POLICY_MAX_LAYERS))
+    if len(set(acts)) > 1:
+        raise _abi.MpeError("MlpPolicy: one activation per actor (got %s)" % sorted(set(acts)))
+    for k, lin in enumerate(lins):
+        if lin.weight.dtype != torch.float32 or (lin.bias is not None and lin.bias.dtype != torch.float32):
+            raise _abi.MpeError("MlpPolicy: Linear layer %d is not float32" % k)
+        if k > 0 and lin.in_features != lins[k - 1].out_features:
+            raise _abi.MpeError("MlpPolicy: Linear layer %d takes %d inputs, layer %d gives %d"
+                                % (k, lin.in_features, k - 1, lins[k - 1].out_features))
+        if k + 1 < len(lins) and lin.out_features > _abi.MPE_POLICY_MAX_WIDTH:
+            raise _abi.MpeError("MlpPolicy: hidden width %d > %d" % (lin.out_features, _abi.MPE_POLICY_MAX_WIDTH))
+    if lins[-1].out_features != _abi.MPE_ACTION_DIM:
+        raise _abi.MpeError("MlpPolicy: the last Linear layer gives %d outputs (need %d)" % (lins[-1].out_features, _abi.MPE_ACTION_DIM))
+    return lins, (acts[0] if acts else "relu")
+
+
+def pack_actor(module):
+    """One actor in the packed layout of include/mpe_hip.h (MpePolicy): for each Linear layer l, W_l as [in_l][out_l'] (W_l[k][j] =
+    weight[j][k]) then bias[out_l'], with in_0 = the input width, in_l = 64 for l > 0, out_l' = 64 for a hidden layer and 8 for the
+    last, zero padding.  -> a float32 tensor on the module's device whose length is a multiple of 16."""
+    lins, _ = _actor_layers(module)
+    dev = lins[0].weight.device
+    parts = []
+    for k, lin in enumerate(lins):
+        n_in = lin.in_features if k == 0 else _abi.MPE_POLICY_MAX_WIDTH
+        n_out = 8 if k + 1 == len(lins) else _abi.MPE_POLICY_MAX_WIDTH
+        w = torch.zeros((n_in, n_out), dtype=torch.float32, device=dev)
+        w[:lin.in_features, :lin.out_features] = lin.weight.detach().t()
+        b = torch.zeros(n_out, dtype=torch.float32, device=dev)
+        if lin.bias is not None:
+            b[:lin.out_features] = lin.bias.detach()
+        parts += [w.reshape(-1), b]
+    flat = torch.cat(parts)
+    pad = (-flat.numel()) % 16
+    return torch.cat([flat, flat.new_zeros(pad)]) if pad else flat
+
+
+class MlpPolicy(object):
+    """Per-agent MLP actors for PolicyRollout: `modules` is one nn.Sequential per agent, or one module every agent shares
+    (MADDPG's actors: Linear layers with ReLU / Tanh between them, hidden widths <= 64, five logits, float32).  Agents handed the
+    SAME module object share one packed copy of its weights.  The weights are packed again at every PolicyRollout.run, so a
+    training step that updates the modules in place is what the next run uses."""
+
+    def __init__(self, modules):
+        import torch.nn as nn
+        self.shared = isinstance(modules, nn.Module)
+        self.modules = [modules] if self.shared else list(modules)
+        if not self.modules:
+            raise _abi.MpeError("MlpPolicy: no actor")
+        self._layers = [_actor_layers(m) for m in self.modules]
+
+    def actor(self, i):
+        return self.modules[0] if self.shared else self.modules[i]
+
+    def _check(self, obs_widths):
+        if not self.shared and len(self.modules) != len(obs_widths):
+            raise _abi.MpeError("MlpPolicy: %d actors for %d agents" % (len(self.modules), len(obs_widths)))
+        for i, D in enumerate(obs_widths):
+            lins, _ = self._layers[0 if self.shared else i]
+            if lins[0].in_features != D:
+                raise _abi.MpeError("MlpPolicy: agent %d's actor takes %d inputs, its observation has %d" % (i, lins[0].in_features, D))
+
+    def pack(self, obs_widths, device, mode, seed):
+        """-> (weights tensor on `device`, MpePolicy) for mpe_rollout_policy."""
+        self._layers = [_actor_layers(m) for m in self.modules]      # (a module may have been edited since)
+        self._check(obs_widths)
+        pol = _abi.MpePolicy()
+        blobs, where, off = [], {}, 0
+        for i in range(len(obs_widths)):
+            m = self.actor(i)
+            if id(m) not in where:
+                blob = pack_actor(m).to(device)
+                where[id(m)] = off
+                blobs.append(blob)
+                off += blob.numel()
+            lins, act = _actor_layers(m)
+            pol.n_layers[i] = len(lins)
+            pol.width[i][0] = lins[0].in_features
+            for k, lin in enumerate(lins):
+                pol.width[i][k + 1] = lin.out_features
+            pol.activation[i] = _abi.MPE_POLICY_TANH if act == "tanh" else _abi.MPE_POLICY_RELU
+            pol.offset[i] = where[id(m)]
+        w = torch.cat(blobs).contiguous()
+        pol.weights = w.data_ptr()
+        pol.mode = _POLICY_MODES[mode]
+        pol.seed = int(seed) & (2 ** 64 - 1)
+        return w, pol
+
+    def logits(self, i, obs):
+        with torch.no_grad():
+            return self.actor(i)(obs)
+
+    def action(self, obs_n, mode="greedy", generator=None):
+        """The reference-style per-agent loop (bin/interactive.py: act_n = [policy.action(obs_n[i])]): obs_n[i] [B, D_i] -> a list
+        of [B, 5] action rows by the rule of `mode` -- greedy: one-hot at argmax (lowest index on ties), softmax: the
+        probabilities, sample: one-hot at an inverse-CDF draw from torch.rand (not the rollout's Philox stream)."""
+        if mode not in _POLICY_MODES:
+            raise _abi.MpeError("mode: one of %s" % sorted(_POLICY_MODES))
+        rows = []
+        for i, o in enumerate(obs_n):
+            z = self.logits(i, o)
+            if mode == "softmax":
+                rows.append(torch.softmax(z, dim=-1))
+                continue
+            if mode == "greedy":
+                idx = torch.argmax(z, dim=-1)
+            else:
+                p = torch.softmax(z, dim=-1)
+                u = torch.rand(z.shape[:-1] + (1,), generator=generator, device=z.device, dtype=z.dtype)
+                idx = torch.clamp((torch.cumsum(p, dim=-1)[..., :4] <= u).sum(dim=-1), max=4)
+            rows.append(torch.nn.functional.one_hot(idx, _abi.MPE_ACTION_DIM).to(z.dtype))
+        return rows
+
+
+class PolicyTrajectory(Trajectory):
+    """Trajectory plus the decisions: act [T, A, B, 5] (the rows applied at each step), obs_in[t][i] [B, D_i] (the observation
+    each decision was taken on, with record_inputs) and logp [T, A, B] (log softmax(z)[chosen], sample mode)."""
+
+    def __init__(self, env, T, record_inputs=False, logp=False):
+        super(PolicyTrajectory, self).__init__(env, T)
+        w = env.world
+        A, B, dev, off = self.A, self.B, w.device, env._obs_off
+        self.act = torch.zeros((self.T, A, B, _abi.MPE_ACTION_DIM), dtype=torch.float32, device=dev)
+        self.obs_in_flat = self.obs_in = None
+        if record_inputs:
+            per = int(off[-1]) * B
+            self.obs_in_flat = torch.zeros(self.T * per, dtype=torch.float32, device=dev)
+            self.obs_in = [[self.obs_in_flat[t * per + off[i] * B: t * per + off[i + 1] * B].view(B, off[i + 1] - off[i])
+                            for i in range(A)] for t in range(self.T)]
+        self.logp = torch.zeros((self.T, A, B), dtype=torch.float32, device=dev) if logp else None
+
+
+class PolicyRollout(object):
+    """T steps of `policy` in the loop with the env as ONE launch (mpe_rollout_policy): at every step each agent's actor reads
+    its observation of the current state, its logits become an action row (mode: greedy / sample / softmax, include/mpe_hip.h),
+    and the env steps with those rows; every episode_len global steps the worlds restart first (world.reset_uniform's device
+    draws of `seed`).  Consecutive run() calls continue the same step count and episode clock; world.pos / vel hold the state
+    after the last step."""
+
+    def __init__(self, env, policy, mode="greedy", episode_len=25, seed=None, policy_seed=0):
+        if mode not in _POLICY_MODES:
+            raise _abi.MpeError("PolicyRollout: mode is one of %s (got %r)" % (sorted(_POLICY_MODES), mode))
+        if not isinstance(policy, MlpPolicy):
+            policy = MlpPolicy(policy)
+        if getattr(env, "_prog", None) is not None:
+            raise _abi.MpeError("PolicyRollout: row-program and traced envs are not served (their step is mpe_step_rows)")
+        _step_many_env_check(env)       # noise, callbacks, flags and max_episode_steps: what env.step would do differently
+        w = env.world
+        if len(w.agents) > _abi.MPE_POLICY_MAX_AGENTS:
+            raise _abi.MpeError("PolicyRollout: more than %d agents (no policy kernel for this shape)" % _abi.MPE_POLICY_MAX_AGENTS)
+        if any(not a.silent for a in w.agents):
+            raise _abi.MpeError("PolicyRollout: speaking agents are not served (the actor gives moves only)")
+        if int(episode_len) and not env._device_restart_ok:
+            raise _abi.MpeError("PolicyRollout(episode_len > 0): the in-launch resets are world.reset_uniform's device draws; "
+                                "this env's reset_world is not that")
+        env._ensure_buffers()
+        self.env, self.world, self.policy, self.mode = env, w, policy, mode
+        self.A, self.B = len(w.agents), w.batch_size
+        self.obs_widths = [int(env._obs_off[i + 1] - env._obs_off[i]) for i in range(self.A)]
+        policy._check(self.obs_widths)
+        self.episode_len = int(episode_len)
+        self.seed = int(w.seed if seed is None else seed) & (2 ** 64 - 1)
+        self.policy_seed = int(policy_seed) & (2 ** 64 - 1)
+        self._L = _abi.lib()
+        self._lr = float(getattr(env._scenario, "landmark_range", 1.0))
+        self._desc = _copy_struct(env._desc)
+        _, pol = policy.pack(self.obs_widths, w.device, mode, self.policy_seed)
+        if self._L.mpe_rollout_policy_supported(C.byref(self._desc), C.byref(pol), self.B) != 1:
+            raise _abi.MpeError("PolicyRollout: no policy kernel for this scenario shape (simple, simple_spread with up to 3 agents, "
+                                "simple_adversary with 3 agents, simple_push): %s"
+                                % self._L.mpe_last_error().decode("utf-8", "replace"))
+        self.t = 0
+
+    def run(self, T, trajectory=None, record_inputs=False):
+        """T steps -> a PolicyTrajectory (or `trajectory`, a PolicyTrajectory of at least T blocks, filled in place)."""
+        T = int(T)
+        env, w = self.env, self.world
+        _step_many_env_check(env)       # (re-reads constants assigned since the last step, as env.step does)
+        self._desc = _copy_struct(env._desc)
+        sample = self.mode == "sample"
+        if trajectory is None:
+            trajectory = PolicyTrajectory(env, T, record_inputs=record_inputs, logp=sample)
+        elif trajectory.T < T or (record_inputs and trajectory.obs_in_flat is None):
+            raise _abi.MpeError("trajectory: a PolicyTrajectory of at least %d blocks%s" % (T, " with record_inputs" if record_inputs else ""))
+        weights, pol = self.policy.pack(self.obs_widths, w.device, self.mode, self.policy_seed)
+        b = trajectory.bufs
+        b.act = b.ids = b.u = None
+        st = _abi.raw_stream(w.device)
+        done = 0
+        # launches bounded by their work (T * B * A agent-world-steps, MPE_POLICY_MAX_LAUNCH_WORK), not by their step count
+        per_launch = max(1, min(65535, _abi.MPE_POLICY_MAX_LAUNCH_WORK // (self.A * self.B)))
+        while done < T:
+            n = min(T - done, per_launch)
+            per, per_in = self.A * self.B, int(env._obs_off[-1]) * self.B
+            bb = _copy_struct(b)
+            bb.obs = b.obs + 4 * done * per_in
+            bb.rew = b.rew + 4 * done * per
+            bb.done = b.done + done * per
+            _abi.check(self._L.mpe_rollout_policy(
+                C.byref(self._desc), C.byref(bb), C.byref(pol), self.B, n, self.episode_len, self._lr, self.seed, self.t,
+                int(w.world_offset), 1, trajectory.act[done].data_ptr(),
+                None if (not record_inputs or trajectory.obs_in_flat is None) else trajectory.obs_in_flat.data_ptr() + 4 * done * per_in,
+                trajectory.logp[done].data_ptr() if (sample and trajectory.logp is not None) else None, st), "mpe_rollout_policy")
+            self.t += n
+            done += n
+        del weights      # (stream-ordered: the caching allocator reuses the block only behind the launch)
+        env._scenario_state_stale = True
+        env._fast_acts.clear()
+        for out in env._sets or ():
+            out.act_ptr = None
+        if env.episode_step is not None and self.episode_len:
+            env.episode_step.fill_(self.t % self.episode_len)
+        return trajectory
