@@ -576,12 +576,13 @@ __device__ __forceinline__ void store_state(const MpeBuffers &b, size_t B, int i
 // `door > g` -- rung (door += n) by mpe_step_server_ring, a one-thread launch ordered on the CALLER's stream behind whatever produced
 // that step's moves -- reads its one-hot moves from tensor g % ring of the caller's move ring with system-scope loads
 // (another kernel wrote them while this one runs: no cache of ours may serve them), writes that step's rows / rewards /
-// dones / state WRITE-THROUGH (sc1: visible to other kernels when acknowledged, not at kernel end) into output block
-// g % slots, and publishes per workgroup `flag[wg] = g + 1` once every wave's stores of step g are acknowledged.  State
-// stays in registers between steps and episodes restart inside the launch (the rollout's in-kernel reset), so a launch
-// serves up to T steps; a wave that waits longer than `timeout_ticks` of the 100 MHz wall clock for its next command sets
-// `status` and leaves (a server never outlives its commander).  Same device functions in the same order as the per-step
-// kernel: bit-identical to T x {mpe_reset at the boundaries; mpe_step} (tests/test_gpu_server.py).
+// dones WRITE-THROUGH (sc1: visible to other kernels when acknowledged, not at kernel end) into output block g % slots,
+// and its state likewise into world.pos / vel when the state is AT REST (next_commanded, below), and publishes per
+// workgroup `flag[wg] = g + 1` once every wave's stores of step g are acknowledged.  State stays in registers between
+// steps and episodes restart inside the launch (the rollout's in-kernel reset), so a launch serves up to T steps; a wave
+// that waits longer than `timeout_ticks` of the 100 MHz wall clock for its next command sets `status` and leaves (a server
+// never outlives its commander).  Same device functions in the same order as the per-step kernel: bit-identical to
+// T x {mpe_reset at the boundaries; mpe_step} (tests/test_gpu_server.py, tests/test_gpu_server_stream.py).
 //
 // Completion without a second barrier: the stores of step g are known acknowledged where the wave next waits for memory
 // anyway -- `s_waitcnt vmcnt(0)` in front of step g+1's barrier, behind which the reward wave publishes g+1.  A server that
@@ -731,6 +732,14 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
         return false;
       }
     }
+  };
+  // next_commanded: step t + 1 of this launch is already commanded (`seen` only grows: a stale look only costs a store), so this
+  // wave runs it and step t's state is overwritten before anybody can read it race-free -- a commander that reads the state
+  // after wait(g) has not rung g + 1 yet.  The state goes to HBM only at rest: at the launch's last step, in front of an idle
+  // wait (the commander's next step is not rung) and so in front of a timeout.
+  auto next_commanded = [&](const int t) -> bool {
+    if constexpr (!SERVE) return false;
+    return t + 1 < T && seen > ra.step0 + (unsigned long long)t + 1;
   };
   // behind a barrier: did some wave of this workgroup give up?  (then this one leaves before any further store)
   auto aborted = [&]() -> bool {
@@ -1000,8 +1009,8 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
     // arrival at this barrier -- so no wave can observe a post-step position in World.step, whatever
     // the dispatch order or timing of the waves (core.py:117-131: forces from the pre-step positions).
 #ifndef MPE_STRESS_STORE_BEFORE_BARRIER
-    if (movable_i && step_world && live && (!ROLL || SERVE || t == T - 1) && !(MPE_SPLIT_ABLATE & 8))
-      store_state<AUX>(b, B, i, w0, ln, mx, my, mvx, mvy);   // (a served step leaves its state in HBM like a launched one)
+    if (movable_i && step_world && live && (!ROLL || (SERVE ? !next_commanded(t) : t == T - 1)) && !(MPE_SPLIT_ABLATE & 8))
+      store_state<AUX>(b, B, i, w0, ln, mx, my, mvx, mvy);   // (a served step at rest leaves its state in HBM like a launched one)
 #endif
     if constexpr (SERVE) {
       if (did_reset && live) {   // what mpe_reset would have left in HBM in front of this step: landmarks, picks, an immovable agent

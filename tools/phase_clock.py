@@ -2,7 +2,10 @@
 """Where the cycles of one step go: run the MPE_PHASE_CLOCK build of k_split (tools/ab_build.sh clk split
 -DMPE_PHASE_CLOCK) and print, per role, the mean shader-clock delta between the phase stamps of a step.
 
-    MPE_HIP_LIB=.../libmpe_hip_ab_clk.so python tools/phase_clock.py simple_tag 16384 [roll|step]
+    MPE_HIP_LIB=.../libmpe_hip_ab_clk.so python tools/phase_clock.py simple_tag 16384 [roll|step|serve]
+
+serve: the step server's launch of T = 25 steps, every command issued before it (tools/server_profile.py's protocol); at
+65536 worlds it is the single-role server, at up to 1.5 workgroups per CU the dual-role one (agent stamps: its physics waves)
 
 agent wave stamps  0 step start | 1 World.step done | 2 published, at the barrier | 3 through the barrier |
                    4 siblings' positions read | 5 rows on their way
@@ -17,7 +20,31 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import multiagent_particle_envs_amd as mpe  # noqa: E402
-from multiagent_particle_envs_amd.rollout import RandomRollout, Trajectory  # noqa: E402
+from multiagent_particle_envs_amd import _abi  # noqa: E402
+from multiagent_particle_envs_amd.rollout import RandomRollout, StepServer, Trajectory  # noqa: E402
+
+
+def served(env, T, dbg, reps=3):
+    """reps server launches of T commanded steps (commands first), stamping into dbg; -> the last launch's duration (ms)"""
+    A, B = len(env.world.agents), env.world.batch_size
+    moves = torch.empty((T, A, B, _abi.MPE_ACTION_DIM), dtype=torch.float32, device="cuda")
+    L = _abi.lib()
+    srv = StepServer(env, moves, slots=2, episode_len=25, timeout_s=3.0, probe=False)
+    srv.blocks.bufs.force = dbg.data_ptr()
+    for k in range(reps):
+        _abi.check(L.mpe_random_actions_block(moves.data_ptr(), None, A, B, 0, k * T, T, 0, _abi.raw_stream(env.world.device)), "draw")
+        dbg.zero_()
+        torch.cuda.synchronize()
+        srv.served_to += T          # (commands first: ring() checks them against the launches started so far)
+        srv.ring(T)
+        srv.served_to -= T
+        torch.cuda.synchronize()
+        srv.launch_events = []
+        srv.start(T)
+        srv.join()
+        torch.cuda.synchronize()
+        srv.check()
+    return srv.launch_events[0][0].elapsed_time(srv.launch_events[0][1])
 
 
 def main():
@@ -32,7 +59,7 @@ def main():
     for bufs in [s.bufs for s in env._sets] + [traj.bufs]:
         bufs.force = dbg.data_ptr()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for rep in range(3):
+    for rep in range(0 if mode == "serve" else 3):
         dbg.zero_()
         torch.cuda.synchronize()
         e0.record()
@@ -42,9 +69,9 @@ def main():
             rr.enqueue(1)
         e1.record()
         torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1)
+    ms = served(env, T, dbg) if mode == "serve" else e0.elapsed_time(e1)
     d = dbg.cpu().numpy().reshape(4, 16, 32, 8).astype(np.int64)
-    nt = T if mode == "roll" else 1
+    nt = T if mode in ("roll", "serve") else 1
     print("%s B=%d %s: launch %.2f us by events (%d steps)" % (scn, B, mode, ms * 1e3, nt))
     t_first = d[:, :, 0, 0][d[:, :, 0, 0] > 0].min()
     t_last = d[:, :, :nt, :].max()
