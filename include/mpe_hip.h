@@ -339,6 +339,52 @@ int mpe_rollout_policy(const MpeScenarioDesc *desc, const MpeBuffers *bufs, cons
                        int32_t episode_len, float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset,
                        int32_t trajectory, float *act_out, float *obs_in_out, float *logp_out, void *stream);
 
+/* ---- the standalone actor kernel: every agent's MLP actor for all B worlds in ONE launch (csrc/mpe_policy.hip) ----------------
+ * The policy half of the reference's loop (act_n = [policy.action(obs_n[i])]; env.step(act_n)) for ANY env: the launch reads one
+ * contiguous float32 [B][D_i] block per agent (obs_ptrs[i]: the env's own observation rows qualify, and so does any tensor of
+ * that layout) and writes the rows mpe_step takes -- moves [A][B][5] and, where agents speak, utterances [A][B][dim_c].  The
+ * layers run on f32-input MFMA (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain, accumulators start at the bias), weights
+ * staged in LDS; arithmetic order, Tanh, softmax and the head rule are those of mpe_rollout_policy above.
+ * Heads: agent i's last Linear layer gives n_out = 5 * movable + dim_c * speaks logits (1 <= n_out <= MPE_ACTOR_MAX_OUT).  A
+ * movable agent's FIRST 5 logits are its move head, a speaking agent's LAST dim_c logits its utterance head; each head gets
+ * `mode`'s rule on its own logits.  SAMPLE draws: the move head uses mpe_rollout_policy's draw exactly (stream
+ * MPE_STREAM_POLICY), the utterance head the same counter layout on MPE_STREAM_POLICY_COMM.  An immovable agent's move row and a
+ * silent agent's utterance row are zeros.
+ * PACKED layout of one actor, at weights + offset[i] (floats, offset a multiple of 16): for each layer l, W_l as
+ * [in_l][out_l'] row-major (W_l[k][j] = Linear.weight[j][k]) followed by bias[out_l'], where in_0 = the input width D_i,
+ * in_l = 64 for l > 0, out_l' = 64 for a hidden layer and 16 for the last; every padding entry is zero.  Agents may share one
+ * packed actor (equal offsets).  (MpePolicy's layout with a 16-wide last layer.)                                             */
+#define MPE_ACTOR_MAX_AGENTS 16
+#define MPE_ACTOR_MAX_OUT 16
+#define MPE_ACTOR_MAX_INPUT 256                 /* widest input row D_i (streamed through the k loop 32 columns at a time)  */
+#define MPE_STREAM_POLICY 0x504F4C49u           /* "POLI": the move head's SAMPLE draws (mpe_rollout_policy's stream)       */
+#define MPE_STREAM_POLICY_COMM 0x504F4C43u      /* "POLC": the utterance head's SAMPLE draws                                */
+typedef struct MpeActorSet {
+  int32_t n_agents;                               /* 1..MPE_ACTOR_MAX_AGENTS                                               */
+  int32_t mode;                                   /* MPE_POLICY_GREEDY / SAMPLE / SOFTMAX                                  */
+  uint64_t seed;                                  /* key of the SAMPLE draws                                               */
+  const float *weights;                           /* device memory, the packed actors                                      */
+  int64_t offset[MPE_ACTOR_MAX_AGENTS];           /* floats from `weights` to agent i's packed actor                       */
+  int32_t n_layers[MPE_ACTOR_MAX_AGENTS];         /* Linear layers of agent i's actor, 1..MPE_POLICY_MAX_LAYERS            */
+  int32_t width[MPE_ACTOR_MAX_AGENTS][4];         /* width[i][0] = D_i, width[i][l + 1] = output of layer l                */
+  int32_t activation[MPE_ACTOR_MAX_AGENTS];       /* MPE_POLICY_RELU / TANH (between the layers)                           */
+  uint8_t movable[MPE_ACTOR_MAX_AGENTS];          /* agent i has a move head (its first 5 logits)                          */
+  uint8_t speaks[MPE_ACTOR_MAX_AGENTS];           /* agent i has an utterance head (its last dim_c logits)                 */
+  int32_t dim_c;                                  /* utterance width, 0 if nobody speaks                                   */
+  int32_t reserved_;
+} MpeActorSet;
+size_t mpe_sizeof_actor_set(void);
+/* 1 if the set can be evaluated for B worlds, 0 if it is valid but out of scope (more than MPE_ACTOR_MAX_AGENTS agents, an input
+ * wider than MPE_ACTOR_MAX_INPUT, a hidden layer wider than MPE_POLICY_MAX_WIDTH: named in mpe_last_error), < 0 if invalid.  */
+int mpe_actor_supported(const MpeActorSet *set, int64_t B);
+/* obs_ptrs: HOST array of n_agents device pointers, agent i's [B][D_i] rows.  step, world_offset: the SAMPLE draws' global step
+ * and first world.  moves [A][B][5] (required).  Optional (NULL = not written): utter [A][B][dim_c]; ids int32 [2][A][B] -- the
+ * chosen index of the move head, then of the utterance head (argmax in SOFTMAX mode, -1 where the agent has no such head);
+ * logp [A][B] -- the sum over the agent's heads of log softmax(z)[chosen]; logits [A][B][MPE_ACTOR_MAX_OUT] -- the raw
+ * outputs of the last layer, zero beyond n_out.                                                                             */
+int mpe_actor_act(const MpeActorSet *set, const float *const *obs_ptrs, int64_t B, uint64_t step, int64_t world_offset,
+                  float *moves, float *utter, int32_t *ids, float *logp, float *logits, void *stream);
+
 /* ---- composable output stage: a USER scenario's observation / reward as a row program ---------------------------------
  * The reference's plug-in promise (README "Creating new environments", scenario.py:4-10) is that new scenarios are the
  * normal use; every shipped observation is a concatenation of a few segment kinds and every shipped reward an ordered

@@ -69,6 +69,18 @@ class MpePolicy(C.Structure):          # include/mpe_hip.h: per-agent MLP actors
                 ("weights", C.c_void_p), ("mode", C.c_int32), ("reserved_", C.c_int32), ("seed", C.c_uint64)]
 
 
+MPE_ACTOR_MAX_AGENTS, MPE_ACTOR_MAX_OUT, MPE_ACTOR_MAX_INPUT = 16, 16, 256
+MPE_STREAM_POLICY, MPE_STREAM_POLICY_COMM = 0x504F4C49, 0x504F4C43
+
+
+class MpeActorSet(C.Structure):        # include/mpe_hip.h: the actors of one mpe_actor_act launch
+    _fields_ = [("n_agents", C.c_int32), ("mode", C.c_int32), ("seed", C.c_uint64), ("weights", C.c_void_p),
+                ("offset", C.c_int64 * MPE_ACTOR_MAX_AGENTS), ("n_layers", C.c_int32 * MPE_ACTOR_MAX_AGENTS),
+                ("width", (C.c_int32 * 4) * MPE_ACTOR_MAX_AGENTS), ("activation", C.c_int32 * MPE_ACTOR_MAX_AGENTS),
+                ("movable", C.c_uint8 * MPE_ACTOR_MAX_AGENTS), ("speaks", C.c_uint8 * MPE_ACTOR_MAX_AGENTS),
+                ("dim_c", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class MpeBuffers(C.Structure):
     _fields_ = [
         ("pos", C.c_void_p), ("vel", C.c_void_p), ("act", C.c_void_p), ("ids", C.c_void_p), ("u", C.c_void_p),
@@ -159,6 +171,10 @@ EXPORTS = {
     "mpe_rollout_policy": (C.c_int, [C.POINTER(MpeScenarioDesc), C.POINTER(MpeBuffers), C.POINTER(MpePolicy), C.c_int64, C.c_int32,
                                      C.c_int32, C.c_float, C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    "mpe_sizeof_actor_set": (C.c_size_t, []),
+    "mpe_actor_supported": (C.c_int, [C.POINTER(MpeActorSet), C.c_int64]),
+    "mpe_actor_act": (C.c_int, [C.POINTER(MpeActorSet), C.POINTER(C.c_void_p), C.c_int64, C.c_uint64, C.c_int64, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -188,7 +204,8 @@ def lib():
         raise MpeError("ABI version mismatch: library %d, binding %d" % (handle.mpe_abi_version(), MPE_ABI_VERSION))
     if handle.mpe_sizeof_desc() != C.sizeof(MpeScenarioDesc) or handle.mpe_sizeof_buffers() != C.sizeof(MpeBuffers) or \
             handle.mpe_sizeof_row_program() != C.sizeof(MpeRowProgram) or handle.mpe_sizeof_step_server() != C.sizeof(MpeStepServer) or \
-            handle.mpe_sizeof_render_args() != C.sizeof(MpeRenderArgs) or handle.mpe_sizeof_policy() != C.sizeof(MpePolicy):
+            handle.mpe_sizeof_render_args() != C.sizeof(MpeRenderArgs) or handle.mpe_sizeof_policy() != C.sizeof(MpePolicy) or \
+            handle.mpe_sizeof_actor_set() != C.sizeof(MpeActorSet):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")
     _lib = handle
     return _lib

@@ -1195,4 +1195,89 @@ int mpe_render(const MpeScenarioDesc *d, const MpeRenderArgs *a, void *stream) {
   return 0;
 }
 
+// ---- the standalone actor kernel (mpe_policy.hip) ---------------------------------------------------------------------------
+size_t mpe_sizeof_actor_set(void) { return sizeof(MpeActorSet); }
+static int check_actor_set(const MpeActorSet *s, const char *what) {
+  if (!s) return fail(MPE_EINVAL, "%s: set is NULL", what);
+  if (s->n_agents < 1) return fail(MPE_EINVAL, "%s: n_agents = %d (need at least 1)", what, s->n_agents);
+  if (s->n_agents > MPE_ACTOR_MAX_AGENTS)
+    return fail(MPE_EUNSUPPORTED, "%s: %d agents in one actor set (at most MPE_ACTOR_MAX_AGENTS = %d: split the agents over "
+                "several sets)", what, s->n_agents, MPE_ACTOR_MAX_AGENTS);
+  if (s->mode != MPE_POLICY_GREEDY && s->mode != MPE_POLICY_SAMPLE && s->mode != MPE_POLICY_SOFTMAX)
+    return fail(MPE_EINVAL, "%s: mode %d (MPE_POLICY_GREEDY / SAMPLE / SOFTMAX)", what, s->mode);
+  if (s->dim_c < 0 || s->dim_c > MPE_ACTOR_MAX_OUT) return fail(MPE_EINVAL, "%s: dim_c = %d (0..%d)", what, s->dim_c, MPE_ACTOR_MAX_OUT);
+  for (int i = 0; i < s->n_agents; ++i) {
+    const int nl = s->n_layers[i];
+    if (nl < 1 || nl > MPE_POLICY_MAX_LAYERS)
+      return fail(MPE_EINVAL, "%s: agent %d has %d Linear layers (1..%d)", what, i, nl, MPE_POLICY_MAX_LAYERS);
+    if (s->activation[i] != MPE_POLICY_RELU && s->activation[i] != MPE_POLICY_TANH)
+      return fail(MPE_EINVAL, "%s: agent %d: activation %d (MPE_POLICY_RELU / TANH)", what, i, s->activation[i]);
+    if (s->width[i][0] < 1) return fail(MPE_EINVAL, "%s: agent %d: input width %d", what, i, s->width[i][0]);
+    if (s->width[i][0] > MPE_ACTOR_MAX_INPUT)
+      return fail(MPE_EUNSUPPORTED, "%s: agent %d: input width %d > MPE_ACTOR_MAX_INPUT = %d", what, i, s->width[i][0],
+                  MPE_ACTOR_MAX_INPUT);
+    for (int l = 1; l < nl; ++l) {
+      if (s->width[i][l] < 1) return fail(MPE_EINVAL, "%s: agent %d: hidden width %d", what, i, s->width[i][l]);
+      if (s->width[i][l] > MPE_POLICY_MAX_WIDTH)
+        return fail(MPE_EUNSUPPORTED, "%s: agent %d: hidden width %d > MPE_POLICY_MAX_WIDTH = %d", what, i, s->width[i][l],
+                    MPE_POLICY_MAX_WIDTH);
+    }
+    const int mv = s->movable[i] ? 1 : 0, sp = s->speaks[i] ? 1 : 0;
+    const int n_out = MPE_ACTION_DIM * mv + s->dim_c * sp;
+    if (n_out < 1) return fail(MPE_EINVAL, "%s: agent %d neither moves nor speaks: it has no head", what, i);
+    if (n_out > MPE_ACTOR_MAX_OUT)
+      return fail(MPE_EUNSUPPORTED, "%s: agent %d: %d logits (5 * movable + dim_c * speaks) > MPE_ACTOR_MAX_OUT = %d", what, i, n_out,
+                  MPE_ACTOR_MAX_OUT);
+    if (s->width[i][nl] != n_out)
+      return fail(MPE_EINVAL, "%s: agent %d: the last layer gives %d outputs, its heads need %d (5 * movable + dim_c * speaks)", what,
+                  i, s->width[i][nl], n_out);
+    if (s->offset[i] < 0 || s->offset[i] % 16 || s->offset[i] > 0x7fffffff)
+      return fail(MPE_EINVAL, "%s: agent %d: offset %lld (a non-negative multiple of 16 floats below 2^31)", what, i,
+                  (long long)s->offset[i]);
+  }
+  return 0;
+}
+int mpe_actor_supported(const MpeActorSet *s, int64_t B) {
+  const int rc = check_actor_set(s, "mpe_actor_supported");
+  if (rc) return rc == MPE_EUNSUPPORTED ? 0 : rc;
+  return B > 0 ? 1 : 0;
+}
+int mpe_actor_act(const MpeActorSet *s, const float *const *obs_ptrs, int64_t B, uint64_t step, int64_t world_offset, float *moves,
+                  float *utter, int32_t *ids, float *logp, float *logits, void *stream) {
+  const char *what = "mpe_actor_act";
+  if (int rc = check_actor_set(s, what)) return rc;
+  if (B < 0) return fail(MPE_EINVAL, "%s: B = %lld", what, (long long)B);
+  if (!s->weights || ((uintptr_t)s->weights & 15)) return fail(MPE_EINVAL, "%s: set->weights is NULL or not 16-byte aligned", what);
+  if (!obs_ptrs) return fail(MPE_EINVAL, "%s: obs_ptrs is NULL", what);
+  if (!moves) return fail(MPE_EINVAL, "%s: moves is NULL", what);
+  if (logits && ((uintptr_t)logits & 15)) return fail(MPE_EINVAL, "%s: logits is not 16-byte aligned", what);
+  mpe::ActorArgs a;
+  std::memset(&a, 0, sizeof(a));
+  for (int i = 0; i < s->n_agents; ++i) {
+    if (!obs_ptrs[i]) return fail(MPE_EINVAL, "%s: obs_ptrs[%d] is NULL", what, i);
+    a.obs[i] = obs_ptrs[i];
+    a.off[i] = (int32_t)s->offset[i];
+    for (int l = 0; l < 4; ++l) a.width[i][l] = (int16_t)(l <= s->n_layers[i] ? s->width[i][l] : 0);
+    a.nl[i] = (uint8_t)s->n_layers[i];
+    a.act[i] = (uint8_t)s->activation[i];
+    a.movable[i] = s->movable[i] ? 1 : 0;
+    a.speaks[i] = s->speaks[i] ? 1 : 0;
+  }
+  a.w = s->weights;
+  a.moves = moves;
+  a.utter = utter;
+  a.ids = ids;
+  a.logp = logp;
+  a.logits = logits;
+  a.seed = s->seed;
+  a.step = step;
+  a.world_offset = (uint64_t)world_offset;
+  a.B = (uint64_t)B;
+  a.n_agents = s->n_agents;
+  a.mode = s->mode;
+  a.dim_c = s->dim_c;
+  if (B == 0) return 0;
+  return hip_result(mpe::launch_actor(a, static_cast<hipStream_t>(stream)), what);
+}
+
 }  // extern "C"

@@ -363,6 +363,73 @@ __host__ __device__ inline uint32_t policy_bits(uint64_t seed, uint64_t b, uint6
   return (i & 3) == 0 ? o.x : (i & 3) == 1 ? o.y : (i & 3) == 2 ? o.z : o.w;
 }
 
+// The utterance head of the standalone actor kernel (mpe_actor_act) draws on a stream of its own, same counter layout.
+constexpr uint32_t kStreamPolicyComm = MPE_STREAM_POLICY_COMM;
+static_assert(kStreamPolicy == MPE_STREAM_POLICY, "include/mpe_hip.h names the policy stream");
+__host__ __device__ inline uint32_t policy_comm_bits(uint64_t seed, uint64_t b, uint64_t t, int i) {
+  U4 c;
+  c.x = (uint32_t)b;
+  c.y = (uint32_t)(b >> 32) ^ (uint32_t)(t >> 32);
+  c.z = (uint32_t)(i >> 2);
+  c.w = kStreamPolicyComm ^ (uint32_t)t;
+  const U4 o = philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return (i & 3) == 0 ? o.x : (i & 3) == 1 ? o.y : (i & 3) == 2 ? o.z : o.w;
+}
+
+// ---- actors: the activation and the head rule, shared by k_split<POL> and mpe_policy.hip ----------------
+// Tanh is 1 - 2 / (exp(2x) + 1) on v_exp_f32 (absolute error < 2e-7).
+__device__ __forceinline__ float pol_act(float x, bool tnh) {
+  if (tnh) return 1.f - __fdividef(2.f, __builtin_amdgcn_exp2f(x * 2.88539008177792681f) + 1.f);
+  return fmaxf(x, 0.f);
+}
+// One head of n <= N logits (mode: MPE_POLICY_*; bits: the head's 32 Philox bits, read in SAMPLE mode only) -> its row r[0..n),
+// the chosen index (argmax in SOFTMAX mode) and log softmax(z)[chosen].  argmax ties go to the lowest index (np.argmax); softmax
+// in fp32 is e_j = exp(z_j - max z), s = ((e_0 + e_1) + ...) + e_{n-1}, p_j = e_j / s; SAMPLE picks the first j <= n - 2 with
+// u < c_j, c_0 = p_0, c_j = c_{j-1} + p_j (fp32, in that order), else n - 1, with u = (bits >> 8) * 2^-24.
+template <int N>
+__device__ __forceinline__ int pol_head(const float (&z)[N], int n, int mode, uint32_t bits, float (&r)[N], float &logp) {
+  float zm = z[0];
+  int am = 0;
+#pragma unroll
+  for (int j = 1; j < N; ++j)
+    if (j < n && z[j] > zm) { zm = z[j]; am = j; }
+  float e[N], sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < N; ++j)
+    if (j < n) {
+      e[j] = __expf(z[j] - zm);
+      sum += e[j];
+    } else {
+      e[j] = 0.f;
+    }
+  int m = am;
+  if (mode == MPE_POLICY_SOFTMAX) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) r[j] = e[j] / sum;
+  } else {
+    if (mode == MPE_POLICY_SAMPLE) {
+      const float u = (float)(bits >> 8) * (1.0f / 16777216.0f);
+      float c = 0.f, cj[N];
+      m = n - 1;
+#pragma unroll
+      for (int j = 0; j < N - 1; ++j) {
+        c += e[j] / sum;
+        cj[j] = c;
+      }
+#pragma unroll
+      for (int j = N - 2; j >= 0; --j)   // (descending: the last hit is the first j with u < c_j)
+        if (j < n - 1 && u < cj[j]) m = j;
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) r[j] = j == m ? 1.f : 0.f;
+  }
+  uint32_t zsel = 0u;      // z[m], as an OR of masked words: a select between two elements becomes an indexed load of a private array
+#pragma unroll
+  for (int j = 0; j < N; ++j) zsel |= m == j ? __float_as_uint(z[j]) : 0u;
+  logp = (__uint_as_float(zsel) - zm) - __logf(sum);
+  return m;
+}
+
 // ---- wave-private LDS transpose: 64 per-lane rows of D floats -> one contiguous 64*D-float run ----
 // The drop-in obs layout is row-major [B][D] per agent (72-byte rows at D=18): a thread-per-world
 // store would be stride-D scattered.  Each wave parks its 64 rows in its own LDS tile and streams

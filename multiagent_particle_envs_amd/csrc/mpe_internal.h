@@ -97,6 +97,21 @@ bool split_policy_supports(int kind, int A, int L, int nadv);
 int launch_split_policy(int kind, int A, int L, int nadv, const NarrowDesc &d, const MpeBuffers &b, size_t B, const RollArgs &ra,
                         const PolArgs &pol, hipStream_t stream);
 
+// the standalone actor kernel (mpe_policy.hip): one launch of every agent's actor (mpe_actor_act; checked by the caller)
+struct ActorArgs {
+  const float *obs[MPE_ACTOR_MAX_AGENTS];      // agent i's [B][D_i] input rows
+  const float *w;                              // packed actors (MpeActorSet's layout)
+  float *moves, *utter, *logp, *logits;        // [A][B][5]; [A][B][dim_c], [A][B], [A][B][16] or nullptr
+  int32_t *ids;                                // [2][A][B] or nullptr
+  uint64_t seed, step, world_offset;
+  uint64_t B;
+  int32_t n_agents, mode, dim_c;
+  int32_t off[MPE_ACTOR_MAX_AGENTS];           // float offset of agent i's packed actor
+  int16_t width[MPE_ACTOR_MAX_AGENTS][4];      // input width, then each layer's output width
+  uint8_t nl[MPE_ACTOR_MAX_AGENTS], act[MPE_ACTOR_MAX_AGENTS], movable[MPE_ACTOR_MAX_AGENTS], speaks[MPE_ACTOR_MAX_AGENTS];
+};
+int launch_actor(const ActorArgs &a, hipStream_t stream);
+
 // the composable output stage (mpe_rows.hip): kernel-side header of an MpeRowProgram
 constexpr int kRowSlots = 8;
 constexpr int kRowPicks = MPE_MAX_CHOICES;

@@ -478,10 +478,7 @@ __device__ __forceinline__ void reward_wave(const NarrowDesc &d, const float *co
 // outgoing weights are zero).  Tanh is 1 - 2 / (exp(2x) + 1) on v_exp_f32 (absolute error < 2e-7).
 typedef float vf2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(4))) const vf2 cvf2;
-__device__ __forceinline__ float pol_act(float x, bool tnh) {
-  if (tnh) return 1.f - __fdividef(2.f, __builtin_amdgcn_exp2f(x * 2.88539008177792681f) + 1.f);
-  return fmaxf(x, 0.f);
-}
+// (pol_act -- the activation -- is in mpe_device.h: the standalone actor kernel, mpe_policy.hip, evaluates the same formula)
 __device__ __forceinline__ vf2 pol_act2(vf2 x, bool tnh) { return vf2{pol_act(x.x, tnh), pol_act(x.y, tnh)}; }
 // layer 0: NO2 unit pairs from the D inputs of this lane's tile row (element k at row[4 * ((k >> 2) ^ sw) + (k & 3)]: the
 // tile's own layout, swizzled or not); with `rec`, the inputs are also stored as this lane's decision observation

@@ -1,0 +1,359 @@
+"""Policies in the loop for every env: `Actors` evaluates one MLP actor per agent for all B worlds in ONE launch of the standalone
+MFMA actor kernel (mpe_actor_act, csrc/mpe_policy.hip) and hands back exactly the rows `env.step` takes; `PolicyLoop` drives
+`act -> env.step` with device-side episode resets, eagerly or as one HIP graph.  DESIGN.md 2.10.
+
+    pi = Actors(env, modules, mode="sample", seed=0)
+    action = pi.act(obs_n, t)
+    obs_n, rew_n, done_n, _ = env.step(action)
+"""
+import ctypes as C
+
+import torch
+
+from . import _abi
+from .rollout import _POLICY_MODES, _actor_layers, _copy_struct, _step_many_env_check
+
+_W, _LW = _abi.MPE_POLICY_MAX_WIDTH, _abi.MPE_ACTOR_MAX_OUT
+
+
+def pack_actor16(module, n_out):
+    """One actor in the packed layout of include/mpe_hip.h (MpeActorSet): for each Linear layer l, W_l as [in_l][out_l'] (W_l[k][j] =
+    weight[j][k]) then bias[out_l'], with in_0 = the input width, in_l = 64 for l > 0, out_l' = 64 for a hidden layer and 16 for the
+    last, zero padding.  -> a float32 tensor on the module's device whose length is a multiple of 16."""
+    lins, _ = _actor_layers(module, n_out, "Actors")
+    dev = lins[0].weight.device
+    parts = []
+    for k, lin in enumerate(lins):
+        n_in = lin.in_features if k == 0 else _W
+        wide = _LW if k + 1 == len(lins) else _W
+        w = torch.zeros((n_in, wide), dtype=torch.float32, device=dev)
+        w[:lin.in_features, :lin.out_features] = lin.weight.detach().t()
+        b = torch.zeros(wide, dtype=torch.float32, device=dev)
+        if lin.bias is not None:
+            b[:lin.out_features] = lin.bias.detach()
+        parts += [w.reshape(-1), b]
+    return torch.cat(parts)
+
+
+class Actors(object):
+    """Per-agent MLP actors for any env: `modules` is one nn.Sequential per agent, or one module every agent shares (Linear layers
+    with ReLU / Tanh between them, at most 3 Linear layers, hidden widths <= 64, float32).  Agent i's first Linear takes its
+    observation width D_i; its last gives 5 * movable + dim_c * speaks logits: a movable agent's first 5 are its move head, a
+    speaking agent's last dim_c its utterance head, and each head gets `mode`'s rule (greedy / softmax / sample).
+    logp / ids / logits = True: the same launch also fills pi.logp [A,B] (sum over the heads of log p[chosen]), pi.ids [2,A,B]
+    int32 (move head, utterance head; -1 where an agent has no such head) and pi.logits [A,B,16] (raw last-layer outputs).
+    The weights are packed again at every act() unless freeze() was called, so in-place optimiser updates are seen; agents
+    handed the SAME module object share one packed copy."""
+
+    def __init__(self, env, modules, mode="sample", seed=0, logp=False, ids=False, logits=False):
+        import torch.nn as nn
+        if mode not in _POLICY_MODES:
+            raise _abi.MpeError("Actors: mode is one of %s (got %r)" % (sorted(_POLICY_MODES), mode))
+        w = env.world
+        self.env, self.world, self.mode = env, w, mode
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.A, self.B = len(w.agents), w.batch_size
+        if self.A > _abi.MPE_ACTOR_MAX_AGENTS:
+            raise _abi.MpeError("Actors: %d agents (at most MPE_ACTOR_MAX_AGENTS = %d per set)" % (self.A, _abi.MPE_ACTOR_MAX_AGENTS))
+        off = getattr(env, "_obs_off", None)
+        if off is None:
+            raise _abi.MpeError("Actors: this env has no device-side observation layout (env.fused is False)")
+        self.obs_widths = [int(off[i + 1] - off[i]) for i in range(self.A)]
+        self.movable = [bool(a.movable) for a in w.agents]
+        self.speaks = [not a.silent for a in w.agents]
+        self.dim_c = int(w.dim_c) if any(self.speaks) else 0
+        self.n_out = [_abi.MPE_ACTION_DIM * m + self.dim_c * s for m, s in zip(self.movable, self.speaks)]
+        self.shared = isinstance(modules, nn.Module)
+        self.modules = [modules] * self.A if self.shared else list(modules)
+        if len(self.modules) != self.A:
+            raise _abi.MpeError("Actors: %d actors for %d agents" % (len(self.modules), self.A))
+        self._want = (bool(logp), bool(ids), bool(logits))
+        self.moves = self.utter = self.logp = self.ids = self.logits = None
+        self._frozen = None
+        self._ptrs = {}
+        self._check()
+
+    def _check(self):
+        """Every module against its agent; -> [(Linear layers, activation)] per agent."""
+        layers = []
+        for i, m in enumerate(self.modules):
+            if self.n_out[i] < 1:
+                raise _abi.MpeError("Actors: agent %d neither moves nor speaks: it has no head" % i)
+            if self.n_out[i] > _LW:
+                raise _abi.MpeError("Actors: agent %d needs %d logits (5 * movable + dim_c * speaks), at most MPE_ACTOR_MAX_OUT = %d"
+                                    % (i, self.n_out[i], _LW))
+            try:
+                lins, act = _actor_layers(m, self.n_out[i], "Actors")
+            except _abi.MpeError as e:
+                raise _abi.MpeError("%s [agent %d: movable = %s, speaks = %s, dim_c = %d]"
+                                    % (e, i, self.movable[i], self.speaks[i], self.dim_c))
+            D = self.obs_widths[i]
+            if lins[0].in_features != D:
+                raise _abi.MpeError("Actors: agent %d's actor takes %d inputs, its observation has %d" % (i, lins[0].in_features, D))
+            if D > _abi.MPE_ACTOR_MAX_INPUT:
+                raise _abi.MpeError("Actors: agent %d's input width %d > MPE_ACTOR_MAX_INPUT = %d" % (i, D, _abi.MPE_ACTOR_MAX_INPUT))
+            layers.append((lins, act))
+        return layers
+
+    def pack(self, device=None):
+        """-> (weights tensor, MpeActorSet): the set's packed actors, one copy per distinct module object."""
+        layers = self._check()
+        aset = _abi.MpeActorSet()
+        blobs, where, off = [], {}, 0
+        for i, m in enumerate(self.modules):
+            if id(m) not in where:
+                blob = pack_actor16(m, self.n_out[i])
+                where[id(m)] = off
+                blobs.append(blob if device is None else blob.to(device))
+                off += blob.numel()
+            lins, act = layers[i]
+            aset.n_layers[i] = len(lins)
+            aset.width[i][0] = lins[0].in_features
+            for k, lin in enumerate(lins):
+                aset.width[i][k + 1] = lin.out_features
+            aset.activation[i] = _abi.MPE_POLICY_TANH if act == "tanh" else _abi.MPE_POLICY_RELU
+            aset.offset[i] = where[id(m)]
+            aset.movable[i] = int(self.movable[i])
+            aset.speaks[i] = int(self.speaks[i])
+        wts = torch.cat(blobs).contiguous()
+        aset.n_agents, aset.dim_c = self.A, self.dim_c
+        aset.mode, aset.seed = _POLICY_MODES[self.mode], self.seed
+        aset.weights = wts.data_ptr() if wts.is_cuda else None
+        return wts, aset
+
+    def freeze(self):
+        """Pack the weights once; act() stops re-reading the modules (call again after an update; unfreeze() goes back)."""
+        self._frozen = self.pack(self.world.device)
+        return self
+
+    def unfreeze(self):
+        self._frozen = None
+        return self
+
+    def _buffers(self):
+        if self.moves is not None:
+            return
+        A, B, dev = self.A, self.B, self.world.device
+        self.moves = torch.zeros((A, B, _abi.MPE_ACTION_DIM), dtype=torch.float32, device=dev)
+        if self.dim_c:
+            self.utter = torch.zeros((A, B, self.dim_c), dtype=torch.float32, device=dev)
+            self._action = (self.moves, self.utter)
+        else:
+            self._action = self.moves
+        logp, ids, logits = self._want
+        if logp:
+            self.logp = torch.zeros((A, B), dtype=torch.float32, device=dev)
+        if ids:
+            self.ids = torch.zeros((2, A, B), dtype=torch.int32, device=dev)
+        if logits:
+            self.logits = torch.zeros((A, B, _LW), dtype=torch.float32, device=dev)
+
+    def _obs_ptrs(self, obs_n):
+        if len(obs_n) != self.A:
+            raise _abi.MpeError("Actors.act: %d observation blocks for %d agents" % (len(obs_n), self.A))
+        key = tuple(o.data_ptr() for o in obs_n)
+        arr = self._ptrs.get(key)
+        if arr is None:
+            for i, o in enumerate(obs_n):
+                if not torch.is_tensor(o) or o.dtype != torch.float32 or not o.is_contiguous() or o.device != self.world.device or \
+                        tuple(o.shape) != (self.B, self.obs_widths[i]):
+                    raise _abi.MpeError("Actors.act: obs_n[%d] is a contiguous float32 [%d, %d] tensor on the env's device"
+                                        % (i, self.B, self.obs_widths[i]))
+            if len(self._ptrs) >= 64:
+                self._ptrs.clear()
+            arr = self._ptrs[key] = (C.c_void_p * self.A)(*key)
+        return arr
+
+    def act(self, obs_n, t=0, moves=None, logp=None):
+        """One launch: every agent's rows for the observations obs_n (a list of [B, D_i] device tensors: env.step's / env.reset's
+        own output qualifies) at global step t (the sample draws' key) -> the [A,B,5] move tensor, or (moves, utterances
+        [A,B,dim_c]) where agents speak: what env.step takes, zero-copy.  The tensors are this object's own and are rewritten by
+        the next act(); moves / logp: write those two into the caller's tensors instead (a trajectory's rows)."""
+        self._buffers()
+        wts, aset = self._frozen if self._frozen is not None else self.pack(self.world.device)
+        mv = self.moves if moves is None else moves
+        lp = self.logp if logp is None else logp
+        _abi.check(_abi.lib().mpe_actor_act(
+            C.byref(aset), self._obs_ptrs(obs_n), self.B, int(t), int(self.world.world_offset), mv.data_ptr(),
+            self.utter.data_ptr() if self.utter is not None else None, self.ids.data_ptr() if self.ids is not None else None,
+            lp.data_ptr() if lp is not None else None, self.logits.data_ptr() if self.logits is not None else None,
+            _abi.raw_stream(self.world.device)), "mpe_actor_act")
+        del wts      # (stream-ordered: the caching allocator reuses the block only behind the launch)
+        if moves is None:
+            return self._action
+        return (mv, self.utter) if self.dim_c else mv
+
+    def reference(self, obs_n):
+        """The fp64 torch forward pass, on whatever device the modules and obs_n are: per agent (move logits [B,5] or None,
+        utterance logits [B,dim_c] or None)."""
+        import copy
+        out = []
+        for i, o in enumerate(obs_n):
+            m = copy.deepcopy(self.modules[i]).double()
+            with torch.no_grad():
+                z = m(torch.as_tensor(o).to(next(m.parameters()).device).double())
+            out.append((z[:, :_abi.MPE_ACTION_DIM] if self.movable[i] else None,
+                        z[:, z.shape[1] - self.dim_c:] if self.speaks[i] else None))
+        return out
+
+
+class LoopTrajectory(object):
+    """What PolicyLoop.run recorded: obs[t][i] [B, D_i], rew [T,A,B], done [T,A,B] (the outputs of step t), act [T,A,B,5] (the rows
+    applied at step t), utter [T,A,B,dim_c] or None, logp [T,A,B] or None."""
+
+    def __init__(self, env, pi, T):
+        w, off = env.world, env._obs_off
+        A, B, dev = pi.A, pi.B, w.device
+        self.T = T
+        self.obs_flat = torch.zeros((T, int(off[-1]) * B), dtype=torch.float32, device=dev)
+        self.obs = [[self.obs_flat[t, off[i] * B: off[i + 1] * B].view(B, off[i + 1] - off[i]) for i in range(A)] for t in range(T)]
+        self.rew = torch.zeros((T, A, B), dtype=torch.float32, device=dev)
+        self.done = torch.zeros((T, A, B), dtype=torch.bool, device=dev)
+        self.act = torch.zeros((T, A, B, _abi.MPE_ACTION_DIM), dtype=torch.float32, device=dev)
+        self.utter = torch.zeros((T, A, B, pi.dim_c), dtype=torch.float32, device=dev) if pi.dim_c else None
+        self.logp = torch.zeros((T, A, B), dtype=torch.float32, device=dev) if pi._want[0] else None
+
+
+class PolicyLoop(object):
+    """The closed loop `act_n = policy(obs_n); env.step(act_n)` on the device: per step one actor launch (Actors.act) and one
+    env.step, and every episode_len global steps, first, the device-side reset RandomRollout.enqueue makes (mpe_reset /
+    mpe_reset_rows with `seed`'s draws, the comm state zeroed) and the observation of the reset state.  Works wherever env.step
+    is a device step: the built-in scenarios at any size, row-program envs, traced reference-style files; refuses what
+    step_many refuses, by the same names.  run() calls continue one step count and episode clock."""
+
+    def __init__(self, env, actors, episode_len=25, seed=None):
+        if not isinstance(actors, Actors):
+            raise _abi.MpeError("PolicyLoop: actors is an Actors(env, modules, ...)")
+        if actors.env is not env:
+            raise _abi.MpeError("PolicyLoop: the Actors were built for another env")
+        _step_many_env_check(env)
+        if int(episode_len) and not env._device_restart_ok:
+            raise _abi.MpeError("PolicyLoop(episode_len > 0): the resets are world.reset_uniform's device draws; this env's "
+                                "reset_world is not that -- use episode_len = 0 and reset it yourself")
+        env._ensure_buffers()
+        self.env, self.world, self.pi = env, env.world, actors
+        self.episode_len = int(episode_len)
+        self.seed = int(env.world.seed if seed is None else seed) & (2 ** 64 - 1)
+        self._prog = getattr(env, "_prog", None)
+        self._lr = float(getattr(env._scenario, "landmark_range", 1.0))
+        self._gen_desc = _copy_struct(self.world.scenario_desc(_abi.MPE_SCN_GENERIC))
+        self.t = 0
+        self.obs_n = None      # the observation the next decision is taken on (None: observed at the next step)
+
+    def device_reset(self, episode):
+        """Restart every world with the draws of (seed, episode) on the device and observe the new state -> obs_n."""
+        env, w, L = self.env, self.world, _abi.lib()
+        st = _abi.raw_stream(w.device)
+        b = env._sets[0].bufs
+        if self._prog is not None:
+            _abi.check(L.mpe_reset_rows(C.byref(self._gen_desc), C.byref(b), self._prog.ref, w.batch_size, None, self._lr, self.seed,
+                                        int(episode), int(w.world_offset), st), "mpe_reset_rows")
+        else:
+            _abi.check(L.mpe_reset(C.byref(self._gen_desc), C.byref(b), w.batch_size, None, self._lr, self.seed, int(episode),
+                                   int(w.world_offset), st), "mpe_reset")
+        if env._comm is not None:
+            env._comm.zero_()
+        return self._observe()
+
+    def _observe(self):
+        env = self.env
+        out = env._next_set()
+        env._observe_into(out)
+        return list(out.obs_n)
+
+    def _mark_stale(self):
+        env = self.env
+        if self.episode_len:      # (device-side resets bypass Scenario.reset_world: re-derived before the next Python-API step)
+            env._scenario_state_stale = True
+            if env.episode_step is not None:
+                env.episode_step.fill_(self.t % self.episode_len)
+
+    def step(self, traj=None, k=0):
+        """One step of the loop at global step self.t -> env.step's outputs."""
+        env, pi = self.env, self.pi
+        if self.episode_len and self.t % self.episode_len == 0:
+            self.obs_n = self.device_reset(self.t // self.episode_len)
+        elif self.obs_n is None:
+            self.obs_n = self._observe()
+        if traj is not None:
+            action = pi.act(self.obs_n, self.t, moves=traj.act[k], logp=traj.logp[k] if traj.logp is not None else None)
+        else:
+            action = pi.act(self.obs_n, self.t)
+        out = env.step(action)
+        self.obs_n = out[0]
+        if traj is not None:
+            o = env._sets[env._flip]
+            traj.obs_flat[k].copy_(o.obs)
+            traj.rew[k].copy_(o.rew)
+            traj.done[k].copy_(o.done)
+            if traj.utter is not None:
+                traj.utter[k].copy_(pi.utter)
+        self.t += 1
+        return out
+
+    def run(self, T, record=True):
+        """T steps.  record: -> a LoopTrajectory (three device copies per step); False: -> the last step's env.step outputs."""
+        _step_many_env_check(self.env)
+        traj = LoopTrajectory(self.env, self.pi, int(T)) if record else None
+        out = None
+        for k in range(int(T)):
+            out = self.step(traj, k)
+        self._mark_stale()
+        return traj if record else out
+
+    def capture(self, T):
+        """The next T steps (from self.t, the current state) as ONE HIP graph: a straight line of kernels -- reset, observe, act,
+        step -- with nothing recorded.  -> an object whose replay() runs them and advances this loop's step count by T; the
+        draw keys and episode numbers are those of the captured steps (a replay repeats them: capture a multiple of episode_len
+        steps from an episode start for a periodic rollout, as RandomRollout.capture).  The weights are frozen for the capture
+        (freeze() again and re-capture after an update).  Two warm-up steps really run in front of the capture; the state and the
+        step count are put back."""
+        _step_many_env_check(self.env)
+        env, w, pi = self.env, self.world, self.pi
+        if pi._frozen is None:
+            pi.freeze()
+        g = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream(device=w.device)
+        s.wait_stream(torch.cuda.current_stream(w.device))
+        t0, obs0, flip0 = self.t, self.obs_n, env._flip
+        with torch.cuda.stream(s):
+            if self.obs_n is None and not (self.episode_len and self.t % self.episode_len == 0):
+                self.obs_n = obs0 = self._observe()
+                flip0 = env._flip
+            pos, vel = w.pos.clone(), w._vel_all.clone()
+            comm = env._comm.clone() if env._comm is not None else None
+            keep = [o.clone() for o in obs0] if obs0 is not None else None
+            choice = w.choice_i32.clone() if w.choice_i32 is not None else None
+            for _ in range(2):      # code objects and allocations outside the capture
+                self.step()
+            w.pos.copy_(pos)
+            w._vel_all.copy_(vel)
+            if comm is not None:
+                env._comm.copy_(comm)
+            if choice is not None:
+                w.choice_i32.copy_(choice)
+            if keep is not None:
+                for dst, src in zip(obs0, keep):
+                    dst.copy_(src)
+            self.t, self.obs_n, env._flip = t0, obs0, flip0
+            torch.cuda.synchronize()
+            with torch.cuda.graph(g, stream=s):
+                for _ in range(int(T)):
+                    self.step()
+        torch.cuda.current_stream(w.device).wait_stream(s)
+        self.t = t0
+        return _LoopGraph(g, self, int(T), self.obs_n, env._flip)
+
+
+class _LoopGraph(object):
+    def __init__(self, graph, loop, T, obs_n, flip):
+        self.graph, self.loop, self.T, self._obs_n, self._flip = graph, loop, T, obs_n, flip
+
+    def replay(self):
+        loop = self.loop
+        self.graph.replay()
+        loop.t += self.T
+        loop.obs_n, loop.env._flip = self._obs_n, self._flip
+        loop._mark_stale()
+        for out in loop.env._sets:
+            out.act_ptr = None

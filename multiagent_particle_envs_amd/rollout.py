@@ -789,12 +789,13 @@ def _rollout_actions(env, moves, episode_len, seed, comm, cache, key):
 _POLICY_MODES = {"greedy": _abi.MPE_POLICY_GREEDY, "sample": _abi.MPE_POLICY_SAMPLE, "softmax": _abi.MPE_POLICY_SOFTMAX}
 
 
-def _actor_layers(module):
-    """nn.Sequential (or a lone nn.Linear) -> ([Linear, ...], activation name); refuses anything the kernel does not evaluate."""
+def _actor_layers(module, n_out=_abi.MPE_ACTION_DIM, who="MlpPolicy"):
+    """nn.Sequential (or a lone nn.Linear) -> ([Linear, ...], activation name); refuses anything the kernel does not evaluate.
+    n_out: the width the last Linear layer must have; who: the class the refusals name (policy.Actors checks its modules here)."""
     import torch.nn as nn
     mods = [module] if isinstance(module, nn.Linear) else list(module.children()) if isinstance(module, nn.Sequential) else None
     if mods is None:
-        raise _abi.MpeError("MlpPolicy: an actor is an nn.Sequential of Linear layers with ReLU / Tanh between them (got %s)"
+        raise _abi.MpeError(who + ": an actor is an nn.Sequential of Linear layers with ReLU / Tanh between them (got %s)"
                             % type(module).__name__)
     lins, acts = [], []
     for k, m in enumerate(mods):
@@ -804,24 +805,24 @@ def _actor_layers(module):
         elif not want_linear and isinstance(m, (nn.ReLU, nn.Tanh)):
             acts.append(type(m).__name__.lower())
         else:
-            raise _abi.MpeError("MlpPolicy: unsupported layer %d (%s): an actor alternates Linear and ReLU / Tanh and ends with a Linear"
+            raise _abi.MpeError(who + ": unsupported layer %d (%s): an actor alternates Linear and ReLU / Tanh and ends with a Linear"
                                 % (k, type(m).__name__))
     if not lins or len(mods) % 2 == 0:
-        raise _abi.MpeError("MlpPolicy: an actor ends with a Linear layer")
+        raise _abi.MpeError(who + ": an actor ends with a Linear layer")
     if len(lins) > _abi.MPE_POLICY_MAX_LAYERS:
-        raise _abi.MpeError("MlpPolicy: %d Linear layers (at most %d)" % (len(lins), _abi.MPE_POLICY_MAX_LAYERS))
+        raise _abi.MpeError(who + ": %d Linear layers (at most %d)" % (len(lins), _abi.MPE_POLICY_MAX_LAYERS))
     if len(set(acts)) > 1:
-        raise _abi.MpeError("MlpPolicy: one activation per actor (got %s)" % sorted(set(acts)))
+        raise _abi.MpeError(who + ": one activation per actor (got %s)" % sorted(set(acts)))
     for k, lin in enumerate(lins):
         if lin.weight.dtype != torch.float32 or (lin.bias is not None and lin.bias.dtype != torch.float32):
-            raise _abi.MpeError("MlpPolicy: Linear layer %d is not float32" % k)
+            raise _abi.MpeError(who + ": Linear layer %d is not float32" % k)
         if k > 0 and lin.in_features != lins[k - 1].out_features:
-            raise _abi.MpeError("MlpPolicy: Linear layer %d takes %d inputs, layer %d gives %d"
+            raise _abi.MpeError(who + ": Linear layer %d takes %d inputs, layer %d gives %d"
                                 % (k, lin.in_features, k - 1, lins[k - 1].out_features))
         if k + 1 < len(lins) and lin.out_features > _abi.MPE_POLICY_MAX_WIDTH:
-            raise _abi.MpeError("MlpPolicy: hidden width %d > %d" % (lin.out_features, _abi.MPE_POLICY_MAX_WIDTH))
-    if lins[-1].out_features != _abi.MPE_ACTION_DIM:
-        raise _abi.MpeError("MlpPolicy: the last Linear layer gives %d outputs (need %d)" % (lins[-1].out_features, _abi.MPE_ACTION_DIM))
+            raise _abi.MpeError(who + ": hidden width %d > %d" % (lin.out_features, _abi.MPE_POLICY_MAX_WIDTH))
+    if lins[-1].out_features != n_out:
+        raise _abi.MpeError(who + ": the last Linear layer gives %d outputs (need %d)" % (lins[-1].out_features, n_out))
     return lins, (acts[0] if acts else "relu")
 
 
