@@ -21,7 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NINE = ["simple", "simple_spread", "simple_tag", "simple_adversary", "simple_push", "simple_speaker_listener", "simple_reference",
         "simple_crypto", "simple_world_comm"]
 ENVS = [(n, {}) for n in NINE] + [("simple_spread", {"num_agents": 10}), (os.path.join(ROOT, "examples", "corral.py"), {}),
-                                  (os.path.join(ROOT, "tests", "refstyle", "convoy.py"), {})]
+                                  (os.path.join(ROOT, "tests", "refstyle", "convoy.py"), {}),
+                                  ("simple_spread", {"num_agents": 16})]      # 96 columns: three passes of the first layer's k loop
 # (activation, hidden widths): 3, 2 and 1 Linear layers, a hidden width that is not a multiple of 16
 CONFIGS = [(torch.nn.ReLU, (64, 64)), (torch.nn.Tanh, (64,)), (torch.nn.ReLU, ()), (torch.nn.Tanh, (20, 64)), (torch.nn.ReLU, (20,))]
 STREAMS = (_abi.MPE_STREAM_POLICY, _abi.MPE_STREAM_POLICY_COMM)
