@@ -1,32 +1,23 @@
-// mpe_wide.hip -- wave-per-world kernel for large entity counts (simple_spread N=64: 128 entities).
+// mpe_wide.hip -- the kernels for large entity counts: lanes over the entities of a world, the world in LDS.
 //
-// One WAVE owns one world; lane = agent (agents lane, lane+64, ... when A > 64).  The world's
-// positions and velocities are staged once in a wave-private LDS block (2 KiB at N=64) and every
-// phase of the step runs out of it with no workgroup barrier at all -- the only synchronisation is
-// the wave's own program order plus LDS fences.  A 256-thread workgroup is four independent waves
-// (four consecutive worlds) that merely share the per-entity constant table.
-//
-// Why a wave and not a workgroup per world (the first version): with a workgroup per world every
-// phase ends in __syncthreads and all co-resident workgroups run their phases in lock-step, so the
-// physics (latency-bound, ~40 us at B=4096) and the observation stores (~90 us) added up.  A wave
-// per world has no barriers, four to eight worlds per SIMD slide against each other, and the whole
-// batch is resident at once: the kernel is the store stream plus one world's latency.
-//
-//   contacts   lane i, two passes over the collidable entities (ascending, SURVEY Q9): pass 1 marks
-//              the partners close enough to exert a non-zero force (squared distance under
-//              (r_i + r_j + 20k)^2: beyond it the fp32 soft-plus term is exactly 0) in a 64-bit mask,
-//              pass 2 evaluates only those.  ~4 of 63 partners at N=64.
-//   obs        98 % of the HBM bytes (A rows x D floats = 98 KiB per world at N=64).  Rows are
-//              computed straight from LDS in output order: consecutive lanes write consecutive
-//              16-byte pieces of a row, a full 1 KiB per wave store.
-//   reward     lane l: min over agents of the SQUARED distance to landmark l (sqrt is monotone: one
-//              sqrt per landmark afterwards), lane i: contact count of agent i with the exact
-//              sqrt_lt test; sums by wave64 shuffle reductions.
-// State loads are 4-byte accesses 4*B bytes apart (the SoA layout is batch-innermost), so a 128-byte
-// line serves 32 neighbouring worlds: the world -> workgroup map keeps each such group of worlds on
-// ONE XCD (blockIdx % 8 selects the XCD), so that the line is fetched into one L2, not eight.
-// Per pair the arithmetic is mpe_device.h's, as in the small-N kernels; sums over landmarks / agents
-// are reduction trees (documented in DESIGN.md 4).
+//   k_wave<PHYS,OUT,ROLL>   one wave per world: any A + L that fits the LDS (spread beyond 64 agents, simple_tag at any
+//                           team sizes, per-entity constant tables), physics-only and observe-only calls, and the rollout
+//                           above MPE_MULTI_ROLL_MAX_N where k_duo_roll does not apply.
+//   k_multi<PHYS,OUT,ROLL>  several worlds per wave (8, 16 or 32 lanes per world): max(A, L) <= 32 and A + L <= 64 -- spread's
+//                           step and rollout, and the physics-only call of any scenario.
+//   k_duo<G>                two waves per world, G worlds per workgroup: the fused spread step of 33..64 identical agents
+//                           (the N = 64 headline shape).
+//   k_duo_roll<G>           the fused T-step rollout on k_duo's plan.
+// launch_wide picks one.  The steps whose results must agree bit for bit (tests/test_gpu_parity.py, _rollout.py) are shared:
+//   near_mask32 / add_contacts   the two passes of the contact loop (all four; k_multi keeps its own copy of pass 2)
+//   rollout_move, EpisodeClock, reset_entity   a rollout step's move, its episode clock and in-launch reset_world draws
+//                                (k_wave<ROLL>, k_multi<ROLL>, k_duo_roll)
+//   xcd_group                    the world -> workgroup map of the persistent kernels (k_wave, k_multi)
+//   duo_world0, duo_stage_state, duo_step_lane, duo_emit, duo_reward   the duo plan (k_duo, k_duo_roll)
+//   emit_rows, emit_rows_fast    spread's observation rows (k_wave and the duo plan; k_multi's rows run over (slot, piece))
+// Per pair the arithmetic is mpe_device.h's, as in the small-N kernels; sums over landmarks / agents are reduction trees
+// (documented in DESIGN.md 4).  The spread reward blocks of k_wave, k_multi and duo_reward only look alike: batches with
+// a per-agent size table, segmented reductions, and one wave with identical agents -- they stay apart.
 
 #include <cstring>
 
@@ -307,6 +298,74 @@ __device__ __forceinline__ unsigned near_mask32(const float2 *CPW, const float *
   return near << (32 - n);
 }
 
+// Pass 2: the partners whose bit is set in `near`, ascending (Q9), each force added as  a = g + a.  UNI: dist_min is
+// r_i + r_i (identical agents, csz is not read), else r_i + csz[partner].
+template <bool UNI>
+__device__ __forceinline__ float2 add_contacts(unsigned near, const float2 *CPW, const float *csz, int kb, float2 me, float ri,
+                                               const WideDesc &d, float2 f) {
+  while (near) {
+    const int j = __clz((int)near);
+    near &= ~(0x80000000u >> j);
+    const float2 pj = CPW[kb + j];
+    float gx, gy;
+    contact_force(me.x - pj.x, me.y - pj.y, UNI ? ri + ri : ri + csz[kb + j], d.cforce, d.cmargin, d.cmargin_inv, gx, gy);
+    f.x = gx + f.x;
+    f.y = gy + f.y;
+  }
+  return f;
+}
+
+// The action force of agent i of world w (global number gw) at step t (global step gt) of a rollout: the caller's move
+// (act_seq) or the one-hot row mpe_random_actions would write, decoded as environment.py:144-181 decodes it.
+__device__ __forceinline__ void rollout_move(const RollArgs &ra, int t, int A, size_t B, int i, size_t w, uint64_t gw, uint64_t gt,
+                                             float accel, float &ux, float &uy) {
+  if (ra.act_seq) {
+    fetch_action_seq(ra.act_seq, t, A, B, i, w, accel, ux, uy);
+  } else {
+    const int m = action_draw(ra.seed, gw, gt, i);
+    ux = ((m == 1 ? 1.f : 0.f) - (m == 2 ? 1.f : 0.f)) * accel;
+    uy = ((m == 3 ? 1.f : 0.f) - (m == 4 ? 1.f : 0.f)) * accel;
+  }
+  ux = ux + 0.f;
+  uy = uy + 0.f;
+}
+
+// The episode clock of a rollout: in-launch resets fall on the global steps that are multiples of episode_len (0 = never).
+// Two scalars in registers.  tick() once per step: true when this step starts with reset_world for episode `ep`; the
+// caller draws it (reset_entity) and then advances ep.
+struct EpisodeClock {
+  int countdown;   // steps until the next reset, -1 = never
+  uint64_t ep;     // the episode the next reset starts
+  __device__ __forceinline__ EpisodeClock(const RollArgs &ra, bool roll) : countdown(-1), ep(0) {   // roll false: never
+    if (roll && ra.episode_len > 0) {
+      const uint64_t len = (uint64_t)ra.episode_len, r = ra.step0 % len;
+      countdown = r == 0 ? 0 : (int)(len - r);
+      ep = ra.step0 / len + (r ? 1 : 0);
+    }
+  }
+  __device__ __forceinline__ bool tick(const RollArgs &ra) {
+    const bool reset_now = countdown == 0;
+    if (countdown >= 0) countdown = reset_now ? ra.episode_len - 1 : countdown - 1;
+    return reset_now;
+  }
+};
+
+// reset_world's position of entity e (agents first) of world gw, as mpe_reset draws it for episode ep: agents in the unit
+// box, landmarks in the landmark_range box; the velocities are zero.
+__device__ __forceinline__ float2 reset_entity(const RollArgs &ra, uint64_t gw, uint64_t ep, int e, bool agent) {
+  float x, y;
+  reset_draw(ra.seed, gw, ep, e, agent ? 1.0f : ra.landmark_range, x, y);
+  return make_float2(x, y);
+}
+
+// x -> group of the persistent kernels (k_wave, k_multi): XCD = x % 8 (hardware round-robin), slot = x / 8; eight
+// consecutive slots of one XCD own eight consecutive groups, so the worlds that share a 128-byte line of every state
+// row stay on one XCD.
+__device__ __forceinline__ unsigned xcd_group(unsigned x) {
+  const unsigned xcd = x & 7u, slot = x >> 3;
+  return ((slot >> 3) << 6) | (xcd << 3) | (slot & 7u);
+}
+
 // sqrt_lt with the bounds of the guard band precomputed (m2 = m*m, lo = m2 (1 - 4e-7), hi = m2 (1 + 4e-7))
 __device__ __forceinline__ bool sqrt_lt_pre(float s2, float m, float lo, float hi, bool has_band) {
   const bool below = s2 < lo;
@@ -316,6 +375,32 @@ __device__ __forceinline__ bool sqrt_lt_pre(float s2, float m, float lo, float h
   return r;
 }
 
+// ---- one wave per world ---------------------------------------------------------------------------------------------
+// One WAVE owns one world; lane = agent (agents lane, lane+64, ... when A > 64).  The world's
+// positions and velocities are staged once in a wave-private LDS block (2 KiB at N=64) and every
+// phase of the step runs out of it with no workgroup barrier at all -- the only synchronisation is
+// the wave's own program order plus LDS fences.  A 256-thread workgroup is four independent waves
+// (four consecutive worlds) that merely share the per-entity constant table.
+//
+// Why a wave and not a workgroup per world (the first version): with a workgroup per world every
+// phase ends in __syncthreads and all co-resident workgroups run their phases in lock-step, so the
+// physics (latency-bound, ~40 us at B=4096) and the observation stores (~90 us) added up.  A wave
+// per world has no barriers, four to eight worlds per SIMD slide against each other, and the whole
+// batch is resident at once: the kernel is the store stream plus one world's latency.
+//
+//   contacts   lane i, two passes over the collidable entities (ascending, SURVEY Q9): pass 1 marks
+//              the partners close enough to exert a non-zero force (squared distance under
+//              (r_i + r_j + 20k)^2: beyond it the fp32 soft-plus term is exactly 0) in a 64-bit mask,
+//              pass 2 evaluates only those.  ~4 of 63 partners at N=64.
+//   obs        98 % of the HBM bytes (A rows x D floats = 98 KiB per world at N=64).  Rows are
+//              computed straight from LDS in output order: consecutive lanes write consecutive
+//              16-byte pieces of a row, a full 1 KiB per wave store.
+//   reward     lane l: min over agents of the SQUARED distance to landmark l (sqrt is monotone: one
+//              sqrt per landmark afterwards), lane i: contact count of agent i with the exact
+//              sqrt_lt test; sums by wave64 shuffle reductions.
+// State loads are 4-byte accesses 4*B bytes apart (the SoA layout is batch-innermost), so a 128-byte
+// line serves 32 neighbouring worlds: the world -> workgroup map keeps each such group of worlds on
+// ONE XCD (blockIdx % 8 selects the XCD), so that the line is fetched into one L2, not eight.
 // ROLL: the fused T-step rollout (mpe_rollout_random) -- the world stays in LDS across the steps, moves and resets
 // are drawn in-kernel (Philox, as mpe_random_actions / mpe_reset draw them), every step's rows / rewards are still
 // written.  A wave runs ahead into step t+1's contact phase while its step-t row stores drain, so the VALU-bound
@@ -407,13 +492,9 @@ k_wave(const WideDesc d, const MpeBuffers b, const size_t B, const unsigned n_gr
   const float far = kFarX * d.cmargin;
   const int D = d.D;
 
-  // ---- persistent loop over groups of kWavesPerWg consecutive worlds ------------------------------
-  // x -> group: XCD = x % 8 (hardware round-robin), slot = x / 8;  eight consecutive slots of one XCD
-  // own eight consecutive groups (32 worlds = one 128-byte line of every state row).
+  // ---- persistent loop over groups of kWavesPerWg consecutive worlds (eight groups = 32 worlds = one line) ------
   for (unsigned x = blockIdx.x; x < n_groups_padded; x += gridDim.x) {
-    const unsigned xcd = x & 7u, slot = x >> 3;
-    const unsigned g = ((slot >> 3) << 6) | (xcd << 3) | (slot & 7u);
-    const size_t w = (size_t)g * kWavesPerWg + wave;
+    const size_t w = (size_t)xcd_group(x) * kWavesPerWg + wave;
     if (w >= B) continue;  // wave-uniform
 
     // ---- stage the world -----------------------------------------------------------------------
@@ -440,38 +521,19 @@ k_wave(const WideDesc d, const MpeBuffers b, const size_t B, const unsigned n_gr
     const int T = ROLL ? ra.T : 1;
     const size_t obs_stride = (ROLL && ra.trajectory) ? (size_t)A * D * B : 0;
     const size_t row_stride = (ROLL && ra.trajectory) ? (size_t)A * B : 0;
-    int countdown = -1;    // resets fall on global steps that are multiples of episode_len
-    uint64_t ep = 0;
-    if (ROLL && ra.episode_len > 0) {
-      const uint64_t len = (uint64_t)ra.episode_len, r = ra.step0 % len;
-      countdown = r == 0 ? 0 : (int)(len - r);
-      ep = ra.step0 / len + (r ? 1 : 0);
-    }
+    EpisodeClock clk(ra, ROLL);
     for (int t = 0; t < T; ++t) {
     if (ROLL) {
       const uint64_t gt = ra.step0 + (uint64_t)t;
-      const bool reset_now = countdown == 0;
-      if (countdown >= 0) countdown = reset_now ? ra.episode_len - 1 : countdown - 1;
-      if (reset_now) {  // reset_world, as mpe_reset draws it for episode ep
-        for (int e = lane; e < E; e += kWave) {
-          float x, y;
-          reset_draw(ra.seed, gw, ep, e, e < A ? 1.0f : ra.landmark_range, x, y);
-          Q[e < A ? L + e : e - A] = make_float2(x, y);
-        }
+      if (clk.tick(ra)) {  // reset_world, as mpe_reset draws it for episode ep
+        for (int e = lane; e < E; e += kWave) Q[e < A ? L + e : e - A] = reset_entity(ra, gw, clk.ep, e, e < A);
         for (int i = lane; i < A; i += kWave) V[i] = make_float2(0.f, 0.f);
-        ++ep;
+        ++clk.ep;
       }
-      for (int i = lane; i < A; i += kWave) {   // the one-hot row mpe_random_actions would write, decoded -- or the caller's (act_seq)
-        const float sens = aconst[i].z;
+      for (int i = lane; i < A; i += kWave) {
         float ux, uy;
-        if (ra.act_seq) {
-          fetch_action_seq(ra.act_seq, t, A, B, i, w, sens, ux, uy);
-        } else {
-          const int m = action_draw(ra.seed, gw, gt, i);
-          ux = ((m == 1 ? 1.f : 0.f) - (m == 2 ? 1.f : 0.f)) * sens;
-          uy = ((m == 3 ? 1.f : 0.f) - (m == 4 ? 1.f : 0.f)) * sens;
-        }
-        U[i] = make_float2(ux + 0.f, uy + 0.f);
+        rollout_move(ra, t, A, B, i, w, gw, gt, aconst[i].z, ux, uy);
+        U[i] = make_float2(ux, uy);
       }
       wave_sync();
       if (!agents_only) {  // the partner list follows the positions
@@ -493,7 +555,7 @@ k_wave(const WideDesc d, const MpeBuffers b, const size_t B, const unsigned n_gr
         const float2 me = Q[L + (have ? i : 0)];
         const float ri = sizeq[L + (have ? i : 0)];
         const float2 u = U[have ? i : 0];
-        float ax = u.x, ay = u.y;  // action force first, then the partners in ascending order (Q9)
+        float2 f = u;  // action force first, then the partners in ascending order (Q9)
         const bool pushes = (fi & kCollide) && (fi & kMovable);
         const int self_rank = pushes ? crank[i] : -1;
         const float rfar = ri + far;
@@ -504,19 +566,11 @@ k_wave(const WideDesc d, const MpeBuffers b, const size_t B, const unsigned n_gr
                                     : near_mask32<false>(CPW, csz, kb, n, me, rfar, 0.f);
           if (self_rank >= kb && self_rank < kb + 32) near &= ~(0x80000000u >> (self_rank - kb));  // not against itself
           if (!pushes) near = 0u;
-          while (near) {  // pass 2: those only, ascending (Q9)
-            const int j = __clz((int)near);
-            near &= ~(0x80000000u >> j);
-            const float2 pj = CPW[kb + j];
-            float gx, gy;
-            contact_force(me.x - pj.x, me.y - pj.y, ri + csz[kb + j], d.cforce, d.cmargin, d.cmargin_inv, gx, gy);
-            ax = gx + ax;
-            ay = gy + ay;
-          }
+          f = add_contacts<false>(near, CPW, csz, kb, me, ri, d, f);
         }
         if (have && (fi & kMovable)) {
           float2 p = me, v = V[i];
-          integrate_one(p.x, p.y, v.x, v.y, ax, ay, ac.x, ac.y, d.damp, d.dt);
+          integrate_one(p.x, p.y, v.x, v.y, f.x, f.y, ac.x, ac.y, d.damp, d.dt);
           QN[i] = p;
           V[i] = v;
           if (!ROLL) {   // (the rollout writes the state back once, after its last step)
@@ -769,6 +823,66 @@ __device__ __forceinline__ void duo_reward(const WideDesc &d, const MpeBuffers &
   }
 }
 
+// ---- the duo plan's shared steps (k_duo and k_duo_roll) -----------------------------------------------------------
+// The worlds of this workgroup: G consecutive ones from w0, nvalid of them inside the batch (false: none).  XCD =
+// blockIdx % 8 (hardware round-robin), and the 32 / G workgroups that share a 128-byte line of every state row (32
+// consecutive worlds) sit on ONE XCD.
+template <int G>
+__device__ __forceinline__ bool duo_world0(size_t B, size_t &w0, int &nvalid) {
+  constexpr unsigned GPL = 32 / G;
+  const unsigned x = blockIdx.x, xcd = x & 7u, slot = x >> 3;
+  w0 = (size_t)(((slot / GPL) * 8u + xcd) * GPL + (slot % GPL)) * G;
+  nvalid = (B - w0) < (size_t)G ? (int)(B - w0) : G;
+  return w0 < B;   // workgroup-uniform
+}
+
+// Cooperative stage of world wg's state by the threads of its slot (thread -> (row, world slot): tid % G is the slot,
+// r0 = tid / G its first row, so the slots of a row are adjacent lanes and adjacent bytes): positions into Q0 in
+// observation order, velocities into V0.  MIRROR: the landmarks also into Q1 (the rollout's second position buffer).
+template <bool MIRROR>
+__device__ __forceinline__ void duo_stage_state(const MpeBuffers &b, size_t B, int A, int L, size_t wg, int r0, float *Q0,
+                                                float *Q1, float *V0) {
+  constexpr int NR = 2 * kWave;   // threads per slot: 2 G waves / G
+  for (int r = r0; r < 2 * (A + L); r += NR) {
+    const int e = r >> 1, qi = 2 * (e < A ? L + e : e - A) + (r & 1);
+    const float val = b.pos[(size_t)r * B + wg];
+    Q0[qi] = val;
+    if (MIRROR && e >= A) Q1[qi] = val;
+  }
+  for (int r = r0; r < 2 * A; r += NR) V0[r] = b.vel[(size_t)r * B + wg];
+}
+
+// World.step of one agent lane (core.py:117-169): (me, v) is agent i's P(t-1) on entry and its P(t) on return.  The
+// decoded action force (ux, uy) comes first, then the partners CPW[0 .. A) -- the agent block of the positions the
+// step reads -- in ascending order (Q9).  The caller loads (me, v) and stores them where its plan keeps P(t).
+__device__ __forceinline__ void duo_step_lane(const WideDesc &d, const float2 *CPW, int A, int i, bool have, bool contacts,
+                                              float ux, float uy, float2 &me, float2 &v) {
+  float2 f = make_float2(ux, uy);
+  if (contacts) {
+    const float ri = d.a_size, rfar = ri + kFarX * d.cmargin, reach = rfar + ri;
+    for (int kb = 0; kb < A; kb += 32) {
+      const int n = min(A - kb, 32);
+      unsigned near = near_mask32<true>(CPW, nullptr, kb, n, me, rfar, reach * reach);
+      if (i >= kb && i < kb + 32) near &= ~(0x80000000u >> (i - kb));   // not against itself
+      if (!have) near = 0u;
+      f = add_contacts<true>(near, CPW, nullptr, kb, me, ri, d, f);
+    }
+  }
+  integrate_one(me.x, me.y, v.x, v.y, f.x, f.y, d.a_inv_mass, d.a_max_speed, d.damp, d.dt);
+}
+
+// Rows [first, last) of one world by one wave.  rows16: D = 6 N floats go out as 16-byte pieces when N is even, as 8-byte
+// pieces when N is odd (rows then start 8 bytes off).
+// (nontemporal rows.  Agent scope (sc1) wins by 0.5-2.5 us when ONE buffer is written launch after launch (profiles/
+//  r3_ab_logs.txt sessions 24-25: 66.6-67.0 vs 67.0-69.2 us fast buffers, 79-82 vs 82-84 slow ones) and loses 0.7 us under
+//  the env's ping-pong of two output sets (session 30: 68.0-69.1 vs 67.3-67.8) -- the protocol that counts)
+__device__ __forceinline__ void duo_emit(const float2 *Q, const float2 *V, int A, int L, int D, float *obs_w, size_t rowlen,
+                                         int lane, int first, int last, bool rows16, bool rows_nt) {
+  if (rows16 && rows_nt) emit_rows_fast<kRowsNt>(Q, V, A, L, D, obs_w, rowlen, lane, first, last);
+  else if (rows16) emit_rows_fast<kRowsPlain>(Q, V, A, L, D, obs_w, rowlen, lane, first, last);
+  else        emit_rows<2>(Q, V, A, L, D, obs_w, rowlen, lane, first, last);
+}
+
 // (register budget: the occupancy caps that were tried -- amdgpu_waves_per_eu forcing 8 or 4 waves per SIMD at 71 VGPRs:
 //  85.6-86.5 / 87.5-88.3 vs 84.5-85.0 us; capping at 6 or 4 at today's 46 VGPRs: 76.8-80.3 / 76.3-83.0 vs 76.1-80.2 --
 //  are inside the run-to-run spread of the row stream)
@@ -777,7 +891,7 @@ __global__ void __launch_bounds__(2 * G * kWave)
 k_duo(const WideDesc d, const MpeBuffers b, const size_t B) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NT = 2 * G * kWave;
-  const int A = d.A, L = d.L, E = A + L, D = d.D;
+  const int A = d.A, L = d.L, D = d.D;
   const int tid = threadIdx.x, lane = tid & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = wave >> 1, role = wave & 1;
@@ -786,31 +900,21 @@ k_duo(const WideDesc d, const MpeBuffers b, const size_t B) {
   auto Vs = [&](int sl) { return reinterpret_cast<float2 *>(smem + (size_t)sl * cv.slot_bytes + cv.v); };
   auto Us = [&](int sl) { return reinterpret_cast<float2 *>(smem + (size_t)sl * cv.slot_bytes + cv.u); };
   auto Rs = [&](int sl) { return reinterpret_cast<float *>(smem + (size_t)sl * cv.slot_bytes + cv.araw); };
-  // worlds of this workgroup: G consecutive ones; XCD = blockIdx % 8 (hardware round-robin), and the 32 / G groups
-  // that share a 128-byte line of every state row (32 consecutive worlds) sit on ONE XCD
-  constexpr unsigned GPL = 32 / G;
-  const unsigned x = blockIdx.x, xcd = x & 7u, slot = x >> 3;
-  const size_t w0 = (size_t)(((slot / GPL) * 8u + xcd) * GPL + (slot % GPL)) * G;
-  if (w0 >= B) return;   // workgroup-uniform
-  const int nvalid = (B - w0) < (size_t)G ? (int)(B - w0) : G;
+  size_t w0;
+  int nvalid;
+  if (!duo_world0<G>(B, w0, nvalid)) return;
   const bool movable = d.a_flags & kMovable, collide = d.a_flags & kCollide;
 #ifdef MPE_STRESS_DELAY_WAVE   // test build (libmpe_hip_stress.so): one wave of every workgroup starts ~30 us late
   if (wave == 1)
     for (int k = 0; k < 10; ++k) __builtin_amdgcn_s_sleep(127);
 #endif
 
-  // ---- cooperative stage: thread -> (row, world slot); the slots of a row are adjacent lanes and adjacent bytes ----
+  // ---- cooperative stage: the state, and the moves the same way (thread -> (row, world slot)) ----------------------
   {
     const int gg = tid % G, r0 = tid / G;
     if (gg < nvalid) {
       const size_t wg = w0 + gg;
-      float *const Qf = reinterpret_cast<float *>(Qs(gg));
-      for (int r = r0; r < 2 * E; r += NT / G) {
-        const int e = r >> 1;
-        Qf[2 * (e < A ? L + e : e - A) + (r & 1)] = b.pos[(size_t)r * B + wg];
-      }
-      float *const Vf = reinterpret_cast<float *>(Vs(gg));
-      for (int r = r0; r < 2 * A; r += NT / G) Vf[r] = b.vel[(size_t)r * B + wg];
+      duo_stage_state<false>(b, B, A, L, wg, r0, reinterpret_cast<float *>(Qs(gg)), nullptr, reinterpret_cast<float *>(Vs(gg)));
       if (b.ids) {
         for (int i = r0; i < A; i += NT / G) {
           float ux, uy;
@@ -852,27 +956,7 @@ k_duo(const WideDesc d, const MpeBuffers b, const size_t B) {
       ux = u.x;
       uy = u.y;
     }
-    float ax = ux, ay = uy;   // action force first, then the partners in ascending order (Q9)
-    if (collide && !(MPE_DUO_ABLATE & 2)) {
-      const float ri = d.a_size, rfar = ri + kFarX * d.cmargin, reach = rfar + ri;
-      const float2 *const CPW = Q + L;
-      for (int kb = 0; kb < A; kb += 32) {
-        const int n = min(A - kb, 32);
-        unsigned near = near_mask32<true>(CPW, nullptr, kb, n, me, rfar, reach * reach);
-        if (i >= kb && i < kb + 32) near &= ~(0x80000000u >> (i - kb));   // not against itself
-        if (!have) near = 0u;
-        while (near) {   // pass 2: the partners within reach only, ascending
-          const int j = __clz((int)near);
-          near &= ~(0x80000000u >> j);
-          const float2 pj = CPW[kb + j];
-          float gx, gy;
-          contact_force(me.x - pj.x, me.y - pj.y, ri + ri, d.cforce, d.cmargin, d.cmargin_inv, gx, gy);
-          ax = gx + ax;
-          ay = gy + ay;
-        }
-      }
-    }
-    integrate_one(me.x, me.y, v.x, v.y, ax, ay, d.a_inv_mass, d.a_max_speed, d.damp, d.dt);
+    duo_step_lane(d, Q + L, A, i, have, collide && !(MPE_DUO_ABLATE & 2), ux, uy, me, v);
     wave_sync();   // every lane has read the old positions
     if (have) {
       Q[L + i] = me;
@@ -881,21 +965,15 @@ k_duo(const WideDesc d, const MpeBuffers b, const size_t B) {
   }
   __syncthreads();
 
-  // rows of D = 6 N floats: 16-byte pieces when N is even, 8-byte pieces when N is odd (rows then start 8 bytes off)
   const bool rows16 = (D & 3) == 0 && ((B * (size_t)D) & 3) == 0;
   if (role == 0) {
-    if (wok && !(MPE_DUO_ABLATE & 4)) {
-      // (nontemporal rows.  Agent scope (sc1) wins by 0.5-2.5 us when ONE buffer is written launch after launch (profiles/
-      //  r3_ab_logs.txt sessions 24-25: 66.6-67.0 vs 67.0-69.2 us fast buffers, 79-82 vs 82-84 slow ones) and loses 0.7 us under
-      //  the env's ping-pong of two output sets (session 30: 68.0-69.1 vs 67.3-67.8) -- the protocol that counts)
-      if (rows16 && d.rows_nt) emit_rows_fast<kRowsNt>(Q, V, A, L, D, b.obs + w * (size_t)D, (size_t)B * D, lane, 0, split);
-      else if (rows16) emit_rows_fast<kRowsPlain>(Q, V, A, L, D, b.obs + w * (size_t)D, (size_t)B * D, lane, 0, split);
-      else        emit_rows<2>(Q, V, A, L, D, b.obs + w * (size_t)D, (size_t)B * D, lane, 0, split);
-    }
+    if (wok && !(MPE_DUO_ABLATE & 4)) duo_emit(Q, V, A, L, D, b.obs + w * (size_t)D, (size_t)B * D, lane, 0, split, rows16, d.rows_nt);
     return;
   }
 
   // ---- odd waves: the new state back to HBM by rows (thread -> (row, world slot)), reward, the other rows --------
+  // (not shared with k_duo_roll's write-back: here the G odd waves store the agent rows only, position and velocity in one
+  //  loop; there every thread stores every entity once, after the last step)
   if (movable) {
     const int t1 = g * kWave + lane;   // 0 .. 64 G - 1 over the G odd waves
     const int gg = t1 % G;
@@ -910,11 +988,7 @@ k_duo(const WideDesc d, const MpeBuffers b, const size_t B) {
   }
   if (!wok) return;
   if (!(MPE_DUO_ABLATE & 1)) duo_reward(d, b, Q, A, L, B, w, (size_t)lane * B + w, lane, collide);
-  if (!(MPE_DUO_ABLATE & 4)) {
-    if (rows16 && d.rows_nt) emit_rows_fast<kRowsNt>(Q, V, A, L, D, b.obs + w * (size_t)D, (size_t)B * D, lane, split, A);
-    else if (rows16) emit_rows_fast<kRowsPlain>(Q, V, A, L, D, b.obs + w * (size_t)D, (size_t)B * D, lane, split, A);
-    else        emit_rows<2>(Q, V, A, L, D, b.obs + w * (size_t)D, (size_t)B * D, lane, split, A);
-  }
+  if (!(MPE_DUO_ABLATE & 4)) duo_emit(Q, V, A, L, D, b.obs + w * (size_t)D, (size_t)B * D, lane, split, A, rows16, d.rows_nt);
 }
 
 // ---- the fused T-step rollout on k_duo's plan (mpe_rollout_random, spread 32 < N <= 64, identical agents) ---------
@@ -936,7 +1010,7 @@ __host__ __device__ inline DuoRollCarve duo_roll_carve(int A, int L) {
   return c;
 }
 
-// (128 VGPRs, no scratch; forcing the budget of 5 / 6 / 8 waves per SIMD measured 71.1-72.3 / 72.6-73.2 / 74.5-75.7 vs
+// (110 VGPRs, no scratch; forcing the budget of 5 / 6 / 8 waves per SIMD measured 71.1-72.3 / 72.6-73.2 / 74.5-75.7 vs
 //  70.5-72.3 us per step in the same box)
 template <int G>
 __global__ void __launch_bounds__(2 * G * kWave)
@@ -951,28 +1025,17 @@ k_duo_roll(const WideDesc d, const MpeBuffers b, const size_t B, const RollArgs 
   // (offsets by arithmetic, not by indexing an array with the step parity: that would live in scratch memory)
   auto Qs = [&](int sl, int k) { return reinterpret_cast<float2 *>(smem + (size_t)sl * cv.slot_bytes + (size_t)k * cv.q_bytes); };
   auto Vs = [&](int sl, int k) { return reinterpret_cast<float2 *>(smem + (size_t)sl * cv.slot_bytes + cv.v0 + (size_t)k * cv.v_bytes); };
-  constexpr unsigned GPL = 32 / G;
-  const unsigned x = blockIdx.x, xcd = x & 7u, slot = x >> 3;
-  const size_t w0 = (size_t)(((slot / GPL) * 8u + xcd) * GPL + (slot % GPL)) * G;
-  if (w0 >= B) return;   // workgroup-uniform
-  const int nvalid = (B - w0) < (size_t)G ? (int)(B - w0) : G;
+  size_t w0;
+  int nvalid;
+  if (!duo_world0<G>(B, w0, nvalid)) return;
   const bool movable = d.a_flags & kMovable, collide = d.a_flags & kCollide;
 
-  // ---- stage P(-1) into buffer 0 (landmarks into both buffers), cooperatively: thread -> (row, world slot) ----------
+  // ---- stage P(-1) into buffer 0 (landmarks into both buffers), cooperatively --------------------------------------
   {
     const int gg = tid % G, r0 = tid / G;
-    if (gg < nvalid) {
-      const size_t wg = w0 + gg;
-      float *const Q0 = reinterpret_cast<float *>(Qs(gg, 0)), *const Q1 = reinterpret_cast<float *>(Qs(gg, 1));
-      for (int r = r0; r < 2 * E; r += NT / G) {
-        const int e = r >> 1, qi = 2 * (e < A ? L + e : e - A) + (r & 1);
-        const float val = b.pos[(size_t)r * B + wg];
-        Q0[qi] = val;
-        if (e >= A) Q1[qi] = val;
-      }
-      float *const V0 = reinterpret_cast<float *>(Vs(gg, 0));
-      for (int r = r0; r < 2 * A; r += NT / G) V0[r] = b.vel[(size_t)r * B + wg];
-    }
+    if (gg < nvalid)
+      duo_stage_state<true>(b, B, A, L, w0 + gg, r0, reinterpret_cast<float *>(Qs(gg, 0)), reinterpret_cast<float *>(Qs(gg, 1)),
+                            reinterpret_cast<float *>(Vs(gg, 0)));
   }
   __syncthreads();
 
@@ -984,13 +1047,7 @@ k_duo_roll(const WideDesc d, const MpeBuffers b, const size_t B, const RollArgs 
   const size_t obs_stride = ra.trajectory ? (size_t)A * D * B : 0;
   const size_t row_stride = ra.trajectory ? (size_t)A * B : 0;
   const bool rows16 = (D & 3) == 0 && ((B * (size_t)D) & 3) == 0 && ((obs_stride & 3) == 0);
-  int countdown = -1;    // resets fall on global steps that are multiples of episode_len
-  uint64_t ep = 0;
-  if (ra.episode_len > 0) {
-    const uint64_t len = (uint64_t)ra.episode_len, r = ra.step0 % len;
-    countdown = r == 0 ? 0 : (int)(len - r);
-    ep = ra.step0 / len + (r ? 1 : 0);
-  }
+  EpisodeClock clk(ra, true);
 
   for (int t = 0; t < T; ++t) {
 #ifdef MPE_STRESS_DELAY_WAVE   // test build: every step one wave lags ~7 us -- alternately a row/reward wave and a physics wave --
@@ -999,26 +1056,21 @@ k_duo_roll(const WideDesc d, const MpeBuffers b, const size_t B, const RollArgs 
 #endif
     const int cur = t & 1, nxt = cur ^ 1;            // P(t-1) in buffer cur, P(t) goes to buffer nxt
     const uint64_t gt = ra.step0 + (uint64_t)t;
-    const bool reset_now = countdown == 0;           // uniform over the grid
-    if (countdown >= 0) countdown = reset_now ? ra.episode_len - 1 : countdown - 1;
-    if (reset_now) {
+    if (clk.tick(ra)) {   // uniform over the grid
       __syncthreads();   // the rows of step t-1 (read from buffer cur by both waves) are out
       if (role == 0 && wok) {   // reset_world, as mpe_reset draws it for episode ep
         if (lane < A) {
-          float px, py;
-          reset_draw(ra.seed, gw, ep, lane, 1.0f, px, py);
-          Qs(g, cur)[L + lane] = make_float2(px, py);
+          Qs(g, cur)[L + lane] = reset_entity(ra, gw, clk.ep, lane, true);
           Vs(g, cur)[lane] = make_float2(0.f, 0.f);
         }
         if (lane < L) {
-          float px, py;
-          reset_draw(ra.seed, gw, ep, A + lane, ra.landmark_range, px, py);
-          Qs(g, cur)[lane] = make_float2(px, py);
-          Qs(g, nxt)[lane] = make_float2(px, py);
+          const float2 p = reset_entity(ra, gw, clk.ep, A + lane, false);
+          Qs(g, cur)[lane] = p;
+          Qs(g, nxt)[lane] = p;
         }
         wave_sync();
       }
-      ++ep;
+      ++clk.ep;
     }
     if (role == 0 && wok) {
       // ---- World.step (core.py:117-169), lane = agent: P(t-1) -> P(t) -----------------------------------------
@@ -1027,35 +1079,9 @@ k_duo_roll(const WideDesc d, const MpeBuffers b, const size_t B, const RollArgs 
       const int i = have ? lane : 0;
       float2 me = Qc[L + i], v = Vs(g, cur)[i];
       if (movable) {
-        float ux, uy;      // the one-hot row mpe_random_actions would write, decoded -- or the caller's (act_seq)
-        if (ra.act_seq) {
-          fetch_action_seq(ra.act_seq, t, A, B, i, w, d.a_accel, ux, uy);
-        } else {
-          const int m = action_draw(ra.seed, gw, gt, i);
-          ux = ((m == 1 ? 1.f : 0.f) - (m == 2 ? 1.f : 0.f)) * d.a_accel;
-          uy = ((m == 3 ? 1.f : 0.f) - (m == 4 ? 1.f : 0.f)) * d.a_accel;
-        }
-        float ax = ux + 0.f, ay = uy + 0.f;   // action force first, then the partners in ascending order (Q9)
-        if (collide) {
-          const float ri = d.a_size, rfar = ri + kFarX * d.cmargin, reach = rfar + ri;
-          const float2 *const CPW = Qc + L;
-          for (int kb = 0; kb < A; kb += 32) {
-            const int n = min(A - kb, 32);
-            unsigned near = near_mask32<true>(CPW, nullptr, kb, n, me, rfar, reach * reach);
-            if (i >= kb && i < kb + 32) near &= ~(0x80000000u >> (i - kb));   // not against itself
-            if (!have) near = 0u;
-            while (near) {   // pass 2: the partners within reach only, ascending
-              const int j = __clz((int)near);
-              near &= ~(0x80000000u >> j);
-              const float2 pj = CPW[kb + j];
-              float gx, gy;
-              contact_force(me.x - pj.x, me.y - pj.y, ri + ri, d.cforce, d.cmargin, d.cmargin_inv, gx, gy);
-              ax = gx + ax;
-              ay = gy + ay;
-            }
-          }
-        }
-        integrate_one(me.x, me.y, v.x, v.y, ax, ay, d.a_inv_mass, d.a_max_speed, d.damp, d.dt);
+        float ux, uy;
+        rollout_move(ra, t, A, B, i, w, gw, gt, d.a_accel, ux, uy);
+        duo_step_lane(d, Qc + L, A, i, have, collide, ux, uy, me, v);
       }
       if (have) {   // the other buffer: nobody reads it before the barrier below
         Qs(g, nxt)[L + i] = me;
@@ -1067,16 +1093,10 @@ k_duo_roll(const WideDesc d, const MpeBuffers b, const size_t B, const RollArgs 
     const float2 *const Q = Qs(g, nxt), *const V = Vs(g, nxt);
     float *const obs_w = b.obs + (size_t)t * obs_stride + w * (size_t)D;
     if (role == 0) {
-      if (wok) {
-        if (rows16 && d.rows_nt) emit_rows_fast<kRowsNt>(Q, V, A, L, D, obs_w, (size_t)B * D, lane, 0, split);
-        else if (rows16) emit_rows_fast<kRowsPlain>(Q, V, A, L, D, obs_w, (size_t)B * D, lane, 0, split);
-        else        emit_rows<2>(Q, V, A, L, D, obs_w, (size_t)B * D, lane, 0, split);
-      }
+      if (wok) duo_emit(Q, V, A, L, D, obs_w, (size_t)B * D, lane, 0, split, rows16, d.rows_nt);
     } else if (wok) {
       duo_reward(d, b, Q, A, L, B, w, (size_t)t * row_stride + (size_t)lane * B + w, lane, collide);
-      if (rows16 && d.rows_nt) emit_rows_fast<kRowsNt>(Q, V, A, L, D, obs_w, (size_t)B * D, lane, split, A);
-      else if (rows16) emit_rows_fast<kRowsPlain>(Q, V, A, L, D, obs_w, (size_t)B * D, lane, split, A);
-      else        emit_rows<2>(Q, V, A, L, D, obs_w, (size_t)B * D, lane, split, A);
+      duo_emit(Q, V, A, L, D, obs_w, (size_t)B * D, lane, split, A, rows16, d.rows_nt);
     }
   }
 
@@ -1188,9 +1208,7 @@ k_multi(const WideDesc d, const MpeBuffers b, const size_t B, const unsigned n_g
 
   const size_t per_wg = (size_t)kWavesPerWg * WPW;
   for (unsigned x = blockIdx.x; x < n_groups_padded; x += gridDim.x) {
-    const unsigned xcd = x & 7u, sl8 = x >> 3;
-    const unsigned g = ((sl8 >> 3) << 6) | (xcd << 3) | (sl8 & 7u);
-    const size_t wb = (size_t)g * per_wg + (size_t)wave * WPW;   // first world of this wave
+    const size_t wb = (size_t)xcd_group(x) * per_wg + (size_t)wave * WPW;   // first world of this wave
     if (wb >= B) continue;                                       // wave-uniform
     const size_t w = wb + slot;
     const bool ok = w < B;                                       // this lane's slot holds a world
@@ -1219,43 +1237,22 @@ k_multi(const WideDesc d, const MpeBuffers b, const size_t B, const unsigned n_g
 
     const bool have = ok && a < A;
     const uint64_t gw = ra.world_offset + w;   // global world number (RNG streams)
-    int countdown = -1;    // resets fall on global steps that are multiples of episode_len (as in k_wave<ROLL>)
-    uint64_t ep = 0;
-    if (ROLL && ra.episode_len > 0) {
-      const uint64_t len = (uint64_t)ra.episode_len, r = ra.step0 % len;
-      countdown = r == 0 ? 0 : (int)(len - r);
-      ep = ra.step0 / len + (r ? 1 : 0);
-    }
+    EpisodeClock clk(ra, ROLL);
     for (int t = 0; t < T; ++t) {
     if (ROLL) {
       const uint64_t gt = ra.step0 + (uint64_t)t;
-      const bool reset_now = countdown == 0;   // wave-uniform
-      if (countdown >= 0) countdown = reset_now ? ra.episode_len - 1 : countdown - 1;
-      if (reset_now) {  // reset_world, as mpe_reset draws it for episode ep
+      if (clk.tick(ra)) {  // wave-uniform: reset_world, as mpe_reset draws it for episode ep
         if (ok && a < A) {
-          float x, y;
-          reset_draw(ra.seed, gw, ep, a, 1.0f, x, y);
-          Q[L + a] = make_float2(x, y);
+          Q[L + a] = reset_entity(ra, gw, clk.ep, a, true);
           V[a] = make_float2(0.f, 0.f);
         }
-        if (ok && a < L) {
-          float x, y;
-          reset_draw(ra.seed, gw, ep, A + a, ra.landmark_range, x, y);
-          Q[a] = make_float2(x, y);
-        }
-        ++ep;
+        if (ok && a < L) Q[a] = reset_entity(ra, gw, clk.ep, A + a, false);
+        ++clk.ep;
       }
-      if (have) {   // the one-hot row mpe_random_actions would write, decoded -- or the caller's (act_seq)
-        const float sens = aconst[a].z;
+      if (have) {
         float ux, uy;
-        if (ra.act_seq) {
-          fetch_action_seq(ra.act_seq, t, A, B, a, w, sens, ux, uy);
-        } else {
-          const int m = action_draw(ra.seed, gw, gt, a);
-          ux = ((m == 1 ? 1.f : 0.f) - (m == 2 ? 1.f : 0.f)) * sens;
-          uy = ((m == 3 ? 1.f : 0.f) - (m == 4 ? 1.f : 0.f)) * sens;
-        }
-        U[a] = make_float2(ux + 0.f, uy + 0.f);
+        rollout_move(ra, t, A, B, a, w, gw, gt, aconst[a].z, ux, uy);
+        U[a] = make_float2(ux, uy);
       }
       wave_sync();
       if (!agents_only) {  // the partner list follows the positions
@@ -1280,6 +1277,7 @@ k_multi(const WideDesc d, const MpeBuffers b, const size_t B, const unsigned n_g
         unsigned near = near_mask32<false>(CPW, csz, kb, n, me, rfar, 0.f);
         if (self_rank >= kb && self_rank < kb + 32) near &= ~(0x80000000u >> (self_rank - kb));
         if (!pushes) near = 0u;
+        // (add_contacts<false>, as this kernel's own copy: the call changed k_multi's code and time, profiles/wide_refactor_ab.txt)
         while (near) {
           const int j = __clz((int)near);
           near &= ~(0x80000000u >> j);
