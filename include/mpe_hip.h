@@ -385,6 +385,55 @@ int mpe_actor_supported(const MpeActorSet *set, int64_t B);
 int mpe_actor_act(const MpeActorSet *set, const float *const *obs_ptrs, int64_t B, uint64_t step, int64_t world_offset,
                   float *moves, float *utter, int32_t *ids, float *logp, float *logits, void *stream);
 
+/* ---- the replay buffer: the last S steps of all B worlds in device memory (csrc/mpe_replay.hip) ------------------------------
+ * What an off-policy learner keeps beside the loop above: a ring of transitions (obs, action, reward, done, next obs) of every
+ * agent, filled by ONE launch per step (mpe_replay_push) and sampled by ONE launch per minibatch (mpe_replay_sample), the same
+ * transition indices for every agent.  Both launches read the write position from DEVICE memory (`head`, the number of steps
+ * pushed so far) and the push advances it itself, so a captured push moves to the next slot at every graph replay.
+ * Ring layout (slot s = step number % S; the per-slot layouts are those of the step outputs above):
+ *   obs, next_obs  [S][sum D_i * B]    agent i's block at floats off[i] * B .. off[i + 1] * B of a slot, [B][D_i] row-major
+ *   act            [S][A][B][5]        the move rows applied at the step
+ *   utter          [S][A][B][dim_c]    the utterance rows (NULL when dim_c = 0)
+ *   rew            [S][A][B]           done [S][A][B] uint8
+ * The draw: sample k of draw number d is Philox4x32-10 with key (seed lo, seed hi) on the counter
+ *   ((k >> 1) lo, (k >> 1) hi ^ d hi, 0, MPE_STREAM_REPLAY ^ d lo);
+ * an even k takes the words (x, y), an odd k (z, w); u = first << 32 | second; with n_valid = min(head, S) * B the transition
+ * is j = (u * n_valid) >> 64: slot j / B, world j % B (uniform with replacement over the valid part of the ring).            */
+#define MPE_REPLAY_MAX_AGENTS 16
+#define MPE_REPLAY_MAX_WIDTH 4096               /* widest observation row D_i                                               */
+#define MPE_STREAM_REPLAY 0x5245504Cu           /* "REPL": the sample draws                                                 */
+typedef struct MpeReplay {
+  int32_t n_agents;                               /* 1..MPE_REPLAY_MAX_AGENTS                                              */
+  int32_t dim_c;                                  /* utterance width, 0 if nobody speaks                                   */
+  int64_t B;                                      /* worlds                                                                */
+  int64_t S;                                      /* slots (steps kept); S * B < 2^40                                      */
+  int32_t obs_width[MPE_REPLAY_MAX_AGENTS];       /* D_i                                                                   */
+  uint8_t movable[MPE_REPLAY_MAX_AGENTS];         /* agent i has a move head: 5 columns of a joint row                     */
+  uint8_t speaks[MPE_REPLAY_MAX_AGENTS];          /* agent i has an utterance head: dim_c columns of a joint row           */
+  float *obs, *next_obs, *act, *utter, *rew;      /* the ring (device memory, layouts above)                               */
+  uint8_t *done;
+  int64_t *head;                                  /* device: steps pushed so far; read by both launches, advanced by push  */
+  uint32_t *ticket;                               /* device: the push's block counter, zero between launches               */
+  uint64_t seed;                                  /* key of the sample draws                                               */
+} MpeReplay;
+size_t mpe_sizeof_replay(void);
+/* 1 if the ring can be pushed to and sampled, 0 if it is valid but out of scope (more than MPE_REPLAY_MAX_AGENTS agents, a row
+ * wider than MPE_REPLAY_MAX_WIDTH: named in mpe_last_error), < 0 if invalid.  Pointers are not looked at.                   */
+int mpe_replay_supported(const MpeReplay *replay);
+/* One step's transitions into slot head % S, then head += 1 (on the device, by the launch's last block).  obs_ptrs,
+ * next_obs_ptrs: HOST arrays of n_agents device pointers, agent i's [B][D_i] rows before and after the step; moves [A][B][5];
+ * utter [A][B][dim_c] (required when an agent speaks, else ignored); rew [A][B]; done [A][B], one byte each.               */
+int mpe_replay_push(const MpeReplay *replay, const float *const *obs_ptrs, const float *const *next_obs_ptrs, const float *moves,
+                    const float *utter, const float *rew, const uint8_t *done, void *stream);
+/* M transitions drawn as above with draw number `draw`, every field of every agent gathered for them: idx int64 [M]; obs,
+ * next_obs flat [sum D_i * M], agent i's block at floats off[i] * M, [M][D_i] row-major; act [A][M][5]; utter [A][M][dim_c]
+ * (required when dim_c > 0); rew [A][M]; done [A][M] uint8.  joint, joint_next: both NULL, or [M][sum D_i + sum n_act_i] -- all
+ * agents' observations in agent order, then per agent its move row (if movable) and its utterance row (if it speaks),
+ * n_act_i = 5 * movable_i + dim_c * speaks_i -- and [M][sum D_i] of the next observations.  Nothing is written while the
+ * ring is empty (head = 0).                                                                                                */
+int mpe_replay_sample(const MpeReplay *replay, int64_t M, uint64_t draw, int64_t *idx, float *obs, float *next_obs, float *act,
+                      float *utter, float *rew, uint8_t *done, float *joint, float *joint_next, void *stream);
+
 /* ---- composable output stage: a USER scenario's observation / reward as a row program ---------------------------------
  * The reference's plug-in promise (README "Creating new environments", scenario.py:4-10) is that new scenarios are the
  * normal use; every shipped observation is a concatenation of a few segment kinds and every shipped reward an ordered

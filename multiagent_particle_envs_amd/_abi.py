@@ -81,6 +81,18 @@ class MpeActorSet(C.Structure):        # include/mpe_hip.h: the actors of one mp
                 ("dim_c", C.c_int32), ("reserved_", C.c_int32)]
 
 
+MPE_REPLAY_MAX_AGENTS, MPE_REPLAY_MAX_WIDTH = 16, 4096
+MPE_STREAM_REPLAY = 0x5245504C
+
+
+class MpeReplay(C.Structure):          # include/mpe_hip.h: the replay ring of mpe_replay_push / mpe_replay_sample
+    _fields_ = [("n_agents", C.c_int32), ("dim_c", C.c_int32), ("B", C.c_int64), ("S", C.c_int64),
+                ("obs_width", C.c_int32 * MPE_REPLAY_MAX_AGENTS), ("movable", C.c_uint8 * MPE_REPLAY_MAX_AGENTS),
+                ("speaks", C.c_uint8 * MPE_REPLAY_MAX_AGENTS), ("obs", C.c_void_p), ("next_obs", C.c_void_p), ("act", C.c_void_p),
+                ("utter", C.c_void_p), ("rew", C.c_void_p), ("done", C.c_void_p), ("head", C.c_void_p), ("ticket", C.c_void_p),
+                ("seed", C.c_uint64)]
+
+
 class MpeBuffers(C.Structure):
     _fields_ = [
         ("pos", C.c_void_p), ("vel", C.c_void_p), ("act", C.c_void_p), ("ids", C.c_void_p), ("u", C.c_void_p),
@@ -175,6 +187,12 @@ EXPORTS = {
     "mpe_actor_supported": (C.c_int, [C.POINTER(MpeActorSet), C.c_int64]),
     "mpe_actor_act": (C.c_int, [C.POINTER(MpeActorSet), C.POINTER(C.c_void_p), C.c_int64, C.c_uint64, C.c_int64, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mpe_sizeof_replay": (C.c_size_t, []),
+    "mpe_replay_supported": (C.c_int, [C.POINTER(MpeReplay)]),
+    "mpe_replay_push": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mpe_replay_sample": (C.c_int, [C.POINTER(MpeReplay), C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -205,7 +223,7 @@ def lib():
     if handle.mpe_sizeof_desc() != C.sizeof(MpeScenarioDesc) or handle.mpe_sizeof_buffers() != C.sizeof(MpeBuffers) or \
             handle.mpe_sizeof_row_program() != C.sizeof(MpeRowProgram) or handle.mpe_sizeof_step_server() != C.sizeof(MpeStepServer) or \
             handle.mpe_sizeof_render_args() != C.sizeof(MpeRenderArgs) or handle.mpe_sizeof_policy() != C.sizeof(MpePolicy) or \
-            handle.mpe_sizeof_actor_set() != C.sizeof(MpeActorSet):
+            handle.mpe_sizeof_actor_set() != C.sizeof(MpeActorSet) or handle.mpe_sizeof_replay() != C.sizeof(MpeReplay):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")
     _lib = handle
     return _lib

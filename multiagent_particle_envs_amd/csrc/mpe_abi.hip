@@ -1280,4 +1280,123 @@ int mpe_actor_act(const MpeActorSet *s, const float *const *obs_ptrs, int64_t B,
   return hip_result(mpe::launch_actor(a, static_cast<hipStream_t>(stream)), what);
 }
 
+// ---- the replay buffer (mpe_replay.hip) ---------------------------------------------------------------------------------------
+size_t mpe_sizeof_replay(void) { return sizeof(MpeReplay); }
+static int check_replay(const MpeReplay *r, const char *what, bool pointers) {
+  if (!r) return fail(MPE_EINVAL, "%s: replay is NULL", what);
+  if (r->n_agents < 1) return fail(MPE_EINVAL, "%s: n_agents = %d (need at least 1)", what, r->n_agents);
+  if (r->n_agents > MPE_REPLAY_MAX_AGENTS)
+    return fail(MPE_EUNSUPPORTED, "%s: %d agents in one replay buffer (at most MPE_REPLAY_MAX_AGENTS = %d)", what, r->n_agents,
+                MPE_REPLAY_MAX_AGENTS);
+  if (r->S < 1) return fail(MPE_EINVAL, "%s: S = %lld slots (need at least 1)", what, (long long)r->S);
+  if (r->B < 1) return fail(MPE_EINVAL, "%s: B = %lld worlds (need at least 1)", what, (long long)r->B);
+  if (r->B > 0x7fffffffll || r->S > (((int64_t)1 << 40) - 1) / r->B)
+    return fail(MPE_EINVAL, "%s: S * B = %lld * %lld transitions (need S * B < 2^40 and B < 2^31)", what, (long long)r->S,
+                (long long)r->B);
+  if (r->dim_c < 0) return fail(MPE_EINVAL, "%s: dim_c = %d", what, r->dim_c);
+  if (r->dim_c > MPE_REPLAY_MAX_WIDTH)
+    return fail(MPE_EUNSUPPORTED, "%s: dim_c = %d > MPE_REPLAY_MAX_WIDTH = %d", what, r->dim_c, MPE_REPLAY_MAX_WIDTH);
+  for (int i = 0; i < r->n_agents; ++i) {
+    if (r->obs_width[i] < 1) return fail(MPE_EINVAL, "%s: agent %d: obs_width %d", what, i, r->obs_width[i]);
+    if (r->obs_width[i] > MPE_REPLAY_MAX_WIDTH)
+      return fail(MPE_EUNSUPPORTED, "%s: agent %d: obs_width %d > MPE_REPLAY_MAX_WIDTH = %d", what, i, r->obs_width[i],
+                  MPE_REPLAY_MAX_WIDTH);
+    if (r->speaks[i] && r->dim_c == 0) return fail(MPE_EINVAL, "%s: agent %d speaks but dim_c = 0", what, i);
+    if (!r->movable[i] && !r->speaks[i]) return fail(MPE_EINVAL, "%s: agent %d neither moves nor speaks: it has no head", what, i);
+  }
+  if (!pointers) return 0;
+  const struct { const void *p; const char *name; bool need; unsigned align; } ring[] = {
+      {r->obs, "obs", true, 4}, {r->next_obs, "next_obs", true, 4}, {r->act, "act", true, 4}, {r->utter, "utter", r->dim_c > 0, 4},
+      {r->rew, "rew", true, 4}, {r->done, "done", true, 1}, {r->head, "head", true, 8}, {r->ticket, "ticket", true, 4}};
+  for (const auto &f : ring) {
+    if (f.need && !f.p) return fail(MPE_EINVAL, "%s: replay->%s is NULL", what, f.name);
+    if (f.need && ((uintptr_t)f.p & (f.align - 1))) return fail(MPE_EINVAL, "%s: replay->%s is not %u-byte aligned", what, f.name, f.align);
+  }
+  return 0;
+}
+int mpe_replay_supported(const MpeReplay *r) {
+  const int rc = check_replay(r, "mpe_replay_supported", false);
+  if (rc) return rc == MPE_EUNSUPPORTED ? 0 : rc;
+  return 1;
+}
+int mpe_replay_push(const MpeReplay *r, const float *const *obs_ptrs, const float *const *next_obs_ptrs, const float *moves,
+                    const float *utter, const float *rew, const uint8_t *done, void *stream) {
+  const char *what = "mpe_replay_push";
+  if (int rc = check_replay(r, what, true)) return rc;
+  if (!obs_ptrs) return fail(MPE_EINVAL, "%s: obs_ptrs is NULL", what);
+  if (!next_obs_ptrs) return fail(MPE_EINVAL, "%s: next_obs_ptrs is NULL", what);
+  if (!moves || ((uintptr_t)moves & 3)) return fail(MPE_EINVAL, "%s: moves is NULL or not 4-byte aligned", what);
+  if (!rew || ((uintptr_t)rew & 3)) return fail(MPE_EINVAL, "%s: rew is NULL or not 4-byte aligned", what);
+  if (!done) return fail(MPE_EINVAL, "%s: done is NULL", what);
+  bool speaker = false;
+  for (int i = 0; i < r->n_agents; ++i) speaker = speaker || r->speaks[i];
+  if (speaker && !utter) return fail(MPE_EINVAL, "%s: utter is NULL but an agent speaks", what);
+  if (utter && ((uintptr_t)utter & 3)) return fail(MPE_EINVAL, "%s: utter is not 4-byte aligned", what);
+  mpe::ReplayPushArgs a;
+  std::memset(&a, 0, sizeof(a));
+  const uint64_t A = (uint64_t)r->n_agents, B = (uint64_t)r->B;
+  uint64_t d_sum = 0;
+  for (int i = 0; i < r->n_agents; ++i) d_sum += (uint64_t)r->obs_width[i];
+  int n = 0;
+  for (int half = 0; half < 2; ++half) {
+    const float *const *ptrs = half ? next_obs_ptrs : obs_ptrs;
+    uint64_t off = 0;
+    for (int i = 0; i < r->n_agents; ++i) {
+      if (!ptrs[i] || ((uintptr_t)ptrs[i] & 3))
+        return fail(MPE_EINVAL, "%s: %s[%d] is NULL or not 4-byte aligned", what, half ? "next_obs_ptrs" : "obs_ptrs", i);
+      a.seg[n++] = {ptrs[i], (half ? r->next_obs : r->obs) + off * B, d_sum * B * 4, (uint64_t)r->obs_width[i] * B * 4, 0, 0};
+      off += (uint64_t)r->obs_width[i];
+    }
+  }
+  a.seg[n++] = {moves, r->act, A * B * MPE_ACTION_DIM * 4, A * B * MPE_ACTION_DIM * 4, 0, 0};
+  if (r->dim_c > 0 && utter) a.seg[n++] = {utter, r->utter, A * B * (uint64_t)r->dim_c * 4, A * B * (uint64_t)r->dim_c * 4, 0, 0};
+  a.seg[n++] = {rew, r->rew, A * B * 4, A * B * 4, 0, 0};
+  a.seg[n++] = {done, r->done, A * B, A * B, 0, 0};
+  a.n_seg = n;
+  a.S = (uint64_t)r->S;
+  a.head = r->head;
+  a.ticket = r->ticket;
+  mpe::replay_push_plan(a);
+  if (a.n_blocks == 0) return fail(MPE_EUNSUPPORTED, "%s: one step of this ring is more than 2^31 blocks of copies", what);
+  return hip_result(mpe::launch_replay_push(a, static_cast<hipStream_t>(stream)), what);
+}
+int mpe_replay_sample(const MpeReplay *r, int64_t M, uint64_t draw, int64_t *idx, float *obs, float *next_obs, float *act,
+                      float *utter, float *rew, uint8_t *done, float *joint, float *joint_next, void *stream) {
+  const char *what = "mpe_replay_sample";
+  if (int rc = check_replay(r, what, true)) return rc;
+  if (M < 1) return fail(MPE_EINVAL, "%s: M = %lld samples (need at least 1)", what, (long long)M);
+  if (M > ((int64_t)1 << 31) - 1) return fail(MPE_EUNSUPPORTED, "%s: M = %lld samples (at most 2^31 - 1 per launch)", what, (long long)M);
+  const struct { const void *p; const char *name; bool need; unsigned align; } out[] = {
+      {idx, "idx", true, 8}, {obs, "obs", true, 4}, {next_obs, "next_obs", true, 4}, {act, "act", true, 4},
+      {utter, "utter", r->dim_c > 0, 4}, {rew, "rew", true, 4}, {done, "done", true, 1}, {joint, "joint", false, 4},
+      {joint_next, "joint_next", false, 4}};
+  for (const auto &f : out) {
+    if (f.need && !f.p) return fail(MPE_EINVAL, "%s: %s is NULL", what, f.name);
+    if (f.p && ((uintptr_t)f.p & (f.align - 1))) return fail(MPE_EINVAL, "%s: %s is not %u-byte aligned", what, f.name, f.align);
+  }
+  if (!joint != !joint_next) return fail(MPE_EINVAL, "%s: joint and joint_next are both NULL or both given", what);
+  mpe::ReplaySampleArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.obs = r->obs, a.next_obs = r->next_obs, a.act = r->act, a.utter = r->utter, a.rew = r->rew, a.done = r->done, a.head = r->head;
+  a.idx = idx, a.o_obs = obs, a.o_next = next_obs, a.o_act = act, a.o_utter = utter, a.o_rew = rew, a.o_done = done;
+  a.joint = joint, a.joint_next = joint_next;
+  a.seed = r->seed, a.draw = draw, a.B = (uint64_t)r->B, a.S = (uint64_t)r->S, a.M = (uint64_t)M;
+  a.A = r->n_agents, a.dim_c = r->dim_c;
+  for (int i = 0; i < r->n_agents; ++i) {
+    a.off[i + 1] = a.off[i] + r->obs_width[i];
+    a.magic[i] = mpe::replay_magic((uint32_t)r->obs_width[i]);
+  }
+  a.d_sum = a.off[r->n_agents];
+  a.magic_c = mpe::replay_magic((uint32_t)r->dim_c);
+  int col = a.d_sum;
+  for (int i = 0; i < r->n_agents; ++i) {
+    a.col_move[i] = r->movable[i] ? col : -1;
+    col += r->movable[i] ? MPE_ACTION_DIM : 0;
+    a.col_utter[i] = r->speaks[i] ? col : -1;
+    col += r->speaks[i] ? r->dim_c : 0;
+  }
+  a.joint_width = col;
+  return hip_result(mpe::launch_replay_sample(a, static_cast<hipStream_t>(stream)), what);
+}
+
 }  // extern "C"

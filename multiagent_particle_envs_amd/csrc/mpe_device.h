@@ -376,6 +376,19 @@ __host__ __device__ inline uint32_t policy_comm_bits(uint64_t seed, uint64_t b, 
   return (i & 3) == 0 ? o.x : (i & 3) == 1 ? o.y : (i & 3) == 2 ? o.z : o.w;
 }
 
+// The replay buffer's sample k of draw number d (mpe_replay_sample): 64 uniform bits, two samples per Philox block.
+constexpr uint32_t kStreamReplay = 0x5245504cu;  // "REPL"
+static_assert(kStreamReplay == MPE_STREAM_REPLAY, "include/mpe_hip.h names the replay stream");
+__host__ __device__ inline uint64_t replay_bits(uint64_t seed, uint64_t k, uint64_t d) {
+  U4 c;
+  c.x = (uint32_t)(k >> 1);
+  c.y = (uint32_t)(k >> 33) ^ (uint32_t)(d >> 32);
+  c.z = 0u;
+  c.w = kStreamReplay ^ (uint32_t)d;
+  const U4 o = philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return (k & 1) ? ((uint64_t)o.z << 32 | o.w) : ((uint64_t)o.x << 32 | o.y);
+}
+
 // ---- actors: the activation and the head rule, shared by k_split<POL> and mpe_policy.hip ----------------
 // Tanh is 1 - 2 / (exp(2x) + 1) on v_exp_f32 (absolute error < 2e-7).
 __device__ __forceinline__ float pol_act(float x, bool tnh) {

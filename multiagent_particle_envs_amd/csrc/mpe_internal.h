@@ -112,6 +112,48 @@ struct ActorArgs {
 };
 int launch_actor(const ActorArgs &a, hipStream_t stream);
 
+// the replay buffer (mpe_replay.hip): both launches' arguments, checked and filled by the caller (mpe_replay_push / _sample)
+constexpr int kReplayMaxSegs = 2 * MPE_REPLAY_MAX_AGENTS + 4;     // obs and next obs per agent, act, utter, rew, done
+constexpr int kReplayPushThreads = 256, kReplayPushUnroll = 4;    // a block copies 1024 units of its segment
+constexpr int kReplayTile = 64;                                   // samples per block of k_replay_sample
+struct ReplaySeg {
+  const void *src;       // the step's tensor
+  void *dst;             // slot 0 of the ring's field (+ the agent's block)
+  uint64_t stride;       // bytes from slot to slot
+  uint64_t nbytes;
+  uint32_t first;        // first block of the segment (replay_push_plan)
+  uint32_t unit;         // 16 / 4 / 1: the widest access under which src and dst stay congruent at EVERY slot
+};
+struct ReplayPushArgs {
+  ReplaySeg seg[kReplayMaxSegs];
+  int32_t n_seg;
+  uint32_t n_blocks;     // set by replay_push_plan
+  uint64_t S;
+  int64_t *head;
+  uint32_t *ticket;
+};
+// seg[i].unit / first and n_blocks from src, dst, stride and nbytes: the grid follows the byte count
+void replay_push_plan(ReplayPushArgs &a);
+int launch_replay_push(const ReplayPushArgs &a, hipStream_t stream);
+struct ReplaySampleArgs {
+  const float *obs, *next_obs, *act, *utter, *rew;     // the ring
+  const uint8_t *done;
+  const int64_t *head;
+  int64_t *idx;
+  float *o_obs, *o_next, *o_act, *o_utter, *o_rew;
+  uint8_t *o_done;
+  float *joint, *joint_next;                           // both or neither
+  uint64_t seed, draw, B, S, M;
+  int32_t A, dim_c;
+  int32_t d_sum, joint_width;                          // sum D_i; d_sum + sum n_act_i
+  int32_t off[MPE_REPLAY_MAX_AGENTS + 1];              // prefix sums of D_i
+  uint32_t magic[MPE_REPLAY_MAX_AGENTS];               // ceil(2^32 / D_i) (0 for D_i = 1): e / D_i = umulhi(e, magic) for e * D_i < 2^32
+  uint32_t magic_c;                                    // the same for dim_c
+  int32_t col_move[MPE_REPLAY_MAX_AGENTS], col_utter[MPE_REPLAY_MAX_AGENTS];   // first joint column of the head, -1: none
+};
+uint32_t replay_magic(uint32_t w);
+int launch_replay_sample(const ReplaySampleArgs &a, hipStream_t stream);
+
 // the composable output stage (mpe_rows.hip): kernel-side header of an MpeRowProgram
 constexpr int kRowSlots = 8;
 constexpr int kRowPicks = MPE_MAX_CHOICES;

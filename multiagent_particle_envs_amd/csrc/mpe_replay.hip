@@ -1,0 +1,187 @@
+// The replay buffer (mpe_replay_push / mpe_replay_sample): a ring of the last S steps' transitions of all B worlds
+// in device memory.  k_replay_push streams one step's tensors into slot head % S and advances `head` on the device;
+// k_replay_sample draws M transitions (Philox, replay_bits in mpe_device.h) and gathers every field of every agent for them.
+// Both only move data: every output is bit-equal to its source.
+#include "mpe_internal.h"
+
+namespace mpe {
+namespace {
+
+constexpr int kPT = kReplayPushThreads, kPU = kReplayPushUnroll;
+
+// Units [lo, hi) of V from s to d: kPU independent loads per lane in flight, then their stores; consecutive lanes on consecutive
+// units.
+template <typename V>
+__device__ __forceinline__ void copy_units(const uint8_t *__restrict__ s, uint8_t *__restrict__ d, uint64_t lo, uint64_t hi) {
+  const V *sv = reinterpret_cast<const V *>(s);
+  V *dv = reinterpret_cast<V *>(d);
+  static_assert(kPU == 4, "four named registers (an array here is promoted to LDS)");
+  const uint64_t i0 = lo + threadIdx.x, i1 = i0 + kPT, i2 = i1 + kPT, i3 = i2 + kPT;
+  V v0{}, v1{}, v2{}, v3{};
+  if (i0 < hi) v0 = sv[i0];
+  if (i1 < hi) v1 = sv[i1];
+  if (i2 < hi) v2 = sv[i2];
+  if (i3 < hi) v3 = sv[i3];
+  if (i0 < hi) dv[i0] = v0;
+  if (i1 < hi) dv[i1] = v1;
+  if (i2 < hi) dv[i2] = v2;
+  if (i3 < hi) dv[i3] = v3;
+}
+
+// One block = 1024 units of one segment (a field of one agent, or a whole [A][B][..] field).  A segment whose source and ring
+// slot are congruent mod 16 at every slot moves in 16-byte units, with the bytes in front of the first 16-byte boundary of the
+// destination and behind the last whole unit peeled (by the segment's first block); congruent mod 4 only (an odd B leaves agent
+// blocks and slots at 4-byte alignment): dwords; else (the done bytes of an odd A * B): bytes.
+__global__ __launch_bounds__(kReplayPushThreads) void k_replay_push(const ReplayPushArgs a) {
+  const uint32_t blk = blockIdx.x;
+  int s = 0;
+  for (int i = 1; i < a.n_seg; ++i) s = blk >= a.seg[i].first ? i : s;
+  const uint64_t head = (uint64_t)*a.head;
+  const uint64_t slot = head % a.S;
+  const uint8_t *src = static_cast<const uint8_t *>(a.seg[s].src);
+  uint8_t *dst = static_cast<uint8_t *>(a.seg[s].dst) + slot * a.seg[s].stride;
+  const uint64_t nbytes = a.seg[s].nbytes;
+  const uint32_t unit = a.seg[s].unit, c = blk - a.seg[s].first;
+  uint64_t lead = (uint64_t)(-(intptr_t)reinterpret_cast<uintptr_t>(dst)) & (unit - 1);
+  lead = lead < nbytes ? lead : nbytes;
+  const uint64_t units = (nbytes - lead) / unit;
+  const uint64_t lo = (uint64_t)c * (kPT * kPU), hi = lo + kPT * kPU < units ? lo + kPT * kPU : units;
+  if (lo < hi) {
+    if (unit == 16) copy_units<uint4>(src + lead, dst + lead, lo, hi);
+    else if (unit == 4) copy_units<uint32_t>(src + lead, dst + lead, lo, hi);
+    else copy_units<uint8_t>(src, dst, lo, hi);
+  }
+  if (c == 0) {      // the peeled ends: fewer than 16 bytes each
+    const uint64_t back = lead + units * unit;
+    const uint32_t t = threadIdx.x;
+    if (t < lead) dst[t] = src[t];
+    if (t >= 32 && back + (t - 32) < nbytes) dst[back + (t - 32)] = src[back + (t - 32)];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {      // the ticket: the block that takes the last one has seen every block read `head`
+    const uint32_t n = atomicAdd(a.ticket, 1u);
+    if (n == gridDim.x - 1) {
+      *a.head = (int64_t)(head + 1);
+      atomicExch(a.ticket, 0u);
+    }
+  }
+}
+
+// Rows of W floats gathered for the n samples of a tile: lanes run over the tile's n * W OUTPUT floats (stores fully coalesced,
+// loads coalesced within a gathered row), four independent elements per lane in flight; element e is row e / W = umulhi(e, magic).
+// d2: the same values into rows of a joint tensor (row stride w2), or nullptr.
+__device__ __forceinline__ void gather_rows(const float *__restrict__ src, uint64_t slot_stride, uint32_t W, uint32_t magic,
+                                            float *__restrict__ d1, float *__restrict__ d2, uint32_t w2, const uint32_t *s_slot,
+                                            const uint32_t *s_world, uint32_t n) {
+  const uint32_t total = n * W;
+  for (uint32_t e0 = threadIdx.x; e0 < total; e0 += 4 * 256) {
+    float v[4];
+    uint32_t r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t e = e0 + k * 256;
+      if (e < total) {
+        r[k] = magic ? __umulhi(e, magic) : e;
+        const uint32_t col = e - r[k] * W;
+        v[k] = src[(uint64_t)s_slot[r[k]] * slot_stride + (uint64_t)s_world[r[k]] * W + col];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t e = e0 + k * 256;
+      if (e < total) {
+        d1[e] = v[k];
+        if (d2) d2[(uint64_t)r[k] * w2 + (e - r[k] * W)] = v[k];
+      }
+    }
+  }
+}
+
+// grid (tiles of kReplayTile samples, jobs): job y gathers one field of one agent -- y in [0, A): obs of agent y; [A, 2A): next obs;
+// [2A, 3A): move rows; then, with dim_c > 0, A utterance jobs; the last job is rew and done of every agent.  Every block draws its
+// tile's indices into LDS itself (32 Philox blocks); the blocks of job 0 write idx.
+__global__ __launch_bounds__(256) void k_replay_sample(const ReplaySampleArgs a) {
+  __shared__ uint32_t s_slot[kReplayTile], s_world[kReplayTile];
+  const uint64_t head = (uint64_t)*a.head;
+  const uint64_t n_valid = (head < a.S ? head : a.S) * a.B;
+  if (n_valid == 0) return;
+  const uint64_t m0 = (uint64_t)blockIdx.x * kReplayTile;
+  const uint32_t n = a.M - m0 < (uint64_t)kReplayTile ? (uint32_t)(a.M - m0) : (uint32_t)kReplayTile;
+  const uint32_t t = threadIdx.x, job = blockIdx.y;
+  if (t < n) {
+    const uint64_t u = replay_bits(a.seed, m0 + t, a.draw);
+    const uint64_t j = __umul64hi(u, n_valid);
+    const uint64_t sl = j / a.B;
+    s_slot[t] = (uint32_t)sl;
+    s_world[t] = (uint32_t)(j - sl * a.B);
+    if (job == 0) a.idx[m0 + t] = (int64_t)j;
+  }
+  __syncthreads();
+  const uint32_t A = (uint32_t)a.A;
+  const uint64_t B = a.B, M = a.M;
+  if (job < 2 * A) {
+    const bool nx = job >= A;
+    const uint32_t i = nx ? job - A : job;
+    const uint32_t W = (uint32_t)(a.off[i + 1] - a.off[i]);
+    const float *src = (nx ? a.next_obs : a.obs) + (uint64_t)a.off[i] * B;
+    float *d1 = (nx ? a.o_next : a.o_obs) + (uint64_t)a.off[i] * M + m0 * W;
+    float *jt = nx ? a.joint_next : a.joint;
+    const uint32_t w2 = nx ? (uint32_t)a.d_sum : (uint32_t)a.joint_width;
+    gather_rows(src, (uint64_t)a.d_sum * B, W, a.magic[i], d1, jt ? jt + m0 * w2 + a.off[i] : nullptr, w2, s_slot, s_world, n);
+  } else if (job < 3 * A) {
+    const uint32_t i = job - 2 * A, W = MPE_ACTION_DIM;
+    float *jt = a.joint && a.col_move[i] >= 0 ? a.joint + m0 * (uint32_t)a.joint_width + a.col_move[i] : nullptr;
+    gather_rows(a.act + (uint64_t)i * B * W, (uint64_t)A * B * W, W, 0x33333334u, a.o_act + ((uint64_t)i * M + m0) * W, jt,
+                (uint32_t)a.joint_width, s_slot, s_world, n);
+  } else if (a.dim_c > 0 && job < 4 * A) {
+    const uint32_t i = job - 3 * A, W = (uint32_t)a.dim_c;
+    float *jt = a.joint && a.col_utter[i] >= 0 ? a.joint + m0 * (uint32_t)a.joint_width + a.col_utter[i] : nullptr;
+    gather_rows(a.utter + (uint64_t)i * B * W, (uint64_t)A * B * W, W, a.magic_c, a.o_utter + ((uint64_t)i * M + m0) * W, jt,
+                (uint32_t)a.joint_width, s_slot, s_world, n);
+  } else {
+    for (uint32_t e = t; e < A * kReplayTile; e += 256) {      // lanes over a tile's samples of one agent
+      const uint32_t i = e / kReplayTile, r = e % kReplayTile;
+      if (r < n) {
+        const uint64_t from = ((uint64_t)s_slot[r] * A + i) * B + s_world[r];
+        a.o_rew[(uint64_t)i * M + m0 + r] = a.rew[from];
+        a.o_done[(uint64_t)i * M + m0 + r] = a.done[from];
+      }
+    }
+  }
+}
+
+}  // namespace
+
+uint32_t replay_magic(uint32_t w) { return w < 2 ? 0u : (uint32_t)((((uint64_t)1 << 32) + w - 1) / w); }
+static_assert((((uint64_t)1 << 32) + MPE_ACTION_DIM - 1) / MPE_ACTION_DIM == 0x33333334u, "the move rows' reciprocal");
+static_assert((uint64_t)kReplayTile * MPE_REPLAY_MAX_WIDTH * MPE_REPLAY_MAX_WIDTH < ((uint64_t)1 << 32),
+              "umulhi(e, magic) is e / W for every element of a tile");
+
+void replay_push_plan(ReplayPushArgs &a) {
+  uint64_t blocks = 0;
+  for (int i = 0; i < a.n_seg; ++i) {
+    ReplaySeg &g = a.seg[i];
+    const uintptr_t apart = reinterpret_cast<uintptr_t>(g.src) - reinterpret_cast<uintptr_t>(g.dst);
+    g.unit = ((apart | g.stride) & 15) == 0 ? 16 : ((apart | g.stride) & 3) == 0 ? 4 : 1;
+    g.first = (uint32_t)blocks;
+    const uint64_t units = g.nbytes / g.unit, per = (uint64_t)kReplayPushThreads * kReplayPushUnroll;
+    blocks += units ? (units + per - 1) / per : 1;
+  }
+  a.n_blocks = blocks > 0x7fffffffull ? 0u : (uint32_t)blocks;
+}
+
+int launch_replay_push(const ReplayPushArgs &a, hipStream_t stream) {
+  if (a.n_blocks == 0) return (int)hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(k_replay_push, dim3(a.n_blocks), dim3(kReplayPushThreads), 0, stream, a);
+  return (int)hipGetLastError();
+}
+
+int launch_replay_sample(const ReplaySampleArgs &a, hipStream_t stream) {
+  const uint64_t tiles = (a.M + kReplayTile - 1) / kReplayTile;
+  const unsigned jobs = (unsigned)((a.dim_c > 0 ? 4 : 3) * a.A + 1);
+  if (tiles == 0 || tiles > 0x7fffffffull) return (int)hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(k_replay_sample, dim3((unsigned)tiles, jobs), dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+
+}  // namespace mpe

@@ -268,8 +268,14 @@ class PolicyLoop(object):
             if env.episode_step is not None:
                 env.episode_step.fill_(self.t % self.episode_len)
 
-    def step(self, traj=None, k=0):
-        """One step of the loop at global step self.t -> env.step's outputs."""
+    def _replay_check(self, replay):
+        from .replay import ReplayBuffer
+        if not isinstance(replay, ReplayBuffer) or replay.env is not self.env:
+            raise _abi.MpeError("PolicyLoop: replay is a ReplayBuffer(env, steps) built for this loop's env")
+
+    def step(self, traj=None, k=0, replay=None):
+        """One step of the loop at global step self.t -> env.step's outputs.  replay: a ReplayBuffer that takes the step's
+        transition (the observation decided on, the action applied, env.step's outputs) with one more launch."""
         env, pi = self.env, self.pi
         if self.episode_len and self.t % self.episode_len == 0:
             self.obs_n = self.device_reset(self.t // self.episode_len)
@@ -280,6 +286,11 @@ class PolicyLoop(object):
         else:
             action = pi.act(self.obs_n, self.t)
         out = env.step(action)
+        if replay is not None:
+            # the env double-buffers its output sets, so the step wrote beside the observation it was decided on
+            if any(a.data_ptr() == b.data_ptr() for a, b in zip(self.obs_n, out[0])):
+                raise _abi.MpeError("PolicyLoop: env.step overwrote the observation the action was chosen on; nothing was pushed")
+            replay.push(self.obs_n, action, out[0], out[1], out[2])
         self.obs_n = out[0]
         if traj is not None:
             o = env._sets[env._flip]
@@ -291,25 +302,33 @@ class PolicyLoop(object):
         self.t += 1
         return out
 
-    def run(self, T, record=True):
-        """T steps.  record: -> a LoopTrajectory (three device copies per step); False: -> the last step's env.step outputs."""
+    def run(self, T, record=True, replay=None):
+        """T steps.  record: -> a LoopTrajectory (three device copies per step); False: -> the last step's env.step outputs.
+        replay: every step's transition is pushed to that ReplayBuffer (one launch per step)."""
         _step_many_env_check(self.env)
+        if replay is not None:
+            self._replay_check(replay)
         traj = LoopTrajectory(self.env, self.pi, int(T)) if record else None
         out = None
         for k in range(int(T)):
-            out = self.step(traj, k)
+            out = self.step(traj, k, replay)
         self._mark_stale()
         return traj if record else out
 
-    def capture(self, T):
+    def capture(self, T, replay=None):
         """The next T steps (from self.t, the current state) as ONE HIP graph: a straight line of kernels -- reset, observe, act,
         step -- with nothing recorded.  -> an object whose replay() runs them and advances this loop's step count by T; the
         draw keys and episode numbers are those of the captured steps (a replay repeats them: capture a multiple of episode_len
         steps from an episode start for a periodic rollout, as RandomRollout.capture).  The weights are frozen for the capture
         (freeze() again and re-capture after an update).  Two warm-up steps really run in front of the capture; the state and the
-        step count are put back."""
+        step count are put back.  replay: every captured step pushes its transition to that ReplayBuffer; the
+        push reads and advances the buffer's device-side step count, so each replay() fills the next T slots (the warm-up steps'
+        pushes are taken back: the count is restored, the two slots they wrote are the first two the graph writes)."""
         _step_many_env_check(self.env)
         env, w, pi = self.env, self.world, self.pi
+        if replay is not None:
+            self._replay_check(replay)
+            replay._alloc()
         if pi._frozen is None:
             pi.freeze()
         g = torch.cuda.CUDAGraph()
@@ -324,8 +343,11 @@ class PolicyLoop(object):
             comm = env._comm.clone() if env._comm is not None else None
             keep = [o.clone() for o in obs0] if obs0 is not None else None
             choice = w.choice_i32.clone() if w.choice_i32 is not None else None
+            head, count = (replay.head.clone(), replay.count) if replay is not None else (None, 0)
             for _ in range(2):      # code objects and allocations outside the capture
-                self.step()
+                self.step(replay=replay)
+            if replay is not None:
+                replay.head.copy_(head)
             w.pos.copy_(pos)
             w._vel_all.copy_(vel)
             if comm is not None:
@@ -339,20 +361,24 @@ class PolicyLoop(object):
             torch.cuda.synchronize()
             with torch.cuda.graph(g, stream=s):
                 for _ in range(int(T)):
-                    self.step()
+                    self.step(replay=replay)
         torch.cuda.current_stream(w.device).wait_stream(s)
         self.t = t0
-        return _LoopGraph(g, self, int(T), self.obs_n, env._flip)
+        if replay is not None:
+            replay.count = count      # (captured launches have not run: replay() counts them)
+        return _LoopGraph(g, self, int(T), self.obs_n, env._flip, replay)
 
 
 class _LoopGraph(object):
-    def __init__(self, graph, loop, T, obs_n, flip):
-        self.graph, self.loop, self.T, self._obs_n, self._flip = graph, loop, T, obs_n, flip
+    def __init__(self, graph, loop, T, obs_n, flip, replay=None):
+        self.graph, self.loop, self.T, self._obs_n, self._flip, self._replay = graph, loop, T, obs_n, flip, replay
 
     def replay(self):
         loop = self.loop
         self.graph.replay()
         loop.t += self.T
+        if self._replay is not None:
+            self._replay.count += self.T
         loop.obs_n, loop.env._flip = self._obs_n, self._flip
         loop._mark_stale()
         for out in loop.env._sets:

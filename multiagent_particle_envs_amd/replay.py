@@ -1,0 +1,209 @@
+"""A device-resident replay buffer for off-policy learners: `ReplayBuffer` keeps the last S steps' transitions of all B worlds in a
+ring on the device, filled by ONE launch per step (mpe_replay_push) and sampled by ONE launch per minibatch (mpe_replay_sample,
+the same transition indices for every agent); both launches capture into a HIP graph, because the write position lives on the
+device and the push advances it itself.  csrc/mpe_replay.hip, DESIGN.md 2.11.
+
+    buf = ReplayBuffer(env, steps=1024, seed=0)
+    next_obs_n, rew_n, done_n, _ = env.step(action)
+    buf.push(obs_n, action, next_obs_n, rew_n, done_n)
+    batch = buf.sample(1024, joint=True)        # batch.obs_n[i] [M, D_i], batch.act [A,M,5], batch.joint [M, sum D + sum n_act] ...
+    PolicyLoop(env, pi).run(T, replay=buf)      # the closed loop pushes every step itself
+"""
+import ctypes as C
+
+import torch
+
+from . import _abi
+
+
+class ReplayBatch(object):
+    """One minibatch of M transitions, the same for every agent: idx [M] int64 (transition slot * B + world), obs_n / next_obs_n
+    (per agent [M, D_i]), act [A,M,5], utter [A,M,dim_c] or None, rew [A,M], done [A,M] (torch.bool), and with joint=True
+    joint [M, sum D_i + sum n_act_i] (every agent's observation in agent order, then every agent's action row: its move row if
+    it is movable, its utterance row if it speaks) and joint_next [M, sum D_i].  The tensors belong to the buffer."""
+    __slots__ = ("idx", "obs_n", "next_obs_n", "act", "utter", "rew", "done", "joint", "joint_next", "_obs", "_next", "_done_u8")
+
+
+class ReplayBuffer(object):
+    """The last `steps` steps of every world of `env`, on the env's device.  Widths, heads and dim_c are taken from the env as
+    Actors takes them.  Ring tensors (slot = step number % steps; layouts of LoopTrajectory): obs, next_obs [S, sum D_i * B] (agent
+    i's block of a slot at floats off[i] * B, [B, D_i]; obs_n[s][i] / next_obs_n[s][i] are views), act [S,A,B,5], utter
+    [S,A,B,dim_c] or None, rew [S,A,B], done [S,A,B] (torch.bool).  head: the device-side int64 step count both launches read;
+    count: its host mirror."""
+
+    def __init__(self, env, steps, seed=0):
+        w = env.world
+        self.env, self.world = env, w
+        self.S = int(steps)
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.A, self.B = len(w.agents), int(w.batch_size)
+        if self.A > _abi.MPE_REPLAY_MAX_AGENTS:
+            raise _abi.MpeError("ReplayBuffer: %d agents (at most MPE_REPLAY_MAX_AGENTS = %d)" % (self.A, _abi.MPE_REPLAY_MAX_AGENTS))
+        off = getattr(env, "_obs_off", None)
+        if off is None:
+            raise _abi.MpeError("ReplayBuffer: this env has no device-side observation layout (env.fused is False)")
+        if self.S < 1:
+            raise _abi.MpeError("ReplayBuffer: steps = %d (need at least 1)" % self.S)
+        if self.S * self.B >= 2 ** 40:
+            raise _abi.MpeError("ReplayBuffer: steps * worlds = %d * %d transitions (need fewer than 2^40)" % (self.S, self.B))
+        self.off = [int(o) for o in off[:self.A + 1]]
+        self.obs_widths = [self.off[i + 1] - self.off[i] for i in range(self.A)]
+        self.movable = [bool(a.movable) for a in w.agents]
+        self.speaks = [not a.silent for a in w.agents]
+        self.dim_c = int(w.dim_c) if any(self.speaks) else 0
+        self.n_act = [_abi.MPE_ACTION_DIM * m + self.dim_c * s for m, s in zip(self.movable, self.speaks)]
+        for i, n in enumerate(self.n_act):
+            if n < 1:
+                raise _abi.MpeError("ReplayBuffer: agent %d neither moves nor speaks: it has no head" % i)
+        if max(self.obs_widths) > _abi.MPE_REPLAY_MAX_WIDTH:
+            raise _abi.MpeError("ReplayBuffer: an observation row of %d floats (at most MPE_REPLAY_MAX_WIDTH = %d)"
+                                % (max(self.obs_widths), _abi.MPE_REPLAY_MAX_WIDTH))
+        self.joint_width = self.off[-1] + sum(self.n_act)
+        self.count = 0
+        self._draw = 0
+        self._ptrs = {}
+        self._batches = {}
+        self._desc = None
+        self.obs = None
+
+    def _alloc(self):
+        if self.obs is not None:
+            return
+        S, A, B, dev, off = self.S, self.A, self.B, self.world.device, self.off
+        self.obs = torch.zeros((S, off[-1] * B), dtype=torch.float32, device=dev)
+        self.next_obs = torch.zeros((S, off[-1] * B), dtype=torch.float32, device=dev)
+        self.act = torch.zeros((S, A, B, _abi.MPE_ACTION_DIM), dtype=torch.float32, device=dev)
+        self.utter = torch.zeros((S, A, B, self.dim_c), dtype=torch.float32, device=dev) if self.dim_c else None
+        self.rew = torch.zeros((S, A, B), dtype=torch.float32, device=dev)
+        self._done_u8 = torch.zeros((S, A, B), dtype=torch.uint8, device=dev)
+        self.done = self._done_u8.view(torch.bool)
+        self.head = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+
+        def views(flat):
+            return [[flat[s, off[i] * B: off[i + 1] * B].view(B, off[i + 1] - off[i]) for i in range(A)] for s in range(S)]
+        self.obs_n, self.next_obs_n = views(self.obs), views(self.next_obs)
+        d = _abi.MpeReplay()
+        d.n_agents, d.dim_c, d.B, d.S, d.seed = A, self.dim_c, B, S, self.seed
+        for i in range(A):
+            d.obs_width[i], d.movable[i], d.speaks[i] = self.obs_widths[i], int(self.movable[i]), int(self.speaks[i])
+        d.obs, d.next_obs, d.act, d.rew = self.obs.data_ptr(), self.next_obs.data_ptr(), self.act.data_ptr(), self.rew.data_ptr()
+        d.utter = self.utter.data_ptr() if self.utter is not None else None
+        d.done, d.head, d.ticket = self._done_u8.data_ptr(), self.head.data_ptr(), self._ticket.data_ptr()
+        self._desc = d
+
+    def __len__(self):
+        """Valid transitions: min(count, steps) * worlds."""
+        return min(self.count, self.S) * self.B
+
+    # ---- push -------------------------------------------------------------------------------------------------------------------
+    def _rows(self, x, dtype, what):
+        """rew / done as env.step returns them (a list of A [B] rows of one [A,B] tensor) or one [A,B] tensor -> an [A,B] tensor."""
+        A, B = self.A, self.B
+        if torch.is_tensor(x):
+            t = x
+        else:
+            x = list(x)
+            if len(x) != A or not all(torch.is_tensor(r) for r in x):
+                raise _abi.MpeError("ReplayBuffer.push: %s is an [A,B] tensor or a list of %d [B] tensors" % (what, A))
+            r0 = x[0]
+            step = B * r0.element_size()
+            if all(r.dtype == r0.dtype and r.device == r0.device and tuple(r.shape) == (B,) and r.is_contiguous() and
+                   r.data_ptr() == r0.data_ptr() + i * step for i, r in enumerate(x)):
+                t = r0.as_strided((A, B), (B, 1))      # (the rows of one [A,B] tensor, as env.step hands them out: no copy)
+            else:
+                t = torch.stack(x)
+        if t.dtype != dtype or tuple(t.shape) != (A, B) or not t.is_contiguous() or t.device != self.world.device:
+            raise _abi.MpeError("ReplayBuffer.push: %s is [%d, %d] %s on the env's device" % (what, A, B, dtype))
+        return t
+
+    def _obs_check(self, obs_n, what):
+        if len(obs_n) != self.A:
+            raise _abi.MpeError("ReplayBuffer.push: %d %s blocks for %d agents" % (len(obs_n), what, self.A))
+        for i, o in enumerate(obs_n):
+            if not torch.is_tensor(o) or o.dtype != torch.float32 or not o.is_contiguous() or o.device != self.world.device or \
+                    tuple(o.shape) != (self.B, self.obs_widths[i]):
+                raise _abi.MpeError("ReplayBuffer.push: %s[%d] is a contiguous float32 [%d, %d] tensor on the env's device"
+                                    % (what, i, self.B, self.obs_widths[i]))
+
+    def push(self, obs_n, action, next_obs_n, rew, done):
+        """One launch: the step's transitions into slot count % steps.  obs_n: the observations the action was chosen on;
+        action: the [A,B,5] moves or (moves, utterances [A,B,dim_c]) env.step took; next_obs_n, rew, done: what it returned."""
+        self._alloc()
+        pair = type(action) is tuple
+        moves, utter = action if pair else (action, None)
+        key = tuple(o.data_ptr() for o in obs_n) + tuple(o.data_ptr() for o in next_obs_n) + \
+            (moves.data_ptr() if torch.is_tensor(moves) else None, utter.data_ptr() if torch.is_tensor(utter) else None) + \
+            ((rew.data_ptr(),) if torch.is_tensor(rew) else tuple(r.data_ptr() for r in rew)) + \
+            ((done.data_ptr(),) if torch.is_tensor(done) else tuple(r.data_ptr() for r in done))
+        args = self._ptrs.get(key)
+        if args is None:      # checked once per pointer set
+            A, B, dev = self.A, self.B, self.world.device
+            self._obs_check(obs_n, "obs_n")
+            self._obs_check(next_obs_n, "next_obs_n")
+            if not torch.is_tensor(moves) or moves.dtype != torch.float32 or tuple(moves.shape) != (A, B, _abi.MPE_ACTION_DIM) or \
+                    not moves.is_contiguous() or moves.device != dev:
+                raise _abi.MpeError("ReplayBuffer.push: action is a contiguous float32 [%d, %d, 5] device tensor, or (moves, utterances)"
+                                    % (A, B))
+            if self.dim_c:
+                if not torch.is_tensor(utter) or utter.dtype != torch.float32 or tuple(utter.shape) != (A, B, self.dim_c) or \
+                        not utter.is_contiguous() or utter.device != dev:
+                    raise _abi.MpeError("ReplayBuffer.push: agents speak: action is (moves [A,B,5], utterances [%d, %d, %d]), two "
+                                        "contiguous float32 device tensors" % (A, B, self.dim_c))
+            r, d = self._rows(rew, torch.float32, "rew"), self._rows(done, torch.bool, "done")
+            stacked = (not torch.is_tensor(rew) and r.data_ptr() != rew[0].data_ptr()) or \
+                (not torch.is_tensor(done) and d.data_ptr() != done[0].data_ptr())
+            args = ((C.c_void_p * A)(*[o.data_ptr() for o in obs_n]), (C.c_void_p * A)(*[o.data_ptr() for o in next_obs_n]),
+                    moves.data_ptr(), utter.data_ptr() if self.dim_c else None, r, d)
+            if not stacked:      # (rows stacked into a new tensor are re-stacked at every push)
+                if len(self._ptrs) >= 64:
+                    self._ptrs.clear()
+                self._ptrs[key] = args
+        o, n, mv, ut, r, d = args
+        _abi.check(_abi.lib().mpe_replay_push(C.byref(self._desc), o, n, mv, ut, r.data_ptr(), d.data_ptr(),
+                                              _abi.raw_stream(self.world.device)), "mpe_replay_push")
+        self.count += 1
+
+    # ---- sample -----------------------------------------------------------------------------------------------------------------
+    def _batch(self, M, joint):
+        b = self._batches.get((M, joint))
+        if b is not None:
+            return b
+        A, dev, off = self.A, self.world.device, self.off
+        b = ReplayBatch()
+        b.idx = torch.zeros(M, dtype=torch.int64, device=dev)
+        b._obs = torch.zeros(off[-1] * M, dtype=torch.float32, device=dev)
+        b._next = torch.zeros(off[-1] * M, dtype=torch.float32, device=dev)
+        b.obs_n = [b._obs[off[i] * M: off[i + 1] * M].view(M, off[i + 1] - off[i]) for i in range(A)]
+        b.next_obs_n = [b._next[off[i] * M: off[i + 1] * M].view(M, off[i + 1] - off[i]) for i in range(A)]
+        b.act = torch.zeros((A, M, _abi.MPE_ACTION_DIM), dtype=torch.float32, device=dev)
+        b.utter = torch.zeros((A, M, self.dim_c), dtype=torch.float32, device=dev) if self.dim_c else None
+        b.rew = torch.zeros((A, M), dtype=torch.float32, device=dev)
+        b._done_u8 = torch.zeros((A, M), dtype=torch.uint8, device=dev)
+        b.done = b._done_u8.view(torch.bool)
+        b.joint = torch.zeros((M, self.joint_width), dtype=torch.float32, device=dev) if joint else None
+        b.joint_next = torch.zeros((M, off[-1]), dtype=torch.float32, device=dev) if joint else None
+        if len(self._batches) >= 16:
+            self._batches.clear()
+        self._batches[(M, joint)] = b
+        return b
+
+    def sample(self, M, draw=None, joint=False):
+        """One launch: M transitions drawn uniformly with replacement from the valid part of the ring with the draws of (seed,
+        draw) -> a ReplayBatch whose tensors are this buffer's per (M, joint) and are rewritten by the next sample of that shape.
+        draw=None: an internal draw counter, advanced by the call."""
+        M, joint = int(M), bool(joint)
+        if M < 1:
+            raise _abi.MpeError("ReplayBuffer.sample: M = %d samples (need at least 1)" % M)
+        if self.count < 1:
+            raise _abi.MpeError("ReplayBuffer.sample: the buffer is empty (nothing was pushed)")
+        if draw is None:
+            draw = self._draw
+            self._draw += 1
+        b = self._batch(M, joint)
+        _abi.check(_abi.lib().mpe_replay_sample(
+            C.byref(self._desc), M, int(draw) & (2 ** 64 - 1), b.idx.data_ptr(), b._obs.data_ptr(), b._next.data_ptr(), b.act.data_ptr(),
+            b.utter.data_ptr() if b.utter is not None else None, b.rew.data_ptr(), b._done_u8.data_ptr(),
+            b.joint.data_ptr() if joint else None, b.joint_next.data_ptr() if joint else None,
+            _abi.raw_stream(self.world.device)), "mpe_replay_sample")
+        return b
