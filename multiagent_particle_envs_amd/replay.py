@@ -19,8 +19,10 @@ from . import _abi
 class ReplayBatch(object):
     """One minibatch of M transitions, the same for every agent: idx [M] int64 (transition slot * B + world), obs_n / next_obs_n
     (per agent [M, D_i]), act [A,M,5], utter [A,M,dim_c] or None, rew [A,M], done [A,M] (torch.bool), and with joint=True
-    joint [M, sum D_i + sum n_act_i] (every agent's observation in agent order, then every agent's action row: its move row if
-    it is movable, its utterance row if it speaks) and joint_next [M, sum D_i].  The tensors belong to the buffer."""
+    joint [M, sum D_i + sum n_act_i] (every agent's observation in agent order, then the action rows agent by agent: agent i's
+    move row [5] if it is movable, directly followed by its utterance row [dim_c] if it speaks, then agent i + 1's -- for two
+    agents with both heads [obs0 obs1 | move0 utter0 | move1 utter1]) and joint_next [M, sum D_i].  The tensors belong to the
+    buffer."""
     __slots__ = ("idx", "obs_n", "next_obs_n", "act", "utter", "rew", "done", "joint", "joint_next", "_obs", "_next", "_done_u8")
 
 

@@ -29,7 +29,9 @@ def draw_indices(seed, draw, M, n_valid):
 
 
 class NumpyRing(object):
-    """obs / next_obs: per slot a list of [B, D_i]; act [S,A,B,5]; utter [S,A,B,dim_c]; rew [S,A,B]; done [S,A,B] bool."""
+    """obs / next_obs: per slot a list of [B, D_i]; act [S,A,B,5]; utter [S,A,B,dim_c]; rew [S,A,B]; done [S,A,B] bool.  Any S, B,
+    widths and dim_c.  The float fields are stored and gathered through their uint32 views, so every bit pattern (NaN payloads,
+    denormals, -0.0) comes back as it went in; compare them with bits()."""
 
     def __init__(self, S, B, widths, dim_c):
         A = len(widths)
@@ -44,11 +46,13 @@ class NumpyRing(object):
     def push(self, obs_n, moves, utter, next_obs_n, rew, done):
         s = self.count % self.S
         for i in range(self.A):
-            self.obs[s][i][...] = obs_n[i]
-            self.next_obs[s][i][...] = next_obs_n[i]
-        self.act[s], self.rew[s], self.done[s] = moves, rew, done
+            _store(self.obs[s][i], obs_n[i])
+            _store(self.next_obs[s][i], next_obs_n[i])
+        _store(self.act[s], moves)
+        _store(self.rew[s], rew)
+        self.done[s] = done
         if self.dim_c:
-            self.utter[s] = utter
+            _store(self.utter[s], utter)
         self.count += 1
 
     def n_valid(self):
@@ -59,16 +63,28 @@ class NumpyRing(object):
         sl = [j // self.B for j in idx]
         wd = [j % self.B for j in idx]
         A = self.A
-        out = {"obs_n": [np.stack([self.obs[s][i][w] for s, w in zip(sl, wd)]) for i in range(A)],
-               "next_obs_n": [np.stack([self.next_obs[s][i][w] for s, w in zip(sl, wd)]) for i in range(A)],
-               "act": np.stack([self.act[sl, i, wd] for i in range(A)]),
-               "utter": np.stack([self.utter[sl, i, wd] for i in range(A)]),
-               "rew": np.stack([self.rew[sl, i, wd] for i in range(A)]),
+        act, utter, rew = self.act.view(np.uint32), self.utter.view(np.uint32), self.rew.view(np.uint32)
+        out = {"obs_n": [np.stack([self.obs[s][i].view(np.uint32)[w] for s, w in zip(sl, wd)]).view(np.float32) for i in range(A)],
+               "next_obs_n": [np.stack([self.next_obs[s][i].view(np.uint32)[w] for s, w in zip(sl, wd)]).view(np.float32)
+                              for i in range(A)],
+               "act": np.stack([act[sl, i, wd] for i in range(A)]).view(np.float32),
+               "utter": np.stack([utter[sl, i, wd] for i in range(A)]).view(np.float32),
+               "rew": np.stack([rew[sl, i, wd] for i in range(A)]).view(np.float32),
                "done": np.stack([self.done[sl, i, wd] for i in range(A)])}
         return out
 
 
-FIELDS = {"obs": 0, "next_obs": 1, "act": 2, "utter": 3, "rew": 4}
+def _store(dst, src):
+    """float32 -> float32 as 32-bit integers: no float ever passes through an arithmetic unit, a NaN keeps its payload."""
+    dst.view(np.uint32)[...] = np.ascontiguousarray(src, dtype=np.float32).view(np.uint32)
+
+
+def bits(x):
+    """A float32 array (or a torch tensor's .cpu().numpy()) as int32: what np.array_equal compares where the data holds NaNs."""
+    return np.ascontiguousarray(x, dtype=np.float32).view(np.int32)
+
+
+FIELDS = {"obs": 0, "next_obs": 1, "act": 2, "utter": 3, "rew": 4, "done": 5}
 
 
 def coded(t, field, agent, B, cols):
@@ -89,4 +105,64 @@ def coded_step(t, B, widths, dim_c):
     utter = np.stack([coded(t, "utter", i, B, dim_c) for i in range(A)]) if dim_c else np.zeros((A, B, 0), np.float32)
     rew = np.stack([coded(t, "rew", i, B, 1)[:, 0] for i in range(A)])
     done = np.array([[(t + 2 * i + w) % 3 == 0 for w in range(B)] for i in range(A)])
+    return obs, moves, utter, nxt, rew, done
+
+
+ODD = 0x9E3779B1      # an odd multiplier: c -> c * ODD mod 2^32 is a bijection of the 32-bit patterns
+SPECIALS = (0x7FC00001, 0xFFC12345, 0x00000001, 0x80000000, 0x7F800000)      # two NaNs with payloads, a denormal, -0.0, +inf
+
+
+def _counter(t, field, agent, B, cols):
+    """[B, cols] uint64: ((t * 8 + field) * 16 + agent) * 2^20 + world * cols + col -- below 2^32 and different for every
+    (t, field, agent, world, col) while t < 32, agent < 16 and B * cols <= 2^20 (a row of 4096 floats for 256 worlds)."""
+    assert 0 <= t < 32 and 0 <= agent < 16 and B * cols <= 2 ** 20
+    e = np.arange(B * cols, dtype=np.uint64).reshape(B, cols)
+    return np.uint64(((t * 8 + FIELDS[field]) * 16 + agent) << 20) + e
+
+
+def bit_patterns(t, field, agent, B, cols):
+    """[B, cols] float32 whose every element is a different 32-bit pattern: the counter times ODD mod 2^32, so floats of every
+    exponent, NaNs among them."""
+    u = ((_counter(t, field, agent, B, cols) * np.uint64(ODD)) & np.uint64(M32)).astype(np.uint32)
+    return u.view(np.float32)
+
+
+def _force_specials(t, field, blocks):
+    """SPECIALS into five consecutive elements of one step's whole field (its agents' blocks in agent order, as the ring lays
+    them out), ONCE per field: at its very first elements for step 0's obs, and five elements further on for every next
+    (step, field), so that in a ring of few worlds no agent's row is nothing but SPECIALS in every slot and field.  Everything
+    else stays distinct: T steps of a field of n floats hold at least T * (n - 5) different patterns."""
+    n = sum(b.size for b in blocks)
+    k = min(len(SPECIALS), n)
+    start = (5 * (t * 8 + FIELDS[field])) % (n - k + 1)
+    flat = [b.reshape(-1).view(np.uint32) for b in blocks]      # (views: the blocks are contiguous)
+    for j in range(k):
+        e = start + j
+        for f in flat:
+            if e < f.size:
+                f[e] = SPECIALS[j]
+                break
+            e -= f.size
+
+
+def distinct_patterns(arrays):
+    """How many different 32-bit patterns the float32 arrays hold between them."""
+    return len(np.unique(np.concatenate([np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).reshape(-1) for a in arrays])))
+
+
+def bits_step(t, A, B, widths, dim_c):
+    """coded_step without its size limits and with every float a bit pattern of its own, but for five SPECIALS per field
+    (_force_specials): (obs_n, moves [A,B,5], utter [A,B,dim_c], next_obs_n, rew [A,B], done [A,B] bool).  done is bit 13 of the
+    same mixed counter."""
+    assert len(widths) == A
+    obs = [bit_patterns(t, "obs", i, B, widths[i]) for i in range(A)]
+    nxt = [bit_patterns(t, "next_obs", i, B, widths[i]) for i in range(A)]
+    moves = np.stack([bit_patterns(t, "act", i, B, 5) for i in range(A)])
+    utter = np.stack([bit_patterns(t, "utter", i, B, dim_c) for i in range(A)]) if dim_c else np.zeros((A, B, 0), np.float32)
+    rew = np.stack([bit_patterns(t, "rew", i, B, 1)[:, 0] for i in range(A)])
+    for field, blocks in (("obs", obs), ("next_obs", nxt), ("act", [moves]), ("utter", [utter]), ("rew", [rew])):
+        if sum(b.size for b in blocks):
+            _force_specials(t, field, blocks)
+    done = np.stack([(((_counter(t, "done", i, B, 1)[:, 0] * np.uint64(ODD)) >> np.uint64(13)) & np.uint64(1)).astype(bool)
+                     for i in range(A)])
     return obs, moves, utter, nxt, rew, done

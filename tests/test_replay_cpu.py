@@ -5,6 +5,7 @@ import os
 import re
 import subprocess
 
+import numpy as np
 import pytest
 
 import multiagent_particle_envs_amd as mpe
@@ -40,6 +41,37 @@ def test_samples_k_and_k_plus_1_are_the_two_halves_of_one_block():
     assert R.draw_indices(seed, draw, 10, n) == [(((int(h) << 32) | int(l)) * n) >> 64 for h, l in zip(hi, lo)]
     assert R.draw_indices(seed, draw + 1, 10, 2 ** 39) != R.draw_indices(seed, draw, 10, 2 ** 39)
     assert R.draw_indices(seed + 1, draw, 10, 2 ** 39) != R.draw_indices(seed, draw, 10, 2 ** 39)
+
+
+@pytest.mark.parametrize("seed,draw,n_valid,M", [(0xC0FFEE12345, 1, 21, 21000), (9, 0, 1000, 200000), (0x1234567890ABCDEF, 3, 65, 65000)])
+def test_restated_draw_is_flat(seed, draw, n_valid, M):
+    """Chi-square of j = (u * n_valid) >> 64 over its n_valid cells, at most four standard deviations (sqrt(2 dof)) above its mean
+    (dof).  The rule is deterministic: the three values are 18.4 (dof 20, bound 45.3), 1020.0 (dof 999, bound 1177.8) and 54.7
+    (dof 64, bound 109.3)."""
+    counts = np.bincount(np.array(R.draw_indices(seed, draw, M, n_valid), dtype=np.int64), minlength=n_valid)
+    assert len(counts) == n_valid and counts.sum() == M
+    expect = M / n_valid
+    chi2 = float(((counts - expect) ** 2).sum() / expect)
+    dof = n_valid - 1
+    print("chi2 %.1f, dof %d, bound %.1f" % (chi2, dof, dof + 4 * (2 * dof) ** 0.5))
+    assert chi2 <= dof + 4 * (2 * dof) ** 0.5
+
+
+def test_reciprocal_rule_is_division():
+    """gather_rows finds element e's row as umulhi(e, ceil(2^32 / W)) and takes e itself for W = 1 (magic 0): for every row width
+    up to MPE_REPLAY_MAX_WIDTH and every element of a full tile (e < 64 * W) that is e // W.  This tests the RULE the kernel
+    file's static_assert claims, restated in uint64 -- not the compiled code (tests/test_gpu_replay.py runs that)."""
+    tile, top = 64, _abi.MPE_REPLAY_MAX_WIDTH
+    assert tile * top * top < 2 ** 32      # the static_assert's bound
+    e_all = np.arange(tile * top, dtype=np.uint64)
+    rows = np.arange(tile, dtype=np.uint64)
+    for W in range(1, top + 1):
+        magic = 0 if W < 2 else (2 ** 32 + W - 1) // W      # replay_magic
+        assert magic < 2 ** 32
+        e = e_all[:tile * W]
+        r = (e * np.uint64(magic)) >> np.uint64(32) if magic else e
+        assert np.array_equal(r, np.repeat(rows, W)), W      # (np.repeat(rows, W)[e] is e // W)
+    assert np.array_equal(np.repeat(rows, 7), np.arange(tile * 7, dtype=np.uint64) // np.uint64(7))
 
 
 def test_header_names_the_stream_and_the_limits():
