@@ -433,6 +433,77 @@ int mpe_replay_push(const MpeReplay *replay, const float *const *obs_ptrs, const
  * ring is empty (head = 0).                                                                                                */
 int mpe_replay_sample(const MpeReplay *replay, int64_t M, uint64_t draw, int64_t *idx, float *obs, float *next_obs, float *act,
                       float *utter, float *rew, uint8_t *done, float *joint, float *joint_next, void *stream);
+/* mpe_replay_sample's gather with the M transitions READ from idx (device, int64 [M], j = slot * B + world) instead of drawn:
+ * every field of every agent, joint and joint_next written exactly as above, idx itself left alone.  An idx outside
+ * [0, S * B) gathers transition 0; a slot that was never pushed gathers what the ring holds there.  Nothing is written (and idx
+ * is not read) while the ring is empty (head = 0).                                                                          */
+int mpe_replay_gather(const MpeReplay *replay, int64_t M, const int64_t *idx, float *obs, float *next_obs, float *act,
+                      float *utter, float *rew, uint8_t *done, float *joint, float *joint_next, void *stream);
+
+/* ---- prioritized replay: one priority per transition and a sum tree over them (csrc/mpe_replay_prio.hip) --------------------
+ * Proportional prioritized experience replay on the ring above, all on the device, every launch capturable: ONE more launch
+ * per push, two launches per minibatch (the draw, then mpe_replay_gather), 2 + (levels - 1) launches per priority update.
+ * The kernels move floats and add non-negative floats in one fixed order, so every output is a function of the inputs alone.
+ *
+ * THE TREE.  Fan-out MPE_REPLAY_PRIO_FANOUT = 16.  Level 0 is the leaves, one float32 per transition j = slot * B + world (the
+ * j of idx above): n_0 = S * B.  Level l has n_l = ceil(n_{l-1} / 16) nodes; the top level has one node, the total; a ring
+ * with S * B = 1 has level 0 only and its total is that leaf.  ONE device allocation `tree` holds the levels one after
+ * another, each padded to a multiple of 16 floats: level l starts at float off[l], off[0] = 0, off[l + 1] = off[l] +
+ * 16 * ceil(n_l / 16); mpe_replay_prio_layout (host only, no device needed) returns the level count, the offsets and the float
+ * count off[levels] for an n_leaves.  The CALLER zeroes the whole allocation once; the padding stays zero (nothing writes it),
+ * which is what makes children beyond a level's end count as 0.  tree is 16-byte aligned.
+ * A node is the float32 sum of its 16 children in balanced adjacent-pair order: (c0 + c1), (c2 + c3), ..., (c14 + c15), then
+ * pairs of those, four rounds -- the order of a 16-lane xor-shuffle reduction and of `v = v[:, 0::2] + v[:, 1::2]` four times.
+ *
+ * PRIORITIES.  A leaf that was never pushed is exactly 0 and can never be drawn.  A stored priority is clamped to
+ * [MPE_REPLAY_PRIO_MIN = 2^-40, MPE_REPLAY_PRIO_MAX = 2^40]; a NaN is stored as MIN; so no denormal arises and no total
+ * overflows (S * B < 2^40).  pmax is a device float the CALLER sets to 1 once; it holds the largest priority ever stored.
+ *
+ * mpe_replay_prio_push sets the B leaves of slot head % S to *pmax and repairs every ancestor, in one launch.  It reads head and
+ * does NOT advance it: enqueue it BEFORE the mpe_replay_push of the same step (which does), so that a captured pair moves on
+ * at every graph replay.  ticket: a device word, zero between launches (the push's block counter).
+ *
+ * mpe_replay_prio_draw draws M transitions in proportion to their priorities, stratified: sample k takes 24 uniform bits r --
+ * u24[k] & 0xFFFFFF where the optional device array u24 (uint32 [M]) is given, else the top 24 bits of the 64 bits of
+ * mpe_replay_sample's draw rule above (same key, same counter, sample k of draw number `draw`) on the stream constant
+ * MPE_STREAM_REPLAY_PRIO in place of MPE_STREAM_REPLAY -- and, with total the top node,
+ *   x = (float)(((double)k + r * 2^-24) / (double)M * (double)total).
+ * The descent starts at the top node and, per level, walks the node's children c = 0..15 with a sequential float32 running sum
+ * acc (acc = 0; acc = acc + child_c after child c): it takes the FIRST c with x < acc + child_c; if no child qualifies (rounding
+ * can make the pairwise total exceed the sequential sum) the LAST child with child_c > 0 (child 0 if none is positive); then
+ * x = x - (the acc in front of the chosen child) and it goes down into that child.  The node reached at level 0 is idx[k].
+ * Outputs (device): idx int64 [M]; prio float32 [M], the drawn leaves as stored; total float32 [1]; n_valid int64 [1] =
+ * min(head, S) * B.  Nothing is written while head is 0.
+ *
+ * mpe_replay_prio_update: for every k < M leaf idx[k] takes clamp(prio[k]); where several k name one leaf it takes the LARGEST
+ * of their values (whatever it held before).  An idx outside [0, S * B) is ignored, and so is a leaf that is still 0 (never
+ * pushed).  *pmax rises to the largest value stored.  Every ancestor of a named leaf is repaired.  The result depends on the
+ * inputs only, never on scheduling.  idx / prio: device, int64 [M] / float32 [M].
+ *
+ * mpe_replay_prio_repair recomputes every ancestor of the leaves [first, first + count) from the leaves as they are: for a
+ * caller that wrote leaves itself (taking back a push: restore the slot's leaves and pmax, then repair).                   */
+#define MPE_REPLAY_PRIO_FANOUT 16
+#define MPE_REPLAY_PRIO_MAX_LEVELS 11           /* n_leaves < 2^40: at most 11 levels                                        */
+#define MPE_REPLAY_PRIO_MIN 0x1p-40f
+#define MPE_REPLAY_PRIO_MAX 0x1p40f
+#define MPE_STREAM_REPLAY_PRIO 0x5250524Fu      /* "RPRO": the prioritized draw's bits                                       */
+typedef struct MpeReplayPrio {
+  int64_t n_leaves;                               /* S * B of the ring it belongs to                                       */
+  float *tree;                                    /* device, mpe_replay_prio_layout's float count, zeroed once, 16-byte aligned */
+  float *pmax;                                    /* device [1], set to 1 once                                             */
+  uint32_t *ticket;                               /* device [1], zero between launches                                     */
+} MpeReplayPrio;
+size_t mpe_sizeof_replay_prio(void);
+/* Host only.  n_levels: 1..MPE_REPLAY_PRIO_MAX_LEVELS; level_off: MPE_REPLAY_PRIO_MAX_LEVELS + 1 entries, off[0..n_levels]
+ * filled (off[n_levels] = the float count, also written to n_floats), the rest zero.  Any output may be NULL.
+ * MPE_EINVAL unless 1 <= n_leaves < 2^40.                                                                                  */
+int mpe_replay_prio_layout(int64_t n_leaves, int32_t *n_levels, int64_t *level_off, int64_t *n_floats);
+int mpe_replay_prio_push(const MpeReplay *replay, const MpeReplayPrio *prio, void *stream);
+int mpe_replay_prio_draw(const MpeReplay *replay, const MpeReplayPrio *prio, int64_t M, uint64_t draw, const uint32_t *u24,
+                         int64_t *idx, float *prio_out, float *total, int64_t *n_valid, void *stream);
+int mpe_replay_prio_update(const MpeReplay *replay, const MpeReplayPrio *prio, int64_t M, const int64_t *idx,
+                           const float *prio_in, void *stream);
+int mpe_replay_prio_repair(const MpeReplay *replay, const MpeReplayPrio *prio, int64_t first, int64_t count, void *stream);
 
 /* ---- composable output stage: a USER scenario's observation / reward as a row program ---------------------------------
  * The reference's plug-in promise (README "Creating new environments", scenario.py:4-10) is that new scenarios are the

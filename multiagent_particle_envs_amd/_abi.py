@@ -93,6 +93,15 @@ class MpeReplay(C.Structure):          # include/mpe_hip.h: the replay ring of m
                 ("seed", C.c_uint64)]
 
 
+MPE_REPLAY_PRIO_FANOUT, MPE_REPLAY_PRIO_MAX_LEVELS = 16, 11
+MPE_REPLAY_PRIO_MIN, MPE_REPLAY_PRIO_MAX = 2.0 ** -40, 2.0 ** 40
+MPE_STREAM_REPLAY_PRIO = 0x5250524F
+
+
+class MpeReplayPrio(C.Structure):      # include/mpe_hip.h: the priorities and their sum tree (mpe_replay_prio_*)
+    _fields_ = [("n_leaves", C.c_int64), ("tree", C.c_void_p), ("pmax", C.c_void_p), ("ticket", C.c_void_p)]
+
+
 class MpeBuffers(C.Structure):
     _fields_ = [
         ("pos", C.c_void_p), ("vel", C.c_void_p), ("act", C.c_void_p), ("ids", C.c_void_p), ("u", C.c_void_p),
@@ -193,6 +202,15 @@ EXPORTS = {
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "mpe_replay_sample": (C.c_int, [C.POINTER(MpeReplay), C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mpe_replay_gather": (C.c_int, [C.POINTER(MpeReplay), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mpe_sizeof_replay_prio": (C.c_size_t, []),
+    "mpe_replay_prio_layout": (C.c_int, [C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mpe_replay_prio_push": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(MpeReplayPrio), C.c_void_p]),
+    "mpe_replay_prio_draw": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(MpeReplayPrio), C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mpe_replay_prio_update": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(MpeReplayPrio), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mpe_replay_prio_repair": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(MpeReplayPrio), C.c_int64, C.c_int64, C.c_void_p]),
 }
 
 _lib = None
@@ -223,10 +241,18 @@ def lib():
     if handle.mpe_sizeof_desc() != C.sizeof(MpeScenarioDesc) or handle.mpe_sizeof_buffers() != C.sizeof(MpeBuffers) or \
             handle.mpe_sizeof_row_program() != C.sizeof(MpeRowProgram) or handle.mpe_sizeof_step_server() != C.sizeof(MpeStepServer) or \
             handle.mpe_sizeof_render_args() != C.sizeof(MpeRenderArgs) or handle.mpe_sizeof_policy() != C.sizeof(MpePolicy) or \
-            handle.mpe_sizeof_actor_set() != C.sizeof(MpeActorSet) or handle.mpe_sizeof_replay() != C.sizeof(MpeReplay):
+            handle.mpe_sizeof_actor_set() != C.sizeof(MpeActorSet) or handle.mpe_sizeof_replay() != C.sizeof(MpeReplay) or \
+            handle.mpe_sizeof_replay_prio() != C.sizeof(MpeReplayPrio):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")
     _lib = handle
     return _lib
+
+
+def replay_prio_layout(n_leaves):
+    """mpe_replay_prio_layout (host only) -> (level offsets off[0..levels], the float count)."""
+    levels, off, n = C.c_int32(0), (C.c_int64 * (MPE_REPLAY_PRIO_MAX_LEVELS + 1))(), C.c_int64(0)
+    check(lib().mpe_replay_prio_layout(int(n_leaves), C.byref(levels), off, C.byref(n)), "mpe_replay_prio_layout")
+    return list(off[:levels.value + 1]), n.value
 
 
 def raw_stream(device):

@@ -1360,9 +1360,10 @@ int mpe_replay_push(const MpeReplay *r, const float *const *obs_ptrs, const floa
   if (a.n_blocks == 0) return fail(MPE_EUNSUPPORTED, "%s: one step of this ring is more than 2^31 blocks of copies", what);
   return hip_result(mpe::launch_replay_push(a, static_cast<hipStream_t>(stream)), what);
 }
-int mpe_replay_sample(const MpeReplay *r, int64_t M, uint64_t draw, int64_t *idx, float *obs, float *next_obs, float *act,
-                      float *utter, float *rew, uint8_t *done, float *joint, float *joint_next, void *stream) {
-  const char *what = "mpe_replay_sample";
+// mpe_replay_sample (idx written) and mpe_replay_gather (from_idx: idx read) share everything but the source of the indices
+static int replay_sample(const char *what, bool from_idx, const MpeReplay *r, int64_t M, uint64_t draw, int64_t *idx, float *obs,
+                         float *next_obs, float *act, float *utter, float *rew, uint8_t *done, float *joint, float *joint_next,
+                         void *stream) {
   if (int rc = check_replay(r, what, true)) return rc;
   if (M < 1) return fail(MPE_EINVAL, "%s: M = %lld samples (need at least 1)", what, (long long)M);
   if (M > ((int64_t)1 << 31) - 1) return fail(MPE_EUNSUPPORTED, "%s: M = %lld samples (at most 2^31 - 1 per launch)", what, (long long)M);
@@ -1396,7 +1397,96 @@ int mpe_replay_sample(const MpeReplay *r, int64_t M, uint64_t draw, int64_t *idx
     col += r->speaks[i] ? r->dim_c : 0;
   }
   a.joint_width = col;
-  return hip_result(mpe::launch_replay_sample(a, static_cast<hipStream_t>(stream)), what);
+  return hip_result(mpe::launch_replay_sample(a, static_cast<hipStream_t>(stream), from_idx), what);
+}
+int mpe_replay_sample(const MpeReplay *r, int64_t M, uint64_t draw, int64_t *idx, float *obs, float *next_obs, float *act,
+                      float *utter, float *rew, uint8_t *done, float *joint, float *joint_next, void *stream) {
+  return replay_sample("mpe_replay_sample", false, r, M, draw, idx, obs, next_obs, act, utter, rew, done, joint, joint_next, stream);
+}
+int mpe_replay_gather(const MpeReplay *r, int64_t M, const int64_t *idx, float *obs, float *next_obs, float *act, float *utter,
+                      float *rew, uint8_t *done, float *joint, float *joint_next, void *stream) {
+  return replay_sample("mpe_replay_gather", true, r, M, 0, const_cast<int64_t *>(idx), obs, next_obs, act, utter, rew, done, joint,
+                       joint_next, stream);
+}
+
+// ---- prioritized replay (mpe_replay_prio.hip) ---------------------------------------------------------------------------------
+size_t mpe_sizeof_replay_prio(void) { return sizeof(MpeReplayPrio); }
+int mpe_replay_prio_layout(int64_t n_leaves, int32_t *n_levels, int64_t *level_off, int64_t *n_floats) {
+  if (n_leaves < 1 || n_leaves >= ((int64_t)1 << 40))
+    return fail(MPE_EINVAL, "mpe_replay_prio_layout: n_leaves = %lld (need 1 <= n_leaves < 2^40)", (long long)n_leaves);
+  int64_t off[MPE_REPLAY_PRIO_MAX_LEVELS + 1] = {0};
+  int levels = 0;
+  for (int64_t n = n_leaves;; n = (n + 15) / 16) {
+    off[levels + 1] = off[levels] + (n + 15) / 16 * 16;
+    ++levels;
+    if (n == 1) break;
+  }
+  if (n_levels) *n_levels = levels;
+  if (level_off) std::memcpy(level_off, off, sizeof(off));
+  if (n_floats) *n_floats = off[levels];
+  return 0;
+}
+static int prio_args(const MpeReplay *r, const MpeReplayPrio *p, const char *what, mpe::PrioArgs &a) {
+  if (int rc = check_replay(r, what, true)) return rc;
+  if (!p) return fail(MPE_EINVAL, "%s: prio is NULL", what);
+  if (p->n_leaves != r->S * r->B)
+    return fail(MPE_EINVAL, "%s: prio->n_leaves = %lld, the ring has S * B = %lld transitions", what, (long long)p->n_leaves,
+                (long long)(r->S * r->B));
+  if (!p->tree || ((uintptr_t)p->tree & 15)) return fail(MPE_EINVAL, "%s: prio->tree is NULL or not 16-byte aligned", what);
+  if (!p->pmax || ((uintptr_t)p->pmax & 3)) return fail(MPE_EINVAL, "%s: prio->pmax is NULL or not 4-byte aligned", what);
+  if (!p->ticket || ((uintptr_t)p->ticket & 3)) return fail(MPE_EINVAL, "%s: prio->ticket is NULL or not 4-byte aligned", what);
+  std::memset(&a, 0, sizeof(a));
+  int64_t off[MPE_REPLAY_PRIO_MAX_LEVELS + 1];
+  if (int rc = mpe_replay_prio_layout(p->n_leaves, &a.n_levels, off, nullptr)) return rc;
+  for (int l = 0; l <= MPE_REPLAY_PRIO_MAX_LEVELS; ++l) a.off[l] = (uint64_t)off[l];
+  a.tree = p->tree, a.pmax = p->pmax, a.ticket = p->ticket, a.head = r->head;
+  a.S = (uint64_t)r->S, a.B = (uint64_t)r->B, a.n_leaves = (uint64_t)p->n_leaves;
+  return 0;
+}
+int mpe_replay_prio_push(const MpeReplay *r, const MpeReplayPrio *p, void *stream) {
+  const char *what = "mpe_replay_prio_push";
+  mpe::PrioArgs a;
+  if (int rc = prio_args(r, p, what, a)) return rc;
+  return hip_result(mpe::launch_prio_push(a, static_cast<hipStream_t>(stream)), what);
+}
+int mpe_replay_prio_draw(const MpeReplay *r, const MpeReplayPrio *p, int64_t M, uint64_t draw, const uint32_t *u24, int64_t *idx,
+                         float *prio_out, float *total, int64_t *n_valid, void *stream) {
+  const char *what = "mpe_replay_prio_draw";
+  mpe::PrioArgs a;
+  if (int rc = prio_args(r, p, what, a)) return rc;
+  if (M < 1) return fail(MPE_EINVAL, "%s: M = %lld samples (need at least 1)", what, (long long)M);
+  if (M > ((int64_t)1 << 31) - 1) return fail(MPE_EUNSUPPORTED, "%s: M = %lld samples (at most 2^31 - 1 per launch)", what, (long long)M);
+  if (u24 && ((uintptr_t)u24 & 3)) return fail(MPE_EINVAL, "%s: u24 is not 4-byte aligned", what);
+  if (!idx || ((uintptr_t)idx & 7)) return fail(MPE_EINVAL, "%s: idx is NULL or not 8-byte aligned", what);
+  if (!prio_out || ((uintptr_t)prio_out & 3)) return fail(MPE_EINVAL, "%s: prio_out is NULL or not 4-byte aligned", what);
+  if (!total || ((uintptr_t)total & 3)) return fail(MPE_EINVAL, "%s: total is NULL or not 4-byte aligned", what);
+  if (!n_valid || ((uintptr_t)n_valid & 7)) return fail(MPE_EINVAL, "%s: n_valid is NULL or not 8-byte aligned", what);
+  mpe::PrioDrawArgs d;
+  d.u24 = u24, d.idx = idx, d.n_valid = n_valid, d.prio = prio_out, d.total = total;
+  d.seed = r->seed, d.draw = draw, d.M = (uint64_t)M;
+  return hip_result(mpe::launch_prio_draw(a, d, static_cast<hipStream_t>(stream)), what);
+}
+int mpe_replay_prio_update(const MpeReplay *r, const MpeReplayPrio *p, int64_t M, const int64_t *idx, const float *prio_in,
+                           void *stream) {
+  const char *what = "mpe_replay_prio_update";
+  mpe::PrioArgs a;
+  if (int rc = prio_args(r, p, what, a)) return rc;
+  if (M < 1) return fail(MPE_EINVAL, "%s: M = %lld samples (need at least 1)", what, (long long)M);
+  if (M > ((int64_t)1 << 31) - 1) return fail(MPE_EUNSUPPORTED, "%s: M = %lld samples (at most 2^31 - 1 per launch)", what, (long long)M);
+  if (!idx || ((uintptr_t)idx & 7)) return fail(MPE_EINVAL, "%s: idx is NULL or not 8-byte aligned", what);
+  if (!prio_in || ((uintptr_t)prio_in & 3)) return fail(MPE_EINVAL, "%s: prio_in is NULL or not 4-byte aligned", what);
+  mpe::PrioUpdateArgs u;
+  u.idx = idx, u.prio = prio_in, u.M = (uint64_t)M, u.first = 0;
+  return hip_result(mpe::launch_prio_update(a, u, static_cast<hipStream_t>(stream)), what);
+}
+int mpe_replay_prio_repair(const MpeReplay *r, const MpeReplayPrio *p, int64_t first, int64_t count, void *stream) {
+  const char *what = "mpe_replay_prio_repair";
+  mpe::PrioArgs a;
+  if (int rc = prio_args(r, p, what, a)) return rc;
+  if (first < 0 || count < 1 || first > p->n_leaves - count)
+    return fail(MPE_EINVAL, "%s: leaves [%lld, %lld + %lld) of %lld", what, (long long)first, (long long)first, (long long)count,
+                (long long)p->n_leaves);
+  return hip_result(mpe::launch_prio_repair(a, (uint64_t)first, (uint64_t)count, static_cast<hipStream_t>(stream)), what);
 }
 
 }  // extern "C"

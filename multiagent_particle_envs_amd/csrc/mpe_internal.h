@@ -152,7 +152,34 @@ struct ReplaySampleArgs {
   int32_t col_move[MPE_REPLAY_MAX_AGENTS], col_utter[MPE_REPLAY_MAX_AGENTS];   // first joint column of the head, -1: none
 };
 uint32_t replay_magic(uint32_t w);
-int launch_replay_sample(const ReplaySampleArgs &a, hipStream_t stream);
+// from_idx: the transitions are read from a.idx (mpe_replay_gather) instead of drawn and written there (mpe_replay_sample)
+int launch_replay_sample(const ReplaySampleArgs &a, hipStream_t stream, bool from_idx = false);
+
+// prioritized replay (mpe_replay_prio.hip): the sum tree of include/mpe_hip.h (MpeReplayPrio), checked by the caller
+struct PrioArgs {
+  float *tree, *pmax;
+  uint32_t *ticket;
+  const int64_t *head;
+  uint64_t S, B, n_leaves;
+  int32_t n_levels;
+  uint64_t off[MPE_REPLAY_PRIO_MAX_LEVELS + 1];        // first float of level l; off[n_levels] = the float count
+};
+struct PrioDrawArgs {
+  const uint32_t *u24;                                 // the caller's 24 bits per sample, or nullptr: drawn
+  int64_t *idx, *n_valid;
+  float *prio, *total;
+  uint64_t seed, draw, M;
+};
+struct PrioUpdateArgs {
+  const int64_t *idx;
+  const float *prio;
+  uint64_t M;                                          // samples, or nodes of a range
+  uint64_t first;                                      // first node of a range (mpe_replay_prio_repair)
+};
+int launch_prio_push(const PrioArgs &a, hipStream_t stream);
+int launch_prio_draw(const PrioArgs &a, const PrioDrawArgs &d, hipStream_t stream);
+int launch_prio_update(const PrioArgs &a, const PrioUpdateArgs &u, hipStream_t stream);
+int launch_prio_repair(const PrioArgs &a, uint64_t first_leaf, uint64_t count, hipStream_t stream);
 
 // the composable output stage (mpe_rows.hip): kernel-side header of an MpeRowProgram
 constexpr int kRowSlots = 8;

@@ -1,4 +1,4 @@
-// The replay buffer (mpe_replay_push / mpe_replay_sample): a ring of the last S steps' transitions of all B worlds
+// The replay buffer (mpe_replay_push / mpe_replay_sample / mpe_replay_gather): a ring of the last S steps' transitions of all B worlds
 // in device memory.  k_replay_push streams one step's tensors into slot head % S and advances `head` on the device;
 // k_replay_sample draws M transitions (Philox, replay_bits in mpe_device.h) and gathers every field of every agent for them.
 // Both only move data: every output is bit-equal to its source.
@@ -99,7 +99,9 @@ __device__ __forceinline__ void gather_rows(const float *__restrict__ src, uint6
 
 // grid (tiles of kReplayTile samples, jobs): job y gathers one field of one agent -- y in [0, A): obs of agent y; [A, 2A): next obs;
 // [2A, 3A): move rows; then, with dim_c > 0, A utterance jobs; the last job is rew and done of every agent.  Every block draws its
-// tile's indices into LDS itself (32 Philox blocks); the blocks of job 0 write idx.
+// tile's indices into LDS itself (32 Philox blocks); the blocks of job 0 write idx.  FROM_IDX (mpe_replay_gather): the tile's
+// transitions are read from idx instead; an index outside [0, S * B) reads transition 0.
+template <bool FROM_IDX>
 __global__ __launch_bounds__(256) void k_replay_sample(const ReplaySampleArgs a) {
   __shared__ uint32_t s_slot[kReplayTile], s_world[kReplayTile];
   const uint64_t head = (uint64_t)*a.head;
@@ -109,12 +111,18 @@ __global__ __launch_bounds__(256) void k_replay_sample(const ReplaySampleArgs a)
   const uint32_t n = a.M - m0 < (uint64_t)kReplayTile ? (uint32_t)(a.M - m0) : (uint32_t)kReplayTile;
   const uint32_t t = threadIdx.x, job = blockIdx.y;
   if (t < n) {
-    const uint64_t u = replay_bits(a.seed, m0 + t, a.draw);
-    const uint64_t j = __umul64hi(u, n_valid);
+    uint64_t j;
+    if (FROM_IDX) {
+      j = (uint64_t)a.idx[m0 + t];
+      j = j < a.S * a.B ? j : 0;
+    } else {
+      const uint64_t u = replay_bits(a.seed, m0 + t, a.draw);
+      j = __umul64hi(u, n_valid);
+    }
     const uint64_t sl = j / a.B;
     s_slot[t] = (uint32_t)sl;
     s_world[t] = (uint32_t)(j - sl * a.B);
-    if (job == 0) a.idx[m0 + t] = (int64_t)j;
+    if (!FROM_IDX && job == 0) a.idx[m0 + t] = (int64_t)j;
   }
   __syncthreads();
   const uint32_t A = (uint32_t)a.A;
@@ -176,11 +184,12 @@ int launch_replay_push(const ReplayPushArgs &a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
-int launch_replay_sample(const ReplaySampleArgs &a, hipStream_t stream) {
+int launch_replay_sample(const ReplaySampleArgs &a, hipStream_t stream, bool from_idx) {
   const uint64_t tiles = (a.M + kReplayTile - 1) / kReplayTile;
   const unsigned jobs = (unsigned)((a.dim_c > 0 ? 4 : 3) * a.A + 1);
   if (tiles == 0 || tiles > 0x7fffffffull) return (int)hipErrorInvalidConfiguration;
-  hipLaunchKernelGGL(k_replay_sample, dim3((unsigned)tiles, jobs), dim3(256), 0, stream, a);
+  if (from_idx) hipLaunchKernelGGL(k_replay_sample<true>, dim3((unsigned)tiles, jobs), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(k_replay_sample<false>, dim3((unsigned)tiles, jobs), dim3(256), 0, stream, a);
   return (int)hipGetLastError();
 }
 

@@ -323,7 +323,8 @@ class PolicyLoop(object):
         (freeze() again and re-capture after an update).  Two warm-up steps really run in front of the capture; the state and the
         step count are put back.  replay: every captured step pushes its transition to that ReplayBuffer; the
         push reads and advances the buffer's device-side step count, so each replay() fills the next T slots (the warm-up steps'
-        pushes are taken back: the count is restored, the two slots they wrote are the first two the graph writes)."""
+        pushes are taken back through the buffer's _mark / _rewind hooks: the count is restored -- and a prioritized buffer's
+        priorities, tree and pmax --, the two slots they wrote are the first two the graph writes)."""
         _step_many_env_check(self.env)
         env, w, pi = self.env, self.world, self.pi
         if replay is not None:
@@ -343,11 +344,12 @@ class PolicyLoop(object):
             comm = env._comm.clone() if env._comm is not None else None
             keep = [o.clone() for o in obs0] if obs0 is not None else None
             choice = w.choice_i32.clone() if w.choice_i32 is not None else None
-            head, count = (replay.head.clone(), replay.count) if replay is not None else (None, 0)
+            mark, count = (replay._mark(2), replay.count) if replay is not None else (None, 0)
             for _ in range(2):      # code objects and allocations outside the capture
                 self.step(replay=replay)
             if replay is not None:
-                replay.head.copy_(head)
+                replay.count = count
+                replay._rewind(mark)
             w.pos.copy_(pos)
             w._vel_all.copy_(vel)
             if comm is not None:

@@ -8,6 +8,15 @@ device and the push advances it itself.  csrc/mpe_replay.hip, DESIGN.md 2.11.
     buf.push(obs_n, action, next_obs_n, rew_n, done_n)
     batch = buf.sample(1024, joint=True)        # batch.obs_n[i] [M, D_i], batch.act [A,M,5], batch.joint [M, sum D + sum n_act] ...
     PolicyLoop(env, pi).run(T, replay=buf)      # the closed loop pushes every step itself
+
+`PrioritizedReplayBuffer` adds one float32 priority per transition and a device sum tree over them (csrc/mpe_replay_prio.hip,
+DESIGN.md 2.12): proportional draws, importance weights and priority updates without a host round trip or a pass over all S * B
+priorities.
+
+    buf = PrioritizedReplayBuffer(env, steps=1024, alpha=0.6)
+    buf.push(obs_n, action, next_obs_n, rew_n, done_n)       # a new transition enters at the largest priority seen so far
+    batch = buf.sample(1024, joint=True)                     # a ReplayBatch plus batch.prio / .total / .n_valid / .weights(beta)
+    buf.update_td(batch.idx, td_error)                       # priority = (|td| + eps) ** alpha
 """
 import ctypes as C
 
@@ -132,6 +141,10 @@ class ReplayBuffer(object):
         """One launch: the step's transitions into slot count % steps.  obs_n: the observations the action was chosen on;
         action: the [A,B,5] moves or (moves, utterances [A,B,dim_c]) env.step took; next_obs_n, rew, done: what it returned."""
         self._alloc()
+        self._launch_push(self._push_args(obs_n, action, next_obs_n, rew, done))
+
+    def _push_args(self, obs_n, action, next_obs_n, rew, done):
+        """The checked arguments of one mpe_replay_push call (checked once per pointer set); nothing is launched."""
         pair = type(action) is tuple
         moves, utter = action if pair else (action, None)
         key = tuple(o.data_ptr() for o in obs_n) + tuple(o.data_ptr() for o in next_obs_n) + \
@@ -161,19 +174,26 @@ class ReplayBuffer(object):
                 if len(self._ptrs) >= 64:
                     self._ptrs.clear()
                 self._ptrs[key] = args
+        return args
+
+    def _launch_push(self, args):
         o, n, mv, ut, r, d = args
         _abi.check(_abi.lib().mpe_replay_push(C.byref(self._desc), o, n, mv, ut, r.data_ptr(), d.data_ptr(),
                                               _abi.raw_stream(self.world.device)), "mpe_replay_push")
         self.count += 1
 
     # ---- sample -----------------------------------------------------------------------------------------------------------------
-    def _batch(self, M, joint):
-        b = self._batches.get((M, joint))
+    _batch_type = ReplayBatch
+
+    def _batch(self, M, joint, gathered=False):
+        """The buffer's output tensors per (M, joint); gathered: a set of its own for gather(), whose idx is the caller's."""
+        key = (M, joint, "gather") if gathered else (M, joint)
+        b = self._batches.get(key)
         if b is not None:
             return b
         A, dev, off = self.A, self.world.device, self.off
-        b = ReplayBatch()
-        b.idx = torch.zeros(M, dtype=torch.int64, device=dev)
+        b = ReplayBatch() if gathered else self._batch_type()
+        b.idx = None if gathered else torch.zeros(M, dtype=torch.int64, device=dev)
         b._obs = torch.zeros(off[-1] * M, dtype=torch.float32, device=dev)
         b._next = torch.zeros(off[-1] * M, dtype=torch.float32, device=dev)
         b.obs_n = [b._obs[off[i] * M: off[i + 1] * M].view(M, off[i + 1] - off[i]) for i in range(A)]
@@ -187,8 +207,39 @@ class ReplayBuffer(object):
         b.joint_next = torch.zeros((M, off[-1]), dtype=torch.float32, device=dev) if joint else None
         if len(self._batches) >= 16:
             self._batches.clear()
-        self._batches[(M, joint)] = b
+        self._batches[key] = b
         return b
+
+    def _gather_into(self, b, M, idx, joint):
+        _abi.check(_abi.lib().mpe_replay_gather(
+            C.byref(self._desc), M, idx.data_ptr(), b._obs.data_ptr(), b._next.data_ptr(), b.act.data_ptr(),
+            b.utter.data_ptr() if b.utter is not None else None, b.rew.data_ptr(), b._done_u8.data_ptr(),
+            b.joint.data_ptr() if joint else None, b.joint_next.data_ptr() if joint else None,
+            _abi.raw_stream(self.world.device)), "mpe_replay_gather")
+
+    def gather(self, idx, joint=False):
+        """One launch: the transitions idx names (a contiguous int64 [M] tensor on the env's device, slot * steps' worlds + world,
+        what ReplayBatch.idx holds) -> a ReplayBatch whose idx IS that tensor; the other tensors are this buffer's per (M, joint)
+        and are rewritten by the next gather of that shape.  An index outside [0, steps * worlds) gathers transition 0."""
+        joint = bool(joint)
+        if not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() < 1 or not idx.is_contiguous() or \
+                idx.device != self.world.device:
+            raise _abi.MpeError("ReplayBuffer.gather: idx is a contiguous int64 [M] tensor (M >= 1) on the env's device")
+        if self.count < 1:
+            raise _abi.MpeError("ReplayBuffer.gather: the buffer is empty (nothing was pushed)")
+        M = int(idx.numel())
+        b = self._batch(M, joint, gathered=True)
+        b.idx = idx
+        self._gather_into(b, M, idx, joint)
+        return b
+
+    # ---- taking pushes back (PolicyLoop.capture's warm-up steps) ----------------------------------------------------------------
+    def _mark(self, steps):
+        """What _rewind needs to take the next `steps` pushes back."""
+        return self.head.clone()
+
+    def _rewind(self, mark):
+        self.head.copy_(mark)
 
     def sample(self, M, draw=None, joint=False):
         """One launch: M transitions drawn uniformly with replacement from the valid part of the ring with the draws of (seed,
@@ -209,3 +260,141 @@ class ReplayBuffer(object):
             b.joint.data_ptr() if joint else None, b.joint_next.data_ptr() if joint else None,
             _abi.raw_stream(self.world.device)), "mpe_replay_sample")
         return b
+
+
+class PrioritizedReplayBatch(ReplayBatch):
+    """A ReplayBatch drawn in proportion to the priorities: also prio [M] float32 (the drawn transitions' priorities as stored),
+    total [1] float32 (the sum of all priorities), n_valid [1] int64 (the valid transitions), all on the device."""
+    __slots__ = ("prio", "total", "n_valid")
+
+    def weights(self, beta):
+        """Importance weights [M]: (n_valid * prio / total) ** -beta, divided by their maximum.  Torch ops on device tensors only,
+        so they stay correct inside a captured graph."""
+        w = (self.prio * (self.n_valid.to(torch.float32) / self.total)).pow(-float(beta))
+        return w / w.max()
+
+
+class PrioritizedReplayBuffer(ReplayBuffer):
+    """A ReplayBuffer with proportional prioritized sampling (Schaul et al. 2016): one float32 priority per transition (leaf
+    slot * worlds + world) and a sum tree of fan-out 16 over them in ONE device tensor `tree` (include/mpe_hip.h: the levels one
+    after another, level l at floats level_off[l]); pmax [1]: the largest priority ever stored, what a new transition enters at.
+    push takes one more launch than ReplayBuffer's, sample two launches (the draw, the gather), update_priorities
+    2 + (levels - 1); all capture into a HIP graph.  alpha, eps: update_td's priority is (|td| + eps) ** alpha."""
+
+    _batch_type = PrioritizedReplayBatch
+
+    def __init__(self, env, steps, seed=0, alpha=0.6, eps=1e-6):
+        ReplayBuffer.__init__(self, env, steps, seed)
+        self.alpha, self.eps = float(alpha), float(eps)
+        if not self.alpha >= 0.0:
+            raise _abi.MpeError("PrioritizedReplayBuffer: alpha = %r (need alpha >= 0)" % (alpha,))
+        if not self.eps > 0.0:
+            raise _abi.MpeError("PrioritizedReplayBuffer: eps = %r (need eps > 0: a zero priority is a transition never drawn again)" % (eps,))
+        self.n_leaves = self.S * self.B
+        self.level_off, self.n_floats = _abi.replay_prio_layout(self.n_leaves)
+        self.tree = None
+
+    def _alloc(self):
+        if self.tree is not None:
+            return
+        ReplayBuffer._alloc(self)
+        dev = self.world.device
+        self.tree = torch.zeros(self.n_floats, dtype=torch.float32, device=dev)
+        self.pmax = torch.ones(1, dtype=torch.float32, device=dev)
+        self._prio_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        p = _abi.MpeReplayPrio()
+        p.n_leaves, p.tree, p.pmax, p.ticket = self.n_leaves, self.tree.data_ptr(), self.pmax.data_ptr(), self._prio_ticket.data_ptr()
+        self._prio = p
+
+    @property
+    def priorities(self):
+        """The leaves as a [steps, worlds] view of the tree."""
+        self._alloc()
+        return self.tree[:self.n_leaves].view(self.S, self.B)
+
+    def level(self, l):
+        """Level l of the tree (a view): level 0 the leaves, the last level the total."""
+        self._alloc()
+        n = self.n_leaves
+        for _ in range(l):
+            n = -(-n // 16)
+        return self.tree[self.level_off[l]: self.level_off[l] + n]
+
+    def push(self, obs_n, action, next_obs_n, rew, done):
+        """Two launches: the slot's priorities = pmax (and the tree above them), then ReplayBuffer.push."""
+        self._alloc()
+        args = self._push_args(obs_n, action, next_obs_n, rew, done)      # (refusals come before anything is enqueued)
+        _abi.check(_abi.lib().mpe_replay_prio_push(C.byref(self._desc), C.byref(self._prio), _abi.raw_stream(self.world.device)),
+                   "mpe_replay_prio_push")
+        self._launch_push(args)
+
+    def _batch(self, M, joint, gathered=False):
+        b = ReplayBuffer._batch(self, M, joint, gathered)
+        if not gathered and getattr(b, "prio", None) is None:
+            dev = self.world.device
+            b.prio = torch.zeros(M, dtype=torch.float32, device=dev)
+            b.total = torch.zeros(1, dtype=torch.float32, device=dev)
+            b.n_valid = torch.zeros(1, dtype=torch.int64, device=dev)
+        return b
+
+    def sample(self, M, draw=None, joint=False, u24=None):
+        """Two launches: M transitions drawn in proportion to their priorities (stratified: sample k from the k-th M-th of the
+        total, with the draws of (seed, draw)), then every field gathered for them -> a PrioritizedReplayBatch whose tensors are
+        this buffer's per (M, joint).  draw=None: an internal draw counter, advanced by the call.  u24: an int32 [M] device tensor
+        whose low 24 bits replace the drawn bits (tests, quasi-random sequences)."""
+        M, joint = int(M), bool(joint)
+        if M < 1:
+            raise _abi.MpeError("PrioritizedReplayBuffer.sample: M = %d samples (need at least 1)" % M)
+        if self.count < 1:
+            raise _abi.MpeError("PrioritizedReplayBuffer.sample: the buffer is empty (nothing was pushed)")
+        if u24 is not None and (not torch.is_tensor(u24) or u24.dtype != torch.int32 or tuple(u24.shape) != (M,) or
+                                not u24.is_contiguous() or u24.device != self.world.device):
+            raise _abi.MpeError("PrioritizedReplayBuffer.sample: u24 is a contiguous int32 [%d] tensor on the env's device" % M)
+        if draw is None:
+            draw = self._draw
+            self._draw += 1
+        b = self._batch(M, joint)
+        stream = _abi.raw_stream(self.world.device)
+        _abi.check(_abi.lib().mpe_replay_prio_draw(
+            C.byref(self._desc), C.byref(self._prio), M, int(draw) & (2 ** 64 - 1), u24.data_ptr() if u24 is not None else None,
+            b.idx.data_ptr(), b.prio.data_ptr(), b.total.data_ptr(), b.n_valid.data_ptr(), stream), "mpe_replay_prio_draw")
+        self._gather_into(b, M, b.idx, joint)
+        return b
+
+    def update_priorities(self, idx, priority):
+        """Transition idx[k] takes priority[k] (clamped to [2^-40, 2^40], a NaN to 2^-40; the largest where several k name one
+        transition); an idx outside the ring, or one that was never pushed, is ignored.  idx: int64 [M], priority: float32 [M],
+        contiguous, on the env's device.  2 + (levels - 1) launches."""
+        self._alloc()
+        dev = self.world.device
+        if not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() < 1 or not idx.is_contiguous() or \
+                idx.device != dev:
+            raise _abi.MpeError("PrioritizedReplayBuffer.update_priorities: idx is a contiguous int64 [M] tensor (M >= 1) on the env's device")
+        if not torch.is_tensor(priority) or priority.dtype != torch.float32 or priority.shape != idx.shape or \
+                not priority.is_contiguous() or priority.device != dev:
+            raise _abi.MpeError("PrioritizedReplayBuffer.update_priorities: priority is a contiguous float32 [%d] tensor on the env's device"
+                                % idx.numel())
+        _abi.check(_abi.lib().mpe_replay_prio_update(C.byref(self._desc), C.byref(self._prio), int(idx.numel()), idx.data_ptr(),
+                                                     priority.data_ptr(), _abi.raw_stream(dev)), "mpe_replay_prio_update")
+
+    def update_td(self, idx, td):
+        """update_priorities(idx, (|td| + eps) ** alpha): the power runs in torch, the kernels hold no transcendental."""
+        if not torch.is_tensor(td) or not td.is_floating_point():
+            raise _abi.MpeError("PrioritizedReplayBuffer.update_td: td is a floating-point tensor of idx's shape")
+        self.update_priorities(idx, ((td.to(torch.float32).abs() + self.eps) ** self.alpha).contiguous())
+
+    # ---- taking pushes back: the leaves of the slots the pushes will write, pmax, and the tree above them -----------------------
+    def _mark(self, steps):
+        self._alloc()
+        slots = sorted(set((self.count + k) % self.S for k in range(int(steps))))
+        return (ReplayBuffer._mark(self, steps), self.pmax.clone(), [(s, self.priorities[s].clone()) for s in slots])
+
+    def _rewind(self, mark):
+        head, pmax, leaves = mark
+        ReplayBuffer._rewind(self, head)
+        self.pmax.copy_(pmax)
+        stream = _abi.raw_stream(self.world.device)
+        for s, row in leaves:
+            self.priorities[s].copy_(row)
+            _abi.check(_abi.lib().mpe_replay_prio_repair(C.byref(self._desc), C.byref(self._prio), s * self.B, self.B, stream),
+                       "mpe_replay_prio_repair")
