@@ -440,6 +440,48 @@ int mpe_replay_sample(const MpeReplay *replay, int64_t M, uint64_t draw, int64_t
 int mpe_replay_gather(const MpeReplay *replay, int64_t M, const int64_t *idx, float *obs, float *next_obs, float *act,
                       float *utter, float *rew, uint8_t *done, float *joint, float *joint_next, void *stream);
 
+/* ---- n-step returns from the ring: draw-or-read, walk, returns and gather in ONE launch (csrc/mpe_replay.hip) ---------------
+ * The ring is time-major and `head` lives on the device, so the absolute step number of every slot is known inside the kernel
+ * and the next n steps of a world are n more rows at a known stride.  THE RULE, for a transition
+ * j = slot * B + world with h = *head, n_valid = min(h, S) * B, n in 1..MPE_REPLAY_MAX_NSTEP, gamma, episode_len = L >= 0 and
+ * episode_phase = p (0 <= p < max(L, 1): the episode-step index of push number 0; L and p count PUSHES):
+ *   A j outside [0, n_valid) is treated as transition 0 (never-pushed slots too, unlike mpe_replay_gather).
+ *   ahead = (h - 1 - slot) mod S is the number of newer steps of that world in the ring; g = h - 1 - ahead is the slot's
+ *   absolute step number.  Walk k = 0, 1, ... over the steps g + k, which live in slot (slot + k) mod S.  Step g + k is USED if
+ *   k < n and k <= ahead.  After using it the walk STOPS if any of
+ *     - any agent's done byte at that step and world is non-zero (the episode ended; world-level: one next_obs for all agents),
+ *     - L > 0 and (g + k + 1 + p) mod L == 0 (the loop restarted the world after this step: a truncation, done stays as stored),
+ *     - k + 1 == n,
+ *     - k == ahead (the newest step in the ring).
+ *   m = the number of steps used, 1 <= m <= min(n, S).
+ * Outputs per sample, beside those of mpe_replay_sample:
+ *   ret [A][M] float32, every operation rounded separately (the build uses -ffp-contract=off) and in this order:
+ *     d_0 = 1, ret = rew[g][i]; for k = 1..m-1: d_k = d_{k-1} * gamma, then ret = ret + d_k * rew[g + k][i];
+ *   discount [M] float32 = d_{m-1} * gamma (gamma^m by repeated multiply: the target is ret + discount * (1 - done) * Q(next));
+ *   n_used [M] int32 = m;   last [M] int64 = ((slot + m - 1) mod S) * B + world;
+ *   done [A][M] and next_obs (per agent, and joint_next) are taken from transition `last`;
+ *   obs, act, utter, rew (the one-step reward), joint and idx from transition j, exactly as mpe_replay_sample writes them.
+ * With n = 1 every output of mpe_replay_sample / _gather is bit-equal to theirs, ret == rew, discount == gamma, n_used == 1 and
+ * last == idx (for idx in [0, n_valid)).  The draw of mpe_replay_sample_nstep is mpe_replay_sample's: the same (seed, draw)
+ * gives the same idx.  ret, discount, n_used and last are all required.  n outside 1..MPE_REPLAY_MAX_NSTEP, a non-finite
+ * gamma, a negative episode_len, a phase out of range and NULL outputs are refused before any launch.  Nothing is written while
+ * the ring is empty (head = 0).                                                                                             */
+#define MPE_REPLAY_MAX_NSTEP 16
+typedef struct MpeReplayNStep {
+  int32_t n;                                      /* 1..MPE_REPLAY_MAX_NSTEP                                               */
+  float gamma;                                    /* finite                                                                */
+  int64_t episode_len;                            /* L: the loop restarts every world after every L-th push; 0: never      */
+  int64_t episode_phase;                          /* p: the episode-step index of push number 0, 0 <= p < max(L, 1)        */
+} MpeReplayNStep;
+size_t mpe_sizeof_replay_nstep(void);
+int mpe_replay_sample_nstep(const MpeReplay *replay, const MpeReplayNStep *nstep, int64_t M, uint64_t draw, int64_t *idx,
+                            float *obs, float *next_obs, float *act, float *utter, float *rew, uint8_t *done, float *joint,
+                            float *joint_next, float *ret, float *discount, int32_t *n_used, int64_t *last, void *stream);
+/* The same with the M transitions READ from idx (left alone), as mpe_replay_gather reads them.                              */
+int mpe_replay_gather_nstep(const MpeReplay *replay, const MpeReplayNStep *nstep, int64_t M, const int64_t *idx, float *obs,
+                            float *next_obs, float *act, float *utter, float *rew, uint8_t *done, float *joint,
+                            float *joint_next, float *ret, float *discount, int32_t *n_used, int64_t *last, void *stream);
+
 /* ---- prioritized replay: one priority per transition and a sum tree over them (csrc/mpe_replay_prio.hip) --------------------
  * Proportional prioritized experience replay on the ring above, all on the device, every launch capturable: ONE more launch
  * per push, two launches per minibatch (the draw, then mpe_replay_gather), 2 + (levels - 1) launches per priority update.

@@ -93,6 +93,13 @@ class MpeReplay(C.Structure):          # include/mpe_hip.h: the replay ring of m
                 ("seed", C.c_uint64)]
 
 
+MPE_REPLAY_MAX_NSTEP = 16
+
+
+class MpeReplayNStep(C.Structure):     # include/mpe_hip.h: the n-step rule of mpe_replay_sample_nstep / mpe_replay_gather_nstep
+    _fields_ = [("n", C.c_int32), ("gamma", C.c_float), ("episode_len", C.c_int64), ("episode_phase", C.c_int64)]
+
+
 MPE_REPLAY_PRIO_FANOUT, MPE_REPLAY_PRIO_MAX_LEVELS = 16, 11
 MPE_REPLAY_PRIO_MIN, MPE_REPLAY_PRIO_MAX = 2.0 ** -40, 2.0 ** 40
 MPE_STREAM_REPLAY_PRIO = 0x5250524F
@@ -204,6 +211,9 @@ EXPORTS = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mpe_replay_gather": (C.c_int, [C.POINTER(MpeReplay), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mpe_sizeof_replay_nstep": (C.c_size_t, []),
+    "mpe_replay_sample_nstep": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(MpeReplayNStep), C.c_int64, C.c_uint64] + [C.c_void_p] * 14),
+    "mpe_replay_gather_nstep": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(MpeReplayNStep), C.c_int64] + [C.c_void_p] * 14),
     "mpe_sizeof_replay_prio": (C.c_size_t, []),
     "mpe_replay_prio_layout": (C.c_int, [C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mpe_replay_prio_push": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(MpeReplayPrio), C.c_void_p]),
@@ -242,7 +252,8 @@ def lib():
             handle.mpe_sizeof_row_program() != C.sizeof(MpeRowProgram) or handle.mpe_sizeof_step_server() != C.sizeof(MpeStepServer) or \
             handle.mpe_sizeof_render_args() != C.sizeof(MpeRenderArgs) or handle.mpe_sizeof_policy() != C.sizeof(MpePolicy) or \
             handle.mpe_sizeof_actor_set() != C.sizeof(MpeActorSet) or handle.mpe_sizeof_replay() != C.sizeof(MpeReplay) or \
-            handle.mpe_sizeof_replay_prio() != C.sizeof(MpeReplayPrio):
+            handle.mpe_sizeof_replay_prio() != C.sizeof(MpeReplayPrio) or \
+            handle.mpe_sizeof_replay_nstep() != C.sizeof(MpeReplayNStep):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")
     _lib = handle
     return _lib

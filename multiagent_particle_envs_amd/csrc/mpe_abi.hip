@@ -1,4 +1,5 @@
 // mpe_abi.hip -- the extern "C" surface declared in include/mpe_hip.h (host code only).
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1361,12 +1362,29 @@ int mpe_replay_push(const MpeReplay *r, const float *const *obs_ptrs, const floa
   return hip_result(mpe::launch_replay_push(a, static_cast<hipStream_t>(stream)), what);
 }
 // mpe_replay_sample (idx written) and mpe_replay_gather (from_idx: idx read) share everything but the source of the indices
+// (and the n-step entry points, `nstep` given: the four outputs they add are required, and k_replay_nstep is launched)
+struct NStepOut { float *ret, *discount; int32_t *n_used; int64_t *last; };
 static int replay_sample(const char *what, bool from_idx, const MpeReplay *r, int64_t M, uint64_t draw, int64_t *idx, float *obs,
                          float *next_obs, float *act, float *utter, float *rew, uint8_t *done, float *joint, float *joint_next,
-                         void *stream) {
+                         void *stream, const MpeReplayNStep *nstep = nullptr, NStepOut x = {}) {
   if (int rc = check_replay(r, what, true)) return rc;
   if (M < 1) return fail(MPE_EINVAL, "%s: M = %lld samples (need at least 1)", what, (long long)M);
   if (M > ((int64_t)1 << 31) - 1) return fail(MPE_EUNSUPPORTED, "%s: M = %lld samples (at most 2^31 - 1 per launch)", what, (long long)M);
+  if (nstep) {
+    if (nstep->n < 1 || nstep->n > MPE_REPLAY_MAX_NSTEP)
+      return fail(MPE_EINVAL, "%s: nstep->n = %d (need 1 <= n <= MPE_REPLAY_MAX_NSTEP = %d)", what, nstep->n, MPE_REPLAY_MAX_NSTEP);
+    if (!std::isfinite(nstep->gamma)) return fail(MPE_EINVAL, "%s: nstep->gamma = %g is not finite", what, (double)nstep->gamma);
+    if (nstep->episode_len < 0) return fail(MPE_EINVAL, "%s: nstep->episode_len = %lld (need >= 0)", what, (long long)nstep->episode_len);
+    if (nstep->episode_phase < 0 || nstep->episode_phase >= (nstep->episode_len > 1 ? nstep->episode_len : 1))
+      return fail(MPE_EINVAL, "%s: nstep->episode_phase = %lld (need 0 <= phase < max(episode_len, 1) = %lld)", what,
+                  (long long)nstep->episode_phase, (long long)(nstep->episode_len > 1 ? nstep->episode_len : 1));
+    const struct { const void *p; const char *name; unsigned align; } more[] = {
+        {x.ret, "ret", 4}, {x.discount, "discount", 4}, {x.n_used, "n_used", 4}, {x.last, "last", 8}};
+    for (const auto &f : more) {
+      if (!f.p) return fail(MPE_EINVAL, "%s: %s is NULL", what, f.name);
+      if ((uintptr_t)f.p & (f.align - 1)) return fail(MPE_EINVAL, "%s: %s is not %u-byte aligned", what, f.name, f.align);
+    }
+  }
   const struct { const void *p; const char *name; bool need; unsigned align; } out[] = {
       {idx, "idx", true, 8}, {obs, "obs", true, 4}, {next_obs, "next_obs", true, 4}, {act, "act", true, 4},
       {utter, "utter", r->dim_c > 0, 4}, {rew, "rew", true, 4}, {done, "done", true, 1}, {joint, "joint", false, 4},
@@ -1397,6 +1415,14 @@ static int replay_sample(const char *what, bool from_idx, const MpeReplay *r, in
     col += r->speaks[i] ? r->dim_c : 0;
   }
   a.joint_width = col;
+  if (nstep) {
+    mpe::ReplayNStepArgs ns;
+    std::memset(&ns, 0, sizeof(ns));
+    ns.ret = x.ret, ns.discount = x.discount, ns.n_used = x.n_used, ns.last = x.last;
+    ns.L = (uint64_t)nstep->episode_len, ns.phase = (uint64_t)nstep->episode_phase;
+    ns.n = (uint32_t)nstep->n, ns.gamma = nstep->gamma;
+    return hip_result(mpe::launch_replay_nstep(a, ns, static_cast<hipStream_t>(stream), from_idx), what);
+  }
   return hip_result(mpe::launch_replay_sample(a, static_cast<hipStream_t>(stream), from_idx), what);
 }
 int mpe_replay_sample(const MpeReplay *r, int64_t M, uint64_t draw, int64_t *idx, float *obs, float *next_obs, float *act,
@@ -1407,6 +1433,23 @@ int mpe_replay_gather(const MpeReplay *r, int64_t M, const int64_t *idx, float *
                       float *rew, uint8_t *done, float *joint, float *joint_next, void *stream) {
   return replay_sample("mpe_replay_gather", true, r, M, 0, const_cast<int64_t *>(idx), obs, next_obs, act, utter, rew, done, joint,
                        joint_next, stream);
+}
+size_t mpe_sizeof_replay_nstep(void) { return sizeof(MpeReplayNStep); }
+int mpe_replay_sample_nstep(const MpeReplay *r, const MpeReplayNStep *nstep, int64_t M, uint64_t draw, int64_t *idx, float *obs,
+                            float *next_obs, float *act, float *utter, float *rew, uint8_t *done, float *joint, float *joint_next,
+                            float *ret, float *discount, int32_t *n_used, int64_t *last, void *stream) {
+  const char *what = "mpe_replay_sample_nstep";
+  if (!nstep) return fail(MPE_EINVAL, "%s: nstep is NULL", what);
+  return replay_sample(what, false, r, M, draw, idx, obs, next_obs, act, utter, rew, done, joint, joint_next, stream, nstep,
+                       {ret, discount, n_used, last});
+}
+int mpe_replay_gather_nstep(const MpeReplay *r, const MpeReplayNStep *nstep, int64_t M, const int64_t *idx, float *obs,
+                            float *next_obs, float *act, float *utter, float *rew, uint8_t *done, float *joint, float *joint_next,
+                            float *ret, float *discount, int32_t *n_used, int64_t *last, void *stream) {
+  const char *what = "mpe_replay_gather_nstep";
+  if (!nstep) return fail(MPE_EINVAL, "%s: nstep is NULL", what);
+  return replay_sample(what, true, r, M, 0, const_cast<int64_t *>(idx), obs, next_obs, act, utter, rew, done, joint, joint_next,
+                       stream, nstep, {ret, discount, n_used, last});
 }
 
 // ---- prioritized replay (mpe_replay_prio.hip) ---------------------------------------------------------------------------------

@@ -154,6 +154,16 @@ struct ReplaySampleArgs {
 uint32_t replay_magic(uint32_t w);
 // from_idx: the transitions are read from a.idx (mpe_replay_gather) instead of drawn and written there (mpe_replay_sample)
 int launch_replay_sample(const ReplaySampleArgs &a, hipStream_t stream, bool from_idx = false);
+// n-step returns (k_replay_nstep): MpeReplayNStep as checked by the caller, and the four outputs it adds
+struct ReplayNStepArgs {
+  float *ret, *discount;                               // [A][M]; [M]
+  int32_t *n_used;                                     // [M]
+  int64_t *last;                                       // [M]
+  uint64_t L, phase;                                   // episode_len (0: none), episode_phase < max(L, 1)
+  uint32_t n;                                          // 1..MPE_REPLAY_MAX_NSTEP
+  float gamma;
+};
+int launch_replay_nstep(const ReplaySampleArgs &a, const ReplayNStepArgs &ns, hipStream_t stream, bool from_idx);
 
 // prioritized replay (mpe_replay_prio.hip): the sum tree of include/mpe_hip.h (MpeReplayPrio), checked by the caller
 struct PrioArgs {

@@ -17,8 +17,17 @@ priorities.
     buf.push(obs_n, action, next_obs_n, rew_n, done_n)       # a new transition enters at the largest priority seen so far
     batch = buf.sample(1024, joint=True)                     # a ReplayBatch plus batch.prio / .total / .n_valid / .weights(beta)
     buf.update_td(batch.idx, td_error)                       # priority = (|td| + eps) ** alpha
+
+n-step returns (the rule is stated in include/mpe_hip.h): `sample(..., n_step=n, gamma=g)` and `gather(idx,
+n_step=n, gamma=g)` of both buffers are still ONE launch of the gather (mpe_replay_sample_nstep / mpe_replay_gather_nstep) and
+return an NStepReplayBatch: ret [A,M] = sum_k gamma^k rew over the m <= n steps that follow the transition in its world and stay
+inside its episode and the ring, discount [M] = gamma^m, n_used [M] = m, last [M] the chain's last transition, from which done and
+next_obs_n / joint_next are taken: the target is ret + discount * (1 - done) * Q(next_obs).
+
+    batch = buf.sample(1024, joint=True, n_step=5, gamma=0.95, episode_len=25)      # PolicyLoop(env, pi, episode_len=25) pushed
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -33,6 +42,13 @@ class ReplayBatch(object):
     agents with both heads [obs0 obs1 | move0 utter0 | move1 utter1]) and joint_next [M, sum D_i].  The tensors belong to the
     buffer."""
     __slots__ = ("idx", "obs_n", "next_obs_n", "act", "utter", "rew", "done", "joint", "joint_next", "_obs", "_next", "_done_u8")
+
+
+class NStepReplayBatch(ReplayBatch):
+    """A ReplayBatch with n-step returns: also ret [A,M] float32 (the discounted sum of the m rewards of the chain that starts
+    at idx), discount [M] float32 (gamma^m), n_used [M] int32 (m) and last [M] int64 (the chain's last transition).  done,
+    next_obs_n and joint_next are those of `last`; idx, obs_n, act, utter, rew (the one-step reward) and joint those of idx."""
+    __slots__ = ("ret", "discount", "n_used", "last")
 
 
 class ReplayBuffer(object):
@@ -184,15 +200,24 @@ class ReplayBuffer(object):
 
     # ---- sample -----------------------------------------------------------------------------------------------------------------
     _batch_type = ReplayBatch
+    _nstep_batch_type = NStepReplayBatch
 
-    def _batch(self, M, joint, gathered=False):
-        """The buffer's output tensors per (M, joint); gathered: a set of its own for gather(), whose idx is the caller's."""
-        key = (M, joint, "gather") if gathered else (M, joint)
+    def _batch(self, M, joint, gathered=False, nstep=False):
+        """The buffer's output tensors per (M, joint); gathered: a set of its own for gather(), whose idx is the caller's; nstep:
+        sets of their own, (M, joint, "nstep"), with the four n-step outputs."""
+        key = (M, joint) + (("nstep",) if nstep else ()) + (("gather",) if gathered else ())
         b = self._batches.get(key)
         if b is not None:
             return b
         A, dev, off = self.A, self.world.device, self.off
-        b = ReplayBatch() if gathered else self._batch_type()
+        if nstep:
+            b = NStepReplayBatch() if gathered else self._nstep_batch_type()
+            b.ret = torch.zeros((A, M), dtype=torch.float32, device=dev)
+            b.discount = torch.zeros(M, dtype=torch.float32, device=dev)
+            b.n_used = torch.zeros(M, dtype=torch.int32, device=dev)
+            b.last = torch.zeros(M, dtype=torch.int64, device=dev)
+        else:
+            b = ReplayBatch() if gathered else self._batch_type()
         b.idx = None if gathered else torch.zeros(M, dtype=torch.int64, device=dev)
         b._obs = torch.zeros(off[-1] * M, dtype=torch.float32, device=dev)
         b._next = torch.zeros(off[-1] * M, dtype=torch.float32, device=dev)
@@ -217,20 +242,56 @@ class ReplayBuffer(object):
             b.joint.data_ptr() if joint else None, b.joint_next.data_ptr() if joint else None,
             _abi.raw_stream(self.world.device)), "mpe_replay_gather")
 
-    def gather(self, idx, joint=False):
+    def _nstep(self, who, n_step, gamma, episode_len, episode_phase):
+        """The checked MpeReplayNStep of a call (the ABI refuses the same by name; here before anything else is looked at)."""
+        if gamma is None:
+            raise _abi.MpeError("%s: gamma is required when n_step is given" % who)
+        n, g, L, p = int(n_step), float(gamma), int(episode_len), int(episode_phase)
+        if not 1 <= n <= _abi.MPE_REPLAY_MAX_NSTEP:
+            raise _abi.MpeError("%s: n_step = %d (need 1 <= n_step <= MPE_REPLAY_MAX_NSTEP = %d)" % (who, n, _abi.MPE_REPLAY_MAX_NSTEP))
+        if not math.isfinite(g):
+            raise _abi.MpeError("%s: gamma = %r is not finite" % (who, gamma))
+        if L < 0 or L >= 2 ** 63:
+            raise _abi.MpeError("%s: episode_len = %d (need 0 <= episode_len < 2^63; 0: the pushes are one episode)" % (who, L))
+        if not 0 <= p < max(L, 1):
+            raise _abi.MpeError("%s: episode_phase = %d (need 0 <= episode_phase < max(episode_len, 1) = %d)" % (who, p, max(L, 1)))
+        ns = _abi.MpeReplayNStep()
+        ns.n, ns.gamma, ns.episode_len, ns.episode_phase = n, g, L, p
+        return ns
+
+    def _nstep_into(self, b, M, joint, ns, idx=None, draw=0):
+        """The one launch of an n-step batch: idx given: read (mpe_replay_gather_nstep), else drawn into b.idx."""
+        L = _abi.lib()
+        outs = (b._obs.data_ptr(), b._next.data_ptr(), b.act.data_ptr(), b.utter.data_ptr() if b.utter is not None else None,
+                b.rew.data_ptr(), b._done_u8.data_ptr(), b.joint.data_ptr() if joint else None,
+                b.joint_next.data_ptr() if joint else None, b.ret.data_ptr(), b.discount.data_ptr(), b.n_used.data_ptr(),
+                b.last.data_ptr(), _abi.raw_stream(self.world.device))
+        if idx is not None:
+            _abi.check(L.mpe_replay_gather_nstep(C.byref(self._desc), C.byref(ns), M, idx.data_ptr(), *outs), "mpe_replay_gather_nstep")
+        else:
+            _abi.check(L.mpe_replay_sample_nstep(C.byref(self._desc), C.byref(ns), M, int(draw) & (2 ** 64 - 1), b.idx.data_ptr(), *outs),
+                       "mpe_replay_sample_nstep")
+
+    def gather(self, idx, joint=False, n_step=None, gamma=None, episode_len=0, episode_phase=0):
         """One launch: the transitions idx names (a contiguous int64 [M] tensor on the env's device, slot * steps' worlds + world,
         what ReplayBatch.idx holds) -> a ReplayBatch whose idx IS that tensor; the other tensors are this buffer's per (M, joint)
-        and are rewritten by the next gather of that shape.  An index outside [0, steps * worlds) gathers transition 0."""
+        and are rewritten by the next gather of that shape.  An index outside [0, steps * worlds) gathers transition 0.
+        n_step (with gamma; episode_len, episode_phase: see sample): still one launch -> an NStepReplayBatch, tensors per
+        (M, joint, "nstep"); there an index outside the VALID part of the ring, [0, len(self)), gathers transition 0."""
         joint = bool(joint)
+        ns = None if n_step is None else self._nstep("ReplayBuffer.gather", n_step, gamma, episode_len, episode_phase)
         if not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() < 1 or not idx.is_contiguous() or \
                 idx.device != self.world.device:
             raise _abi.MpeError("ReplayBuffer.gather: idx is a contiguous int64 [M] tensor (M >= 1) on the env's device")
         if self.count < 1:
             raise _abi.MpeError("ReplayBuffer.gather: the buffer is empty (nothing was pushed)")
         M = int(idx.numel())
-        b = self._batch(M, joint, gathered=True)
+        b = self._batch(M, joint, gathered=True, nstep=ns is not None)
         b.idx = idx
-        self._gather_into(b, M, idx, joint)
+        if ns is None:
+            self._gather_into(b, M, idx, joint)
+        else:
+            self._nstep_into(b, M, joint, ns, idx=idx)
         return b
 
     # ---- taking pushes back (PolicyLoop.capture's warm-up steps) ----------------------------------------------------------------
@@ -241,18 +302,30 @@ class ReplayBuffer(object):
     def _rewind(self, mark):
         self.head.copy_(mark)
 
-    def sample(self, M, draw=None, joint=False):
+    def sample(self, M, draw=None, joint=False, n_step=None, gamma=None, episode_len=0, episode_phase=0):
         """One launch: M transitions drawn uniformly with replacement from the valid part of the ring with the draws of (seed,
         draw) -> a ReplayBatch whose tensors are this buffer's per (M, joint) and are rewritten by the next sample of that shape.
-        draw=None: an internal draw counter, advanced by the call."""
+        draw=None: an internal draw counter, advanced by the call.
+        n_step=n (1..16; gamma is then required): the same draw and still one launch -> an NStepReplayBatch (tensors per
+        (M, joint, "nstep")) with the n-step return of every drawn transition; the chain of a transition stops at a step where
+        any agent is done, at the newest step in the ring and at the end of an episode.  episode_len / episode_phase say where
+        episodes end when nothing in the ring does (PolicyLoop restarts worlds without reporting done); both count PUSHES:
+        the world is restarted after every push number t with (t + 1 + episode_phase) % episode_len == 0, episode_phase being
+        the episode-step index of push number 0.  For a PolicyLoop(env, pi, episode_len=L) whose first pushed step was loop
+        step t0, pass episode_len=L, episode_phase=t0 % L.  episode_len=0: no restarts."""
         M, joint = int(M), bool(joint)
         if M < 1:
             raise _abi.MpeError("ReplayBuffer.sample: M = %d samples (need at least 1)" % M)
+        ns = None if n_step is None else self._nstep("ReplayBuffer.sample", n_step, gamma, episode_len, episode_phase)
         if self.count < 1:
             raise _abi.MpeError("ReplayBuffer.sample: the buffer is empty (nothing was pushed)")
         if draw is None:
             draw = self._draw
             self._draw += 1
+        if ns is not None:
+            b = self._batch(M, joint, nstep=True)
+            self._nstep_into(b, M, joint, ns, draw=draw)
+            return b
         b = self._batch(M, joint)
         _abi.check(_abi.lib().mpe_replay_sample(
             C.byref(self._desc), M, int(draw) & (2 ** 64 - 1), b.idx.data_ptr(), b._obs.data_ptr(), b._next.data_ptr(), b.act.data_ptr(),
@@ -274,6 +347,11 @@ class PrioritizedReplayBatch(ReplayBatch):
         return w / w.max()
 
 
+class PrioritizedNStepReplayBatch(PrioritizedReplayBatch):
+    """A PrioritizedReplayBatch with the n-step outputs of NStepReplayBatch (ret, discount, n_used, last)."""
+    __slots__ = ("ret", "discount", "n_used", "last")
+
+
 class PrioritizedReplayBuffer(ReplayBuffer):
     """A ReplayBuffer with proportional prioritized sampling (Schaul et al. 2016): one float32 priority per transition (leaf
     slot * worlds + world) and a sum tree of fan-out 16 over them in ONE device tensor `tree` (include/mpe_hip.h: the levels one
@@ -282,6 +360,7 @@ class PrioritizedReplayBuffer(ReplayBuffer):
     2 + (levels - 1); all capture into a HIP graph.  alpha, eps: update_td's priority is (|td| + eps) ** alpha."""
 
     _batch_type = PrioritizedReplayBatch
+    _nstep_batch_type = PrioritizedNStepReplayBatch
 
     def __init__(self, env, steps, seed=0, alpha=0.6, eps=1e-6):
         ReplayBuffer.__init__(self, env, steps, seed)
@@ -328,8 +407,8 @@ class PrioritizedReplayBuffer(ReplayBuffer):
                    "mpe_replay_prio_push")
         self._launch_push(args)
 
-    def _batch(self, M, joint, gathered=False):
-        b = ReplayBuffer._batch(self, M, joint, gathered)
+    def _batch(self, M, joint, gathered=False, nstep=False):
+        b = ReplayBuffer._batch(self, M, joint, gathered, nstep)
         if not gathered and getattr(b, "prio", None) is None:
             dev = self.world.device
             b.prio = torch.zeros(M, dtype=torch.float32, device=dev)
@@ -337,14 +416,17 @@ class PrioritizedReplayBuffer(ReplayBuffer):
             b.n_valid = torch.zeros(1, dtype=torch.int64, device=dev)
         return b
 
-    def sample(self, M, draw=None, joint=False, u24=None):
+    def sample(self, M, draw=None, joint=False, u24=None, n_step=None, gamma=None, episode_len=0, episode_phase=0):
         """Two launches: M transitions drawn in proportion to their priorities (stratified: sample k from the k-th M-th of the
         total, with the draws of (seed, draw)), then every field gathered for them -> a PrioritizedReplayBatch whose tensors are
         this buffer's per (M, joint).  draw=None: an internal draw counter, advanced by the call.  u24: an int32 [M] device tensor
-        whose low 24 bits replace the drawn bits (tests, quasi-random sequences)."""
+        whose low 24 bits replace the drawn bits (tests, quasi-random sequences).  n_step (with gamma; episode_len,
+        episode_phase: ReplayBuffer.sample): the same draw, then mpe_replay_gather_nstep in place of the gather -> a
+        PrioritizedNStepReplayBatch; update_td(batch.idx, td) as before."""
         M, joint = int(M), bool(joint)
         if M < 1:
             raise _abi.MpeError("PrioritizedReplayBuffer.sample: M = %d samples (need at least 1)" % M)
+        ns = None if n_step is None else self._nstep("PrioritizedReplayBuffer.sample", n_step, gamma, episode_len, episode_phase)
         if self.count < 1:
             raise _abi.MpeError("PrioritizedReplayBuffer.sample: the buffer is empty (nothing was pushed)")
         if u24 is not None and (not torch.is_tensor(u24) or u24.dtype != torch.int32 or tuple(u24.shape) != (M,) or
@@ -353,12 +435,15 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         if draw is None:
             draw = self._draw
             self._draw += 1
-        b = self._batch(M, joint)
+        b = self._batch(M, joint, nstep=ns is not None)
         stream = _abi.raw_stream(self.world.device)
         _abi.check(_abi.lib().mpe_replay_prio_draw(
             C.byref(self._desc), C.byref(self._prio), M, int(draw) & (2 ** 64 - 1), u24.data_ptr() if u24 is not None else None,
             b.idx.data_ptr(), b.prio.data_ptr(), b.total.data_ptr(), b.n_valid.data_ptr(), stream), "mpe_replay_prio_draw")
-        self._gather_into(b, M, b.idx, joint)
+        if ns is None:
+            self._gather_into(b, M, b.idx, joint)
+        else:
+            self._nstep_into(b, M, joint, ns, idx=b.idx)
         return b
 
     def update_priorities(self, idx, priority):
