@@ -1362,7 +1362,7 @@ int mpe_replay_push(const MpeReplay *r, const float *const *obs_ptrs, const floa
   return hip_result(mpe::launch_replay_push(a, static_cast<hipStream_t>(stream)), what);
 }
 // mpe_replay_sample (idx written) and mpe_replay_gather (from_idx: idx read) share everything but the source of the indices
-// (and the n-step entry points, `nstep` given: the four outputs they add are required, and k_replay_nstep is launched)
+// (and the n-step entry points, `nstep` given: the four outputs they add are required, and k_replay_sample's NSTEP arm runs)
 struct NStepOut { float *ret, *discount; int32_t *n_used; int64_t *last; };
 static int replay_sample(const char *what, bool from_idx, const MpeReplay *r, int64_t M, uint64_t draw, int64_t *idx, float *obs,
                          float *next_obs, float *act, float *utter, float *rew, uint8_t *done, float *joint, float *joint_next,
@@ -1421,9 +1421,9 @@ static int replay_sample(const char *what, bool from_idx, const MpeReplay *r, in
     ns.ret = x.ret, ns.discount = x.discount, ns.n_used = x.n_used, ns.last = x.last;
     ns.L = (uint64_t)nstep->episode_len, ns.phase = (uint64_t)nstep->episode_phase;
     ns.n = (uint32_t)nstep->n, ns.gamma = nstep->gamma;
-    return hip_result(mpe::launch_replay_nstep(a, ns, static_cast<hipStream_t>(stream), from_idx), what);
+    return hip_result(mpe::launch_replay_sample(a, &ns, static_cast<hipStream_t>(stream), from_idx), what);
   }
-  return hip_result(mpe::launch_replay_sample(a, static_cast<hipStream_t>(stream), from_idx), what);
+  return hip_result(mpe::launch_replay_sample(a, nullptr, static_cast<hipStream_t>(stream), from_idx), what);
 }
 int mpe_replay_sample(const MpeReplay *r, int64_t M, uint64_t draw, int64_t *idx, float *obs, float *next_obs, float *act,
                       float *utter, float *rew, uint8_t *done, float *joint, float *joint_next, void *stream) {

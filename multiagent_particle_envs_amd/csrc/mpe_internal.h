@@ -152,9 +152,7 @@ struct ReplaySampleArgs {
   int32_t col_move[MPE_REPLAY_MAX_AGENTS], col_utter[MPE_REPLAY_MAX_AGENTS];   // first joint column of the head, -1: none
 };
 uint32_t replay_magic(uint32_t w);
-// from_idx: the transitions are read from a.idx (mpe_replay_gather) instead of drawn and written there (mpe_replay_sample)
-int launch_replay_sample(const ReplaySampleArgs &a, hipStream_t stream, bool from_idx = false);
-// n-step returns (k_replay_nstep): MpeReplayNStep as checked by the caller, and the four outputs it adds
+// n-step returns (k_replay_sample<.., NSTEP = true>): MpeReplayNStep as checked by the caller, and the four outputs it adds
 struct ReplayNStepArgs {
   float *ret, *discount;                               // [A][M]; [M]
   int32_t *n_used;                                     // [M]
@@ -163,7 +161,9 @@ struct ReplayNStepArgs {
   uint32_t n;                                          // 1..MPE_REPLAY_MAX_NSTEP
   float gamma;
 };
-int launch_replay_nstep(const ReplaySampleArgs &a, const ReplayNStepArgs &ns, hipStream_t stream, bool from_idx);
+// ns: nullptr for the one-step kernel; from_idx: the transitions are read from a.idx (mpe_replay_gather) instead of drawn and
+// written there (mpe_replay_sample)
+int launch_replay_sample(const ReplaySampleArgs &a, const ReplayNStepArgs *ns, hipStream_t stream, bool from_idx);
 
 // prioritized replay (mpe_replay_prio.hip): the sum tree of include/mpe_hip.h (MpeReplayPrio), checked by the caller
 struct PrioArgs {

@@ -1,8 +1,10 @@
 // The replay buffer (mpe_replay_push / mpe_replay_sample / mpe_replay_gather): a ring of the last S steps' transitions of all B worlds
 // in device memory.  k_replay_push streams one step's tensors into slot head % S and advances `head` on the device;
 // k_replay_sample draws M transitions (Philox, replay_bits in mpe_device.h) and gathers every field of every agent for them.
-// Both only move data: every output is bit-equal to its source.  k_replay_nstep (mpe_replay_sample_nstep / _gather_nstep,
-// DESIGN.md 2.13) is k_replay_sample with n-step returns: the only arithmetic here, a fixed sequence of fp32 multiplies and adds.
+// Both only move data: every output is bit-equal to its source.  k_replay_sample's NSTEP instantiations (mpe_replay_sample_nstep /
+// _gather_nstep) add n-step returns: the only arithmetic here, a fixed sequence of fp32 multiplies and adds.
+#include <type_traits>
+
 #include "mpe_internal.h"
 
 namespace mpe {
@@ -98,77 +100,30 @@ __device__ __forceinline__ void gather_rows(const float *__restrict__ src, uint6
   }
 }
 
+// Only the n-step instantiations hold an NStepTile in LDS (1 792 bytes) and take ReplayNStepArgs; NoNStep stands in for both in
+// the one-step ones, which never name either.
+struct NStepTile {
+  uint32_t last[kReplayTile], lim[kReplayTile], m[kReplayTile];      // the chain's last slot; the largest k it may reach; steps used
+  uint8_t stop[MPE_REPLAY_MAX_NSTEP][kReplayTile];                   // any agent done at step k of the sample's chain
+};
+struct NoNStep {};
+
+// ONE kernel, four instantiations: mpe_replay_sample / _gather / _sample_nstep / _gather_nstep.
 // grid (tiles of kReplayTile samples, jobs): job y gathers one field of one agent -- y in [0, A): obs of agent y; [A, 2A): next obs;
 // [2A, 3A): move rows; then, with dim_c > 0, A utterance jobs; the last job is rew and done of every agent.  Every block draws its
-// tile's indices into LDS itself (32 Philox blocks); the blocks of job 0 write idx.  FROM_IDX (mpe_replay_gather): the tile's
-// transitions are read from idx instead; an index outside [0, S * B) reads transition 0.
-template <bool FROM_IDX>
-__global__ __launch_bounds__(256) void k_replay_sample(const ReplaySampleArgs a) {
+// tile's indices into LDS itself (32 Philox blocks); the blocks of job 0 write idx.  FROM_IDX: the tile's transitions are read from
+// idx instead.
+// NSTEP (n-step returns; THE RULE is stated in include/mpe_hip.h): a walk in front of the jobs that need it -- the
+// next-obs jobs gather from the chain's LAST step, the last job also sums the chain's rewards.  The walk has no dependent loads:
+// how far a chain MAY go (lim: n, the newest step, the episode cut) follows from head, slot and the arguments alone, so lanes over
+// (step k, sample) pairs load the A done bytes of every step that may be used at once, and one lane per sample then scans at
+// most 16 flags in LDS for the first stop.  Every ring address is formed from a slot below S (slot + k < 2 S, reduced by one
+// subtraction), a world below B and an agent below A.
+template <bool FROM_IDX, bool NSTEP>
+__global__ __launch_bounds__(256) void k_replay_sample(const ReplaySampleArgs a,
+                                                       const std::conditional_t<NSTEP, ReplayNStepArgs, NoNStep> ns) {
   __shared__ uint32_t s_slot[kReplayTile], s_world[kReplayTile];
-  const uint64_t head = (uint64_t)*a.head;
-  const uint64_t n_valid = (head < a.S ? head : a.S) * a.B;
-  if (n_valid == 0) return;
-  const uint64_t m0 = (uint64_t)blockIdx.x * kReplayTile;
-  const uint32_t n = a.M - m0 < (uint64_t)kReplayTile ? (uint32_t)(a.M - m0) : (uint32_t)kReplayTile;
-  const uint32_t t = threadIdx.x, job = blockIdx.y;
-  if (t < n) {
-    uint64_t j;
-    if (FROM_IDX) {
-      j = (uint64_t)a.idx[m0 + t];
-      j = j < a.S * a.B ? j : 0;
-    } else {
-      const uint64_t u = replay_bits(a.seed, m0 + t, a.draw);
-      j = __umul64hi(u, n_valid);
-    }
-    const uint64_t sl = j / a.B;
-    s_slot[t] = (uint32_t)sl;
-    s_world[t] = (uint32_t)(j - sl * a.B);
-    if (!FROM_IDX && job == 0) a.idx[m0 + t] = (int64_t)j;
-  }
-  __syncthreads();
-  const uint32_t A = (uint32_t)a.A;
-  const uint64_t B = a.B, M = a.M;
-  if (job < 2 * A) {
-    const bool nx = job >= A;
-    const uint32_t i = nx ? job - A : job;
-    const uint32_t W = (uint32_t)(a.off[i + 1] - a.off[i]);
-    const float *src = (nx ? a.next_obs : a.obs) + (uint64_t)a.off[i] * B;
-    float *d1 = (nx ? a.o_next : a.o_obs) + (uint64_t)a.off[i] * M + m0 * W;
-    float *jt = nx ? a.joint_next : a.joint;
-    const uint32_t w2 = nx ? (uint32_t)a.d_sum : (uint32_t)a.joint_width;
-    gather_rows(src, (uint64_t)a.d_sum * B, W, a.magic[i], d1, jt ? jt + m0 * w2 + a.off[i] : nullptr, w2, s_slot, s_world, n);
-  } else if (job < 3 * A) {
-    const uint32_t i = job - 2 * A, W = MPE_ACTION_DIM;
-    float *jt = a.joint && a.col_move[i] >= 0 ? a.joint + m0 * (uint32_t)a.joint_width + a.col_move[i] : nullptr;
-    gather_rows(a.act + (uint64_t)i * B * W, (uint64_t)A * B * W, W, 0x33333334u, a.o_act + ((uint64_t)i * M + m0) * W, jt,
-                (uint32_t)a.joint_width, s_slot, s_world, n);
-  } else if (a.dim_c > 0 && job < 4 * A) {
-    const uint32_t i = job - 3 * A, W = (uint32_t)a.dim_c;
-    float *jt = a.joint && a.col_utter[i] >= 0 ? a.joint + m0 * (uint32_t)a.joint_width + a.col_utter[i] : nullptr;
-    gather_rows(a.utter + (uint64_t)i * B * W, (uint64_t)A * B * W, W, a.magic_c, a.o_utter + ((uint64_t)i * M + m0) * W, jt,
-                (uint32_t)a.joint_width, s_slot, s_world, n);
-  } else {
-    for (uint32_t e = t; e < A * kReplayTile; e += 256) {      // lanes over a tile's samples of one agent
-      const uint32_t i = e / kReplayTile, r = e % kReplayTile;
-      if (r < n) {
-        const uint64_t from = ((uint64_t)s_slot[r] * A + i) * B + s_world[r];
-        a.o_rew[(uint64_t)i * M + m0 + r] = a.rew[from];
-        a.o_done[(uint64_t)i * M + m0 + r] = a.done[from];
-      }
-    }
-  }
-}
-
-// n-step returns (THE RULE is stated in include/mpe_hip.h): k_replay_sample's grid and jobs, with a walk in front
-// of the jobs that need it -- the next-obs jobs gather from the chain's LAST step, the last job also sums the chain's rewards.
-// The walk has no dependent loads: how far a chain MAY go (s_lim: n, the newest step, the episode cut) follows from head, slot
-// and the arguments alone, so lanes over (step k, sample) pairs load the A done bytes of every step that may be used at once,
-// and one lane per sample then scans at most 16 flags in LDS for the first stop.  Every ring address is formed from a slot
-// below S (slot + k < 2 S, reduced by one subtraction), a world below B and an agent below A.
-template <bool FROM_IDX>
-__global__ __launch_bounds__(256) void k_replay_nstep(const ReplaySampleArgs a, const ReplayNStepArgs ns) {
-  __shared__ uint32_t s_slot[kReplayTile], s_world[kReplayTile], s_last[kReplayTile], s_lim[kReplayTile], s_m[kReplayTile];
-  __shared__ uint8_t s_stop[MPE_REPLAY_MAX_NSTEP][kReplayTile];
+  __shared__ std::conditional_t<NSTEP, NStepTile, NoNStep> s_ns;
   const uint64_t head = (uint64_t)*a.head;
   const uint64_t n_valid = (head < a.S ? head : a.S) * a.B;
   if (n_valid == 0) return;
@@ -177,57 +132,63 @@ __global__ __launch_bounds__(256) void k_replay_nstep(const ReplaySampleArgs a, 
   const uint32_t t = threadIdx.x, job = blockIdx.y;
   const uint32_t A = (uint32_t)a.A;
   const uint64_t B = a.B, S = a.S, M = a.M;
-  const bool last_job = job == gridDim.y - 1;
-  const bool walks = (job >= A && job < 2 * A) || last_job;      // (block-uniform: the barriers below are taken by all or none)
+  const uint32_t rew_job = (a.dim_c > 0 ? 4 : 3) * A;      // the grid's last job (launch_replay_sample)
+  const bool walks = (job >= A && job < 2 * A) || job == rew_job;      // (block-uniform: the barriers below are taken by all or none)
   if (t < n) {
     uint64_t j;
     if (FROM_IDX) {
+      // include/mpe_hip.h: mpe_replay_gather reads transition 0 for an index outside the RING, [0, S * B) (a slot never pushed
+      // gathers what the ring holds there); the n-step entry points for one outside its VALID part, [0, n_valid).
       j = (uint64_t)a.idx[m0 + t];
-      j = j < n_valid ? j : 0;
+      j = j < (NSTEP ? n_valid : S * B) ? j : 0;
     } else {
       const uint64_t u = replay_bits(a.seed, m0 + t, a.draw);
       j = __umul64hi(u, n_valid);
     }
-    const uint64_t sl = j / B;      // below min(head, S)
+    const uint64_t sl = j / B;      // n-step: below min(head, S)
     s_slot[t] = (uint32_t)sl;
     s_world[t] = (uint32_t)(j - sl * B);
     if (!FROM_IDX && job == 0) a.idx[m0 + t] = (int64_t)j;
-    if (walks) {      // the largest k the chain may reach: n - 1, the newest step, the step the loop restarted the world after
-      const uint64_t ahead = (head - 1 - sl) % S;
-      uint64_t lim = ahead < ns.n - 1 ? ahead : ns.n - 1;
-      if (ns.L) {
-        const uint64_t c0 = (head - ahead + ns.phase) % ns.L;      // (g + 1 + p) mod L
-        const uint64_t cut = c0 ? ns.L - c0 : 0;                   // the first k with (g + k + 1 + p) mod L == 0
-        lim = cut < lim ? cut : lim;
+    if constexpr (NSTEP) {
+      if (walks) {      // the largest k the chain may reach: n - 1, the newest step, the step the loop restarted the world after
+        const uint64_t ahead = (head - 1 - sl) % S;
+        uint64_t lim = ahead < ns.n - 1 ? ahead : ns.n - 1;
+        if (ns.L) {
+          const uint64_t c0 = (head - ahead + ns.phase) % ns.L;      // (g + 1 + p) mod L
+          const uint64_t cut = c0 ? ns.L - c0 : 0;                   // the first k with (g + k + 1 + p) mod L == 0
+          lim = cut < lim ? cut : lim;
+        }
+        s_ns.lim[t] = (uint32_t)lim;
       }
-      s_lim[t] = (uint32_t)lim;
     }
   }
   __syncthreads();
-  if (walks) {
-    for (uint32_t e = t; e < ns.n * kReplayTile; e += 256) {
-      const uint32_t k = e / kReplayTile, r = e % kReplayTile;
-      if (r < n && k < s_lim[r]) {      // (the step at s_lim ends the chain whatever its done bytes say)
-        uint64_t sl = (uint64_t)s_slot[r] + k;
-        sl = sl >= S ? sl - S : sl;
-        const uint8_t *d = a.done + sl * A * B + s_world[r];
-        uint32_t any = 0;
+  if constexpr (NSTEP) {
+    if (walks) {
+      for (uint32_t e = t; e < ns.n * kReplayTile; e += 256) {
+        const uint32_t k = e / kReplayTile, r = e % kReplayTile;
+        if (r < n && k < s_ns.lim[r]) {      // (the step at lim ends the chain whatever its done bytes say)
+          uint64_t sl = (uint64_t)s_slot[r] + k;
+          sl = sl >= S ? sl - S : sl;
+          const uint8_t *d = a.done + sl * A * B + s_world[r];
+          uint32_t any = 0;
 #pragma unroll 4
-        for (uint32_t i = 0; i < A; ++i) any |= d[(uint64_t)i * B];
-        s_stop[k][r] = any != 0;
+          for (uint32_t i = 0; i < A; ++i) any |= d[(uint64_t)i * B];
+          s_ns.stop[k][r] = any != 0;
+        }
       }
+      __syncthreads();
+      if (t < n) {
+        const uint32_t lim = s_ns.lim[t];
+        uint32_t k = 0;
+        while (k < lim && !s_ns.stop[k][t]) ++k;
+        uint64_t sl = (uint64_t)s_slot[t] + k;
+        sl = sl >= S ? sl - S : sl;
+        s_ns.m[t] = k + 1;
+        s_ns.last[t] = (uint32_t)sl;
+      }
+      __syncthreads();
     }
-    __syncthreads();
-    if (t < n) {
-      const uint32_t lim = s_lim[t];
-      uint32_t k = 0;
-      while (k < lim && !s_stop[k][t]) ++k;
-      uint64_t sl = (uint64_t)s_slot[t] + k;
-      sl = sl >= S ? sl - S : sl;
-      s_m[t] = k + 1;
-      s_last[t] = (uint32_t)sl;
-    }
-    __syncthreads();
   }
   if (job < 2 * A) {
     const bool nx = job >= A;
@@ -237,14 +198,15 @@ __global__ __launch_bounds__(256) void k_replay_nstep(const ReplaySampleArgs a, 
     float *d1 = (nx ? a.o_next : a.o_obs) + (uint64_t)a.off[i] * M + m0 * W;
     float *jt = nx ? a.joint_next : a.joint;
     const uint32_t w2 = nx ? (uint32_t)a.d_sum : (uint32_t)a.joint_width;
-    gather_rows(src, (uint64_t)a.d_sum * B, W, a.magic[i], d1, jt ? jt + m0 * w2 + a.off[i] : nullptr, w2, nx ? s_last : s_slot, s_world,
-                n);
+    const uint32_t *slots = s_slot;
+    if constexpr (NSTEP) slots = nx ? s_ns.last : s_slot;
+    gather_rows(src, (uint64_t)a.d_sum * B, W, a.magic[i], d1, jt ? jt + m0 * w2 + a.off[i] : nullptr, w2, slots, s_world, n);
   } else if (job < 3 * A) {
     const uint32_t i = job - 2 * A, W = MPE_ACTION_DIM;
     float *jt = a.joint && a.col_move[i] >= 0 ? a.joint + m0 * (uint32_t)a.joint_width + a.col_move[i] : nullptr;
     gather_rows(a.act + (uint64_t)i * B * W, (uint64_t)A * B * W, W, 0x33333334u, a.o_act + ((uint64_t)i * M + m0) * W, jt,
                 (uint32_t)a.joint_width, s_slot, s_world, n);
-  } else if (!last_job) {
+  } else if (job < rew_job) {      // (only with dim_c > 0: otherwise rew_job == 3 * A)
     const uint32_t i = job - 3 * A, W = (uint32_t)a.dim_c;
     float *jt = a.joint && a.col_utter[i] >= 0 ? a.joint + m0 * (uint32_t)a.joint_width + a.col_utter[i] : nullptr;
     gather_rows(a.utter + (uint64_t)i * B * W, (uint64_t)A * B * W, W, a.magic_c, a.o_utter + ((uint64_t)i * M + m0) * W, jt,
@@ -253,31 +215,37 @@ __global__ __launch_bounds__(256) void k_replay_nstep(const ReplaySampleArgs a, 
     for (uint32_t e = t; e < A * kReplayTile; e += 256) {      // lanes over a tile's samples of one agent
       const uint32_t i = e / kReplayTile, r = e % kReplayTile;
       if (r < n) {
-        const uint32_t m = s_m[r];
         const uint64_t w = s_world[r], slot = s_slot[r];
-        float v[MPE_REPLAY_MAX_NSTEP];      // the chain's rewards: independent loads (statically indexed: registers)
-#pragma unroll
-        for (uint32_t k = 0; k < MPE_REPLAY_MAX_NSTEP; ++k) {
-          uint64_t sl = slot + k;
-          sl = sl >= S ? sl - S : sl;
-          v[k] = k < m ? a.rew[(sl * A + i) * B + w] : 0.f;
-        }
-        float d = 1.f, ret = v[0];
-#pragma unroll
-        for (uint32_t k = 1; k < MPE_REPLAY_MAX_NSTEP; ++k) {
-          if (k < m) {
-            d = d * ns.gamma;
-            ret = ret + d * v[k];
-          }
-        }
         const uint64_t o = (uint64_t)i * M + m0 + r;
-        a.o_rew[o] = v[0];
-        a.o_done[o] = a.done[((uint64_t)s_last[r] * A + i) * B + w];
-        ns.ret[o] = ret;
-        if (i == 0) {
-          ns.discount[m0 + r] = d * ns.gamma;
-          ns.n_used[m0 + r] = (int32_t)m;
-          ns.last[m0 + r] = (int64_t)((uint64_t)s_last[r] * B + w);
+        if constexpr (!NSTEP) {
+          const uint64_t from = (slot * A + i) * B + w;
+          a.o_rew[o] = a.rew[from];
+          a.o_done[o] = a.done[from];
+        } else {
+          const uint32_t m = s_ns.m[r];
+          float v[MPE_REPLAY_MAX_NSTEP];      // the chain's rewards: independent loads (statically indexed: registers)
+#pragma unroll
+          for (uint32_t k = 0; k < MPE_REPLAY_MAX_NSTEP; ++k) {
+            uint64_t sl = slot + k;
+            sl = sl >= S ? sl - S : sl;
+            v[k] = k < m ? a.rew[(sl * A + i) * B + w] : 0.f;
+          }
+          float d = 1.f, ret = v[0];
+#pragma unroll
+          for (uint32_t k = 1; k < MPE_REPLAY_MAX_NSTEP; ++k) {
+            if (k < m) {
+              d = d * ns.gamma;
+              ret = ret + d * v[k];
+            }
+          }
+          a.o_rew[o] = v[0];
+          a.o_done[o] = a.done[((uint64_t)s_ns.last[r] * A + i) * B + w];
+          ns.ret[o] = ret;
+          if (i == 0) {
+            ns.discount[m0 + r] = d * ns.gamma;
+            ns.n_used[m0 + r] = (int32_t)m;
+            ns.last[m0 + r] = (int64_t)((uint64_t)s_ns.last[r] * B + w);
+          }
         }
       }
     }
@@ -310,21 +278,15 @@ int launch_replay_push(const ReplayPushArgs &a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
-int launch_replay_sample(const ReplaySampleArgs &a, hipStream_t stream, bool from_idx) {
+// ns: the n-step arguments, or nullptr for the one-step kernels
+int launch_replay_sample(const ReplaySampleArgs &a, const ReplayNStepArgs *ns, hipStream_t stream, bool from_idx) {
   const uint64_t tiles = (a.M + kReplayTile - 1) / kReplayTile;
-  const unsigned jobs = (unsigned)((a.dim_c > 0 ? 4 : 3) * a.A + 1);
-  if (tiles == 0 || tiles > 0x7fffffffull) return (int)hipErrorInvalidConfiguration;
-  if (from_idx) hipLaunchKernelGGL(k_replay_sample<true>, dim3((unsigned)tiles, jobs), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(k_replay_sample<false>, dim3((unsigned)tiles, jobs), dim3(256), 0, stream, a);
-  return (int)hipGetLastError();
-}
-
-int launch_replay_nstep(const ReplaySampleArgs &a, const ReplayNStepArgs &ns, hipStream_t stream, bool from_idx) {
-  const uint64_t tiles = (a.M + kReplayTile - 1) / kReplayTile;
-  const unsigned jobs = (unsigned)((a.dim_c > 0 ? 4 : 3) * a.A + 1);
-  if (tiles == 0 || tiles > 0x7fffffffull || ns.n < 1 || ns.n > MPE_REPLAY_MAX_NSTEP) return (int)hipErrorInvalidConfiguration;
-  if (from_idx) hipLaunchKernelGGL(k_replay_nstep<true>, dim3((unsigned)tiles, jobs), dim3(256), 0, stream, a, ns);
-  else hipLaunchKernelGGL(k_replay_nstep<false>, dim3((unsigned)tiles, jobs), dim3(256), 0, stream, a, ns);
+  if (tiles == 0 || tiles > 0x7fffffffull || (ns && (ns->n < 1 || ns->n > MPE_REPLAY_MAX_NSTEP))) return (int)hipErrorInvalidConfiguration;
+  const dim3 grid((unsigned)tiles, (unsigned)((a.dim_c > 0 ? 4 : 3) * a.A + 1)), block(256);
+  if (ns && from_idx) hipLaunchKernelGGL((k_replay_sample<true, true>), grid, block, 0, stream, a, *ns);
+  else if (ns) hipLaunchKernelGGL((k_replay_sample<false, true>), grid, block, 0, stream, a, *ns);
+  else if (from_idx) hipLaunchKernelGGL((k_replay_sample<true, false>), grid, block, 0, stream, a, NoNStep{});
+  else hipLaunchKernelGGL((k_replay_sample<false, false>), grid, block, 0, stream, a, NoNStep{});
   return (int)hipGetLastError();
 }
 

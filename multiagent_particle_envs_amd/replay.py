@@ -235,13 +235,6 @@ class ReplayBuffer(object):
         self._batches[key] = b
         return b
 
-    def _gather_into(self, b, M, idx, joint):
-        _abi.check(_abi.lib().mpe_replay_gather(
-            C.byref(self._desc), M, idx.data_ptr(), b._obs.data_ptr(), b._next.data_ptr(), b.act.data_ptr(),
-            b.utter.data_ptr() if b.utter is not None else None, b.rew.data_ptr(), b._done_u8.data_ptr(),
-            b.joint.data_ptr() if joint else None, b.joint_next.data_ptr() if joint else None,
-            _abi.raw_stream(self.world.device)), "mpe_replay_gather")
-
     def _nstep(self, who, n_step, gamma, episode_len, episode_phase):
         """The checked MpeReplayNStep of a call (the ABI refuses the same by name; here before anything else is looked at)."""
         if gamma is None:
@@ -259,18 +252,41 @@ class ReplayBuffer(object):
         ns.n, ns.gamma, ns.episode_len, ns.episode_phase = n, g, L, p
         return ns
 
-    def _nstep_into(self, b, M, joint, ns, idx=None, draw=0):
-        """The one launch of an n-step batch: idx given: read (mpe_replay_gather_nstep), else drawn into b.idx."""
-        L = _abi.lib()
-        outs = (b._obs.data_ptr(), b._next.data_ptr(), b.act.data_ptr(), b.utter.data_ptr() if b.utter is not None else None,
-                b.rew.data_ptr(), b._done_u8.data_ptr(), b.joint.data_ptr() if joint else None,
-                b.joint_next.data_ptr() if joint else None, b.ret.data_ptr(), b.discount.data_ptr(), b.n_used.data_ptr(),
-                b.last.data_ptr(), _abi.raw_stream(self.world.device))
-        if idx is not None:
-            _abi.check(L.mpe_replay_gather_nstep(C.byref(self._desc), C.byref(ns), M, idx.data_ptr(), *outs), "mpe_replay_gather_nstep")
-        else:
-            _abi.check(L.mpe_replay_sample_nstep(C.byref(self._desc), C.byref(ns), M, int(draw) & (2 ** 64 - 1), b.idx.data_ptr(), *outs),
-                       "mpe_replay_sample_nstep")
+    def _launch(self, b, M, joint, ns=None, idx=None, draw=0):
+        """The one launch of a batch.  idx given: read (mpe_replay_gather), else drawn into b.idx with the draws of (seed, draw)
+        (mpe_replay_sample); ns given: the _nstep entry point of the two, which also takes the four n-step outputs."""
+        name = ("mpe_replay_sample" if idx is None else "mpe_replay_gather") + ("" if ns is None else "_nstep")
+        args = (C.byref(self._desc),) + (() if ns is None else (C.byref(ns),)) + (M,)
+        args += (int(draw) & (2 ** 64 - 1), b.idx.data_ptr()) if idx is None else (idx.data_ptr(),)
+        args += (b._obs.data_ptr(), b._next.data_ptr(), b.act.data_ptr(), b.utter.data_ptr() if b.utter is not None else None,
+                 b.rew.data_ptr(), b._done_u8.data_ptr(), b.joint.data_ptr() if joint else None,
+                 b.joint_next.data_ptr() if joint else None)
+        if ns is not None:
+            args += (b.ret.data_ptr(), b.discount.data_ptr(), b.n_used.data_ptr(), b.last.data_ptr())
+        _abi.check(getattr(_abi.lib(), name)(*args, _abi.raw_stream(self.world.device)), name)
+
+    def _idx_arg(self, who, idx):
+        """idx as gather and update_priorities take it."""
+        if not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() < 1 or not idx.is_contiguous() or \
+                idx.device != self.world.device:
+            raise _abi.MpeError("%s: idx is a contiguous int64 [M] tensor (M >= 1) on the env's device" % who)
+
+    def _sample_args(self, who, M, n_step, gamma, episode_len, episode_phase):
+        """The refusals both sample methods begin with -> (M, the checked MpeReplayNStep or None)."""
+        M = int(M)
+        if M < 1:
+            raise _abi.MpeError("%s: M = %d samples (need at least 1)" % (who, M))
+        ns = None if n_step is None else self._nstep(who, n_step, gamma, episode_len, episode_phase)
+        if self.count < 1:
+            raise _abi.MpeError("%s: the buffer is empty (nothing was pushed)" % who)
+        return M, ns
+
+    def _draw_arg(self, draw):
+        """draw=None: the internal draw counter, advanced here -- so only after a sample method's last refusal."""
+        if draw is None:
+            draw = self._draw
+            self._draw += 1
+        return draw
 
     def gather(self, idx, joint=False, n_step=None, gamma=None, episode_len=0, episode_phase=0):
         """One launch: the transitions idx names (a contiguous int64 [M] tensor on the env's device, slot * steps' worlds + world,
@@ -280,18 +296,13 @@ class ReplayBuffer(object):
         (M, joint, "nstep"); there an index outside the VALID part of the ring, [0, len(self)), gathers transition 0."""
         joint = bool(joint)
         ns = None if n_step is None else self._nstep("ReplayBuffer.gather", n_step, gamma, episode_len, episode_phase)
-        if not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() < 1 or not idx.is_contiguous() or \
-                idx.device != self.world.device:
-            raise _abi.MpeError("ReplayBuffer.gather: idx is a contiguous int64 [M] tensor (M >= 1) on the env's device")
+        self._idx_arg("ReplayBuffer.gather", idx)
         if self.count < 1:
             raise _abi.MpeError("ReplayBuffer.gather: the buffer is empty (nothing was pushed)")
         M = int(idx.numel())
         b = self._batch(M, joint, gathered=True, nstep=ns is not None)
         b.idx = idx
-        if ns is None:
-            self._gather_into(b, M, idx, joint)
-        else:
-            self._nstep_into(b, M, joint, ns, idx=idx)
+        self._launch(b, M, joint, ns, idx=idx)
         return b
 
     # ---- taking pushes back (PolicyLoop.capture's warm-up steps) ----------------------------------------------------------------
@@ -313,25 +324,10 @@ class ReplayBuffer(object):
         the world is restarted after every push number t with (t + 1 + episode_phase) % episode_len == 0, episode_phase being
         the episode-step index of push number 0.  For a PolicyLoop(env, pi, episode_len=L) whose first pushed step was loop
         step t0, pass episode_len=L, episode_phase=t0 % L.  episode_len=0: no restarts."""
-        M, joint = int(M), bool(joint)
-        if M < 1:
-            raise _abi.MpeError("ReplayBuffer.sample: M = %d samples (need at least 1)" % M)
-        ns = None if n_step is None else self._nstep("ReplayBuffer.sample", n_step, gamma, episode_len, episode_phase)
-        if self.count < 1:
-            raise _abi.MpeError("ReplayBuffer.sample: the buffer is empty (nothing was pushed)")
-        if draw is None:
-            draw = self._draw
-            self._draw += 1
-        if ns is not None:
-            b = self._batch(M, joint, nstep=True)
-            self._nstep_into(b, M, joint, ns, draw=draw)
-            return b
-        b = self._batch(M, joint)
-        _abi.check(_abi.lib().mpe_replay_sample(
-            C.byref(self._desc), M, int(draw) & (2 ** 64 - 1), b.idx.data_ptr(), b._obs.data_ptr(), b._next.data_ptr(), b.act.data_ptr(),
-            b.utter.data_ptr() if b.utter is not None else None, b.rew.data_ptr(), b._done_u8.data_ptr(),
-            b.joint.data_ptr() if joint else None, b.joint_next.data_ptr() if joint else None,
-            _abi.raw_stream(self.world.device)), "mpe_replay_sample")
+        joint = bool(joint)
+        M, ns = self._sample_args("ReplayBuffer.sample", M, n_step, gamma, episode_len, episode_phase)
+        b = self._batch(M, joint, nstep=ns is not None)
+        self._launch(b, M, joint, ns, draw=self._draw_arg(draw))
         return b
 
 
@@ -423,27 +419,18 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         whose low 24 bits replace the drawn bits (tests, quasi-random sequences).  n_step (with gamma; episode_len,
         episode_phase: ReplayBuffer.sample): the same draw, then mpe_replay_gather_nstep in place of the gather -> a
         PrioritizedNStepReplayBatch; update_td(batch.idx, td) as before."""
-        M, joint = int(M), bool(joint)
-        if M < 1:
-            raise _abi.MpeError("PrioritizedReplayBuffer.sample: M = %d samples (need at least 1)" % M)
-        ns = None if n_step is None else self._nstep("PrioritizedReplayBuffer.sample", n_step, gamma, episode_len, episode_phase)
-        if self.count < 1:
-            raise _abi.MpeError("PrioritizedReplayBuffer.sample: the buffer is empty (nothing was pushed)")
+        joint = bool(joint)
+        M, ns = self._sample_args("PrioritizedReplayBuffer.sample", M, n_step, gamma, episode_len, episode_phase)
         if u24 is not None and (not torch.is_tensor(u24) or u24.dtype != torch.int32 or tuple(u24.shape) != (M,) or
                                 not u24.is_contiguous() or u24.device != self.world.device):
             raise _abi.MpeError("PrioritizedReplayBuffer.sample: u24 is a contiguous int32 [%d] tensor on the env's device" % M)
-        if draw is None:
-            draw = self._draw
-            self._draw += 1
+        draw = self._draw_arg(draw)
         b = self._batch(M, joint, nstep=ns is not None)
         stream = _abi.raw_stream(self.world.device)
         _abi.check(_abi.lib().mpe_replay_prio_draw(
             C.byref(self._desc), C.byref(self._prio), M, int(draw) & (2 ** 64 - 1), u24.data_ptr() if u24 is not None else None,
             b.idx.data_ptr(), b.prio.data_ptr(), b.total.data_ptr(), b.n_valid.data_ptr(), stream), "mpe_replay_prio_draw")
-        if ns is None:
-            self._gather_into(b, M, b.idx, joint)
-        else:
-            self._nstep_into(b, M, joint, ns, idx=b.idx)
+        self._launch(b, M, joint, ns, idx=b.idx)
         return b
 
     def update_priorities(self, idx, priority):
@@ -452,9 +439,7 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         contiguous, on the env's device.  2 + (levels - 1) launches."""
         self._alloc()
         dev = self.world.device
-        if not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() < 1 or not idx.is_contiguous() or \
-                idx.device != dev:
-            raise _abi.MpeError("PrioritizedReplayBuffer.update_priorities: idx is a contiguous int64 [M] tensor (M >= 1) on the env's device")
+        self._idx_arg("PrioritizedReplayBuffer.update_priorities", idx)
         if not torch.is_tensor(priority) or priority.dtype != torch.float32 or priority.shape != idx.shape or \
                 not priority.is_contiguous() or priority.device != dev:
             raise _abi.MpeError("PrioritizedReplayBuffer.update_priorities: priority is a contiguous float32 [%d] tensor on the env's device"

@@ -155,6 +155,54 @@ def test_sample_is_a_function_of_seed_and_draw(rings):
     assert np.array_equal(s.rew.cpu().numpy(), ring2.gather(s.idx.cpu().tolist())["rew"])
 
 
+def test_gather_of_a_never_pushed_slot_reads_the_ring_one_step_and_transition_0_n_step():
+    """The one place where the one-step and the n-step gather differ on purpose (include/mpe_hip.h): B = 7, S = 4, 3 pushes, so
+    transitions [21, 28) are in the ring but were never pushed.  mpe_replay_gather returns what the ring holds there (a pattern
+    written straight into slot 3) and transition 0 only outside [0, S * B); mpe_replay_gather_nstep returns transition 0 for both."""
+    B, S = 7, 4
+    env = mpe.make_env("simple_speaker_listener", batch_size=B, seed=1)
+    buf = ReplayBuffer(env, steps=S, seed=5)
+    ring = push_coded(buf, 3)
+    assert len(buf) == ring.n_valid() == 21 and buf.dim_c == 3
+    obs, moves, utter, nxt, rew, _ = R.coded_step(5, B, buf.obs_widths, buf.dim_c)      # step 5: in no pushed slot, nowhere zero
+    done_u8 = (1 + np.arange(buf.A * B, dtype=np.uint8)).reshape(buf.A, B)              # a byte of its own per (agent, world)
+    for i in range(buf.A):
+        buf.obs_n[3][i].copy_(dev(obs[i]))
+        buf.next_obs_n[3][i].copy_(dev(nxt[i]))
+        ring.obs[3][i][...], ring.next_obs[3][i][...] = obs[i], nxt[i]
+    buf.act[3].copy_(dev(moves)), buf.utter[3].copy_(dev(utter)), buf.rew[3].copy_(dev(rew)), buf._done_u8[3].copy_(dev(done_u8))
+    ring.act[3], ring.utter[3], ring.rew[3] = moves, utter, rew
+    ring_done = buf._done_u8.cpu().numpy()
+    assert all((x != 0).all() for x in obs + nxt + [moves, utter, rew, done_u8])
+    idx = torch.tensor([3, 21, 27, 28, -1, 2 ** 62, 0], dtype=torch.int64).cuda()
+
+    def check(b, want):
+        g = ring.gather(want)
+        sl, wd = [j // B for j in want], [j % B for j in want]
+        for i in range(buf.A):
+            assert np.array_equal(b.obs_n[i].cpu().numpy(), g["obs_n"][i]), i
+            assert np.array_equal(b.next_obs_n[i].cpu().numpy(), g["next_obs_n"][i]), i
+            assert np.array_equal(b._done_u8[i].cpu().numpy(), ring_done[sl, i, wd]), i
+        for f in ("act", "utter", "rew"):
+            assert np.array_equal(getattr(b, f).cpu().numpy(), g[f]), f
+        assert torch.equal(b.joint, torch.cat([b.obs_n[0], b.obs_n[1], b.utter[0], b.act[1]], dim=1))
+        assert torch.equal(b.joint_next, torch.cat(b.next_obs_n, dim=1))
+
+    b = buf.gather(idx, joint=True)
+    torch.cuda.synchronize()
+    check(b, [3, 21, 27, 0, 0, 0, 0])
+    assert b.idx is idx
+    assert np.array_equal(b.rew[:, 1:3].cpu().numpy(), rew[:, [0, 6]])      # 21 and 27: slot 3's pattern, worlds 0 and 6
+    assert np.array_equal(b._done_u8[:, 1:3].cpu().numpy(), done_u8[:, [0, 6]])
+    assert np.array_equal(b.joint[1:3, :buf.obs_widths[0]].cpu().numpy(), obs[0][[0, 6]])
+    nb = buf.gather(idx, joint=True, n_step=1, gamma=0.5)
+    torch.cuda.synchronize()
+    check(nb, [3, 0, 0, 0, 0, 0, 0])
+    assert nb.last.cpu().tolist() == [3, 0, 0, 0, 0, 0, 0] and nb.n_used.cpu().tolist() == [1] * 7
+    assert torch.equal(nb.ret, nb.rew) and nb.discount.cpu().tolist() == [0.5] * 7
+    assert torch.equal(idx.cpu(), torch.tensor([3, 21, 27, 28, -1, 2 ** 62, 0]))      # (read, never written)
+
+
 def actors(env):
     torch.manual_seed(3)
     return [torch.nn.Sequential(torch.nn.Linear(d, 32), torch.nn.ReLU(), torch.nn.Linear(32, 5)).cuda() for d in

@@ -1,4 +1,4 @@
-"""n-step returns on the GPU (k_replay_nstep in csrc/mpe_replay.hip): one launch that draws or reads, walks,
+"""n-step returns on the GPU (the NSTEP instantiations of k_replay_sample in csrc/mpe_replay.hip): one launch that draws or reads, walks,
 sums and gathers.  The rule fixes the order of every float32 operation, so every comparison is equality -- bit-equal floats, equal
 integers -- against the restatement in tests/_replay_nstep_ref.py."""
 import numpy as np
