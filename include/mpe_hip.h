@@ -316,6 +316,8 @@ int mpe_step_server_wait(const MpeStepServer *srv, int64_t B, uint64_t steps_com
 #define MPE_POLICY_MAX_WIDTH 64
 #define MPE_POLICY_MAX_LAUNCH_WORK (1LL << 25) /* T * B * A of one mpe_rollout_policy launch (~0.1 s of kernel time)   */
 enum { MPE_POLICY_GREEDY = 0, MPE_POLICY_SAMPLE = 1, MPE_POLICY_SOFTMAX = 2 };
+#define MPE_POLICY_VALUE 3 /* an MpeActorSet of critics: mpe_critic_q alone accepts it, every other entry point refuses it as an
+                            * unknown mode                                                                                  */
 enum { MPE_POLICY_RELU = 0, MPE_POLICY_TANH = 1 };
 typedef struct MpePolicy {
   int32_t n_layers[MPE_POLICY_MAX_AGENTS];        /* Linear layers of agent i's actor, 1..3                                */
@@ -384,6 +386,45 @@ int mpe_actor_supported(const MpeActorSet *set, int64_t B);
  * outputs of the last layer, zero beyond n_out.                                                                             */
 int mpe_actor_act(const MpeActorSet *set, const float *const *obs_ptrs, int64_t B, uint64_t step, int64_t world_offset,
                   float *moves, float *utter, int32_t *ids, float *logp, float *logits, void *stream);
+
+/* ---- TD targets: target actors and target critics over M sampled rows, two launches of the kernel above ------
+ * mpe_actor_act_rows is mpe_actor_act over M rows of any origin (a sampled minibatch's next observations): B reads M, and row m
+ * stands where the world stood in the SAMPLE draws' key (world = row_offset + m).  moves, utter, ids, logp, logits: as above,
+ * [A][M]...; moves is optional here when joint is given.  joint (optional): the launch ALSO writes the centralised critic's
+ * input rows, row m at joint + m * joint_stride (floats):
+ *   THE JOINT-ROW RULE.  Columns are those of mpe_replay_sample's joint: every agent's observation first, in agent order (agent
+ *   i's D_i = width[i][0] floats at column off[i] = D_0 + .. + D_(i-1)); then, agent by agent, its move row (5 floats) if it is
+ *   movable, directly followed by its utterance row (dim_c floats) if it speaks.  The joint width is sum D_i + sum (5 * movable_i
+ *   + dim_c * speaks_i).  The observation columns are bit copies of the input rows; the action columns are the very floats the
+ *   launch writes to moves / utter.  Every column below the joint width of every row m < M is written exactly once; nothing at or
+ *   beyond the joint width of a row (joint_stride may be larger) and no row >= M is written.
+ * Refused by name (mpe_last_error): everything mpe_actor_act refuses, moves == NULL && joint == NULL, a joint that is not 4-byte
+ * aligned, a joint_stride below the joint width.  M == 0 returns 0 without a launch.                                         */
+int mpe_actor_act_rows(const MpeActorSet *set, const float *const *obs_ptrs, int64_t M, uint64_t step, int64_t row_offset,
+                       float *moves, float *utter, int32_t *ids, float *logp, float *logits, float *joint, int64_t joint_stride,
+                       void *stream);
+/* mpe_critic_q: one launch evaluates the set's A critics over M rows.  The set is an MpeActorSet in mode MPE_POLICY_VALUE: packed
+ * as an actor whose last layer has ONE output (width[i][n_layers[i]] == 1), movable, speaks and dim_c all 0; no head runs (no
+ * softmax, no draw, seed unused).  in_ptrs: HOST array of n_agents device pointers, critic i's contiguous [M][width[i][0]] input
+ * rows (the same pointer A times: centralised critics on one joint tensor; width[i][0] <= MPE_ACTOR_MAX_INPUT).  q [A][M]
+ * (required): critic i's output for row m, the k-ordered chain mpe_actor_act's logit 0 is.  td (optional) asks for the target:
+ *   THE TD-TARGET RULE.  y[i][m] = done[i][m] ? ret[i][m] : ret[i][m] + d_m * q[i][m], d_m = discount ? discount[m] : gamma, in
+ *   float32, the product rounded, then the sum rounded (no fused multiply-add).  It is a select, not a multiplication by
+ *   (1 - done): a row whose done is set gets y == ret exactly, whatever q is (inf, NaN).  With mpe_replay_sample_nstep's ret,
+ *   discount and done this is the n-step target ret + discount * (1 - done) * Q(next_obs).
+ * y [A][M] is required if and only if td is given.  Refused by name: everything mpe_actor_act refuses of a set (with the VALUE
+ * conditions above), td->ret or td->done NULL, a non-finite td->gamma when td->discount is NULL, q / y / ret / discount not 4-byte
+ * aligned.  M == 0 returns 0 without a launch.                                                                                */
+typedef struct MpeTdTarget {
+  const float *ret;                               /* [A][M] the (n-step) return                                             */
+  const uint8_t *done;                            /* [A][M] nonzero: the chain ended in a terminal step                     */
+  const float *discount;                          /* [M] gamma^m of the row's chain, or NULL: gamma for every row           */
+  float gamma;                                    /* read when discount is NULL                                             */
+  int32_t reserved_;
+} MpeTdTarget;
+size_t mpe_sizeof_td_target(void);
+int mpe_critic_q(const MpeActorSet *set, const float *const *in_ptrs, int64_t M, float *q, const MpeTdTarget *td, float *y,
+                 void *stream);
 
 /* ---- the replay buffer: the last S steps of all B worlds in device memory (csrc/mpe_replay.hip) ------------------------------
  * What an off-policy learner keeps beside the loop above: a ring of transitions (obs, action, reward, done, next obs) of every

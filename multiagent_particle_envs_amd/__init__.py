@@ -7,9 +7,10 @@ from .scenario import BaseScenario  # noqa: F401
 from . import core, scenarios  # noqa: F401
 from .rollout import MlpPolicy, PolicyRollout, PolicyTrajectory  # noqa: F401
 from .policy import Actors, PolicyLoop  # noqa: F401
+from .learner import Critics, TdTargets  # noqa: F401
 from .replay import (ReplayBuffer, ReplayBatch, NStepReplayBatch, PrioritizedReplayBuffer, PrioritizedReplayBatch,  # noqa: F401
                      PrioritizedNStepReplayBatch)
 
 __all__ = ["make_env", "MultiAgentEnv", "BatchMultiAgentEnv", "GraphedStep", "BaseScenario", "core", "scenarios", "MlpPolicy", "PolicyRollout",
-           "PolicyTrajectory", "Actors", "PolicyLoop", "ReplayBuffer", "ReplayBatch",
+           "PolicyTrajectory", "Actors", "PolicyLoop", "Critics", "TdTargets", "ReplayBuffer", "ReplayBatch",
            "PrioritizedReplayBuffer", "PrioritizedReplayBatch", "NStepReplayBatch", "PrioritizedNStepReplayBatch"]

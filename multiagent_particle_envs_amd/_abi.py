@@ -60,6 +60,7 @@ class MpeRenderArgs(C.Structure):      # include/mpe_hip.h: one mpe_render call
 MPE_POLICY_MAX_AGENTS, MPE_POLICY_MAX_LAYERS, MPE_POLICY_MAX_WIDTH = 16, 3, 64
 MPE_POLICY_MAX_LAUNCH_WORK = 1 << 25      # T * B * A of one mpe_rollout_policy launch
 MPE_POLICY_GREEDY, MPE_POLICY_SAMPLE, MPE_POLICY_SOFTMAX = 0, 1, 2
+MPE_POLICY_VALUE = 3                     # an MpeActorSet of critics (mpe_critic_q alone accepts it)
 MPE_POLICY_RELU, MPE_POLICY_TANH = 0, 1
 
 
@@ -79,6 +80,10 @@ class MpeActorSet(C.Structure):        # include/mpe_hip.h: the actors of one mp
                 ("width", (C.c_int32 * 4) * MPE_ACTOR_MAX_AGENTS), ("activation", C.c_int32 * MPE_ACTOR_MAX_AGENTS),
                 ("movable", C.c_uint8 * MPE_ACTOR_MAX_AGENTS), ("speaks", C.c_uint8 * MPE_ACTOR_MAX_AGENTS),
                 ("dim_c", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class MpeTdTarget(C.Structure):        # include/mpe_hip.h: what mpe_critic_q makes the TD target y from
+    _fields_ = [("ret", C.c_void_p), ("done", C.c_void_p), ("discount", C.c_void_p), ("gamma", C.c_float), ("reserved_", C.c_int32)]
 
 
 MPE_REPLAY_MAX_AGENTS, MPE_REPLAY_MAX_WIDTH = 16, 4096
@@ -203,6 +208,11 @@ EXPORTS = {
     "mpe_actor_supported": (C.c_int, [C.POINTER(MpeActorSet), C.c_int64]),
     "mpe_actor_act": (C.c_int, [C.POINTER(MpeActorSet), C.POINTER(C.c_void_p), C.c_int64, C.c_uint64, C.c_int64, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mpe_actor_act_rows": (C.c_int, [C.POINTER(MpeActorSet), C.POINTER(C.c_void_p), C.c_int64, C.c_uint64, C.c_int64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mpe_sizeof_td_target": (C.c_size_t, []),
+    "mpe_critic_q": (C.c_int, [C.POINTER(MpeActorSet), C.POINTER(C.c_void_p), C.c_int64, C.c_void_p, C.POINTER(MpeTdTarget),
+                               C.c_void_p, C.c_void_p]),
     "mpe_sizeof_replay": (C.c_size_t, []),
     "mpe_replay_supported": (C.c_int, [C.POINTER(MpeReplay)]),
     "mpe_replay_push": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
@@ -253,6 +263,7 @@ def lib():
             handle.mpe_sizeof_render_args() != C.sizeof(MpeRenderArgs) or handle.mpe_sizeof_policy() != C.sizeof(MpePolicy) or \
             handle.mpe_sizeof_actor_set() != C.sizeof(MpeActorSet) or handle.mpe_sizeof_replay() != C.sizeof(MpeReplay) or \
             handle.mpe_sizeof_replay_prio() != C.sizeof(MpeReplayPrio) or \
+            handle.mpe_sizeof_td_target() != C.sizeof(MpeTdTarget) or \
             handle.mpe_sizeof_replay_nstep() != C.sizeof(MpeReplayNStep):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")
     _lib = handle

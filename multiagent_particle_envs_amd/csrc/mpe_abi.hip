@@ -1198,13 +1198,16 @@ int mpe_render(const MpeScenarioDesc *d, const MpeRenderArgs *a, void *stream) {
 
 // ---- the standalone actor kernel (mpe_policy.hip) ---------------------------------------------------------------------------
 size_t mpe_sizeof_actor_set(void) { return sizeof(MpeActorSet); }
-static int check_actor_set(const MpeActorSet *s, const char *what) {
+static int check_actor_set(const MpeActorSet *s, const char *what, bool value = false) {
   if (!s) return fail(MPE_EINVAL, "%s: set is NULL", what);
   if (s->n_agents < 1) return fail(MPE_EINVAL, "%s: n_agents = %d (need at least 1)", what, s->n_agents);
   if (s->n_agents > MPE_ACTOR_MAX_AGENTS)
     return fail(MPE_EUNSUPPORTED, "%s: %d agents in one actor set (at most MPE_ACTOR_MAX_AGENTS = %d: split the agents over "
                 "several sets)", what, s->n_agents, MPE_ACTOR_MAX_AGENTS);
-  if (s->mode != MPE_POLICY_GREEDY && s->mode != MPE_POLICY_SAMPLE && s->mode != MPE_POLICY_SOFTMAX)
+  if (value) {
+    if (s->mode != MPE_POLICY_VALUE) return fail(MPE_EINVAL, "%s: mode %d (a critic set's mode is MPE_POLICY_VALUE)", what, s->mode);
+    if (s->dim_c != 0) return fail(MPE_EINVAL, "%s: dim_c = %d (a MPE_POLICY_VALUE set has no heads: dim_c is 0)", what, s->dim_c);
+  } else if (s->mode != MPE_POLICY_GREEDY && s->mode != MPE_POLICY_SAMPLE && s->mode != MPE_POLICY_SOFTMAX)
     return fail(MPE_EINVAL, "%s: mode %d (MPE_POLICY_GREEDY / SAMPLE / SOFTMAX)", what, s->mode);
   if (s->dim_c < 0 || s->dim_c > MPE_ACTOR_MAX_OUT) return fail(MPE_EINVAL, "%s: dim_c = %d (0..%d)", what, s->dim_c, MPE_ACTOR_MAX_OUT);
   for (int i = 0; i < s->n_agents; ++i) {
@@ -1224,7 +1227,11 @@ static int check_actor_set(const MpeActorSet *s, const char *what) {
                     MPE_POLICY_MAX_WIDTH);
     }
     const int mv = s->movable[i] ? 1 : 0, sp = s->speaks[i] ? 1 : 0;
-    const int n_out = MPE_ACTION_DIM * mv + s->dim_c * sp;
+    if (value && (mv || sp))
+      return fail(MPE_EINVAL, "%s: agent %d: movable = %d, speaks = %d (a MPE_POLICY_VALUE set has no heads: both are 0)", what, i, mv, sp);
+    if (value && s->width[i][nl] != 1)
+      return fail(MPE_EINVAL, "%s: agent %d: the last layer gives %d outputs (a critic's last layer has 1)", what, i, s->width[i][nl]);
+    const int n_out = value ? 1 : MPE_ACTION_DIM * mv + s->dim_c * sp;
     if (n_out < 1) return fail(MPE_EINVAL, "%s: agent %d neither moves nor speaks: it has no head", what, i);
     if (n_out > MPE_ACTOR_MAX_OUT)
       return fail(MPE_EUNSUPPORTED, "%s: agent %d: %d logits (5 * movable + dim_c * speaks) > MPE_ACTOR_MAX_OUT = %d", what, i, n_out,
@@ -1243,19 +1250,18 @@ int mpe_actor_supported(const MpeActorSet *s, int64_t B) {
   if (rc) return rc == MPE_EUNSUPPORTED ? 0 : rc;
   return B > 0 ? 1 : 0;
 }
-int mpe_actor_act(const MpeActorSet *s, const float *const *obs_ptrs, int64_t B, uint64_t step, int64_t world_offset, float *moves,
-                  float *utter, int32_t *ids, float *logp, float *logits, void *stream) {
-  const char *what = "mpe_actor_act";
-  if (int rc = check_actor_set(s, what)) return rc;
-  if (B < 0) return fail(MPE_EINVAL, "%s: B = %lld", what, (long long)B);
+// what the three launches of k_actor share: the checks in front of the entry's own, and the set's fields
+static int check_actor_call(const MpeActorSet *s, const float *const *obs_ptrs, int64_t B, const char *rows, const char *ptrs,
+                            const char *what) {
+  if (B < 0) return fail(MPE_EINVAL, "%s: %s = %lld", what, rows, (long long)B);
   if (!s->weights || ((uintptr_t)s->weights & 15)) return fail(MPE_EINVAL, "%s: set->weights is NULL or not 16-byte aligned", what);
-  if (!obs_ptrs) return fail(MPE_EINVAL, "%s: obs_ptrs is NULL", what);
-  if (!moves) return fail(MPE_EINVAL, "%s: moves is NULL", what);
-  if (logits && ((uintptr_t)logits & 15)) return fail(MPE_EINVAL, "%s: logits is not 16-byte aligned", what);
-  mpe::ActorArgs a;
-  std::memset(&a, 0, sizeof(a));
+  if (!obs_ptrs) return fail(MPE_EINVAL, "%s: %s is NULL", what, ptrs);
+  return 0;
+}
+static int fill_actor_args(const MpeActorSet *s, const float *const *obs_ptrs, int64_t B, const char *ptrs, const char *what,
+                           mpe::ActorArgs &a) {
   for (int i = 0; i < s->n_agents; ++i) {
-    if (!obs_ptrs[i]) return fail(MPE_EINVAL, "%s: obs_ptrs[%d] is NULL", what, i);
+    if (!obs_ptrs[i]) return fail(MPE_EINVAL, "%s: %s[%d] is NULL", what, ptrs, i);
     a.obs[i] = obs_ptrs[i];
     a.off[i] = (int32_t)s->offset[i];
     for (int l = 0; l < 4; ++l) a.width[i][l] = (int16_t)(l <= s->n_layers[i] ? s->width[i][l] : 0);
@@ -1265,20 +1271,99 @@ int mpe_actor_act(const MpeActorSet *s, const float *const *obs_ptrs, int64_t B,
     a.speaks[i] = s->speaks[i] ? 1 : 0;
   }
   a.w = s->weights;
+  a.seed = s->seed;
+  a.B = (uint64_t)B;
+  a.n_agents = s->n_agents;
+  a.mode = s->mode;
+  a.dim_c = s->dim_c;
+  return 0;
+}
+int mpe_actor_act(const MpeActorSet *s, const float *const *obs_ptrs, int64_t B, uint64_t step, int64_t world_offset, float *moves,
+                  float *utter, int32_t *ids, float *logp, float *logits, void *stream) {
+  const char *what = "mpe_actor_act";
+  if (int rc = check_actor_set(s, what)) return rc;
+  if (int rc = check_actor_call(s, obs_ptrs, B, "B", "obs_ptrs", what)) return rc;
+  if (!moves) return fail(MPE_EINVAL, "%s: moves is NULL", what);
+  if (logits && ((uintptr_t)logits & 15)) return fail(MPE_EINVAL, "%s: logits is not 16-byte aligned", what);
+  mpe::ActorArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (int rc = fill_actor_args(s, obs_ptrs, B, "obs_ptrs", what, a)) return rc;
   a.moves = moves;
   a.utter = utter;
   a.ids = ids;
   a.logp = logp;
   a.logits = logits;
-  a.seed = s->seed;
   a.step = step;
   a.world_offset = (uint64_t)world_offset;
-  a.B = (uint64_t)B;
-  a.n_agents = s->n_agents;
-  a.mode = s->mode;
-  a.dim_c = s->dim_c;
   if (B == 0) return 0;
   return hip_result(mpe::launch_actor(a, static_cast<hipStream_t>(stream)), what);
+}
+int mpe_actor_act_rows(const MpeActorSet *s, const float *const *obs_ptrs, int64_t M, uint64_t step, int64_t row_offset, float *moves,
+                       float *utter, int32_t *ids, float *logp, float *logits, float *joint, int64_t joint_stride, void *stream) {
+  const char *what = "mpe_actor_act_rows";
+  if (int rc = check_actor_set(s, what)) return rc;
+  if (int rc = check_actor_call(s, obs_ptrs, M, "M", "obs_ptrs", what)) return rc;
+  if (!moves && !joint) return fail(MPE_EINVAL, "%s: moves and joint are both NULL: the launch would write no action", what);
+  if (logits && ((uintptr_t)logits & 15)) return fail(MPE_EINVAL, "%s: logits is not 16-byte aligned", what);
+  mpe::ActorRowsArgs a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  if (int rc = fill_actor_args(s, obs_ptrs, M, "obs_ptrs", what, a)) return rc;
+  if (joint) {
+    // the columns of ReplayBatch.joint (replay_sample below): every observation in agent order, then per agent move | utter
+    int32_t col = 0;
+    for (int i = 0; i < s->n_agents; ++i) {
+      a.col_obs[i] = col;
+      col += s->width[i][0];
+    }
+    for (int i = 0; i < s->n_agents; ++i) {
+      a.col_move[i] = col;
+      col += s->movable[i] ? MPE_ACTION_DIM : 0;
+      a.col_utter[i] = col;
+      col += s->speaks[i] ? s->dim_c : 0;
+    }
+    if ((uintptr_t)joint & 3) return fail(MPE_EINVAL, "%s: joint is not 4-byte aligned", what);
+    if (joint_stride < col)
+      return fail(MPE_EINVAL, "%s: joint_stride = %lld floats is below the set's joint width %d", what, (long long)joint_stride, col);
+    a.joint = joint;
+    a.joint_stride = (uint64_t)joint_stride;
+  }
+  a.moves = moves;
+  a.utter = utter;
+  a.ids = ids;
+  a.logp = logp;
+  a.logits = logits;
+  a.step = step;
+  a.world_offset = (uint64_t)row_offset;
+  if (M == 0) return 0;
+  return hip_result(mpe::launch_actor_rows(a, static_cast<hipStream_t>(stream)), what);
+}
+size_t mpe_sizeof_td_target(void) { return sizeof(MpeTdTarget); }
+int mpe_critic_q(const MpeActorSet *s, const float *const *in_ptrs, int64_t M, float *q, const MpeTdTarget *td, float *y, void *stream) {
+  const char *what = "mpe_critic_q";
+  if (int rc = check_actor_set(s, what, true)) return rc;
+  if (int rc = check_actor_call(s, in_ptrs, M, "M", "in_ptrs", what)) return rc;
+  if (!q || ((uintptr_t)q & 3)) return fail(MPE_EINVAL, "%s: q is NULL or not 4-byte aligned", what);
+  if (td && !y) return fail(MPE_EINVAL, "%s: td is given and y is NULL", what);
+  if (!td && y) return fail(MPE_EINVAL, "%s: y is given and td is NULL", what);
+  mpe::CriticArgs a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  if (int rc = fill_actor_args(s, in_ptrs, M, "in_ptrs", what, a)) return rc;
+  if (td) {
+    if (!td->ret) return fail(MPE_EINVAL, "%s: td->ret is NULL", what);
+    if (!td->done) return fail(MPE_EINVAL, "%s: td->done is NULL", what);
+    if (!td->discount && !std::isfinite(td->gamma))
+      return fail(MPE_EINVAL, "%s: td->gamma = %g is not finite (and td->discount is NULL)", what, (double)td->gamma);
+    if (((uintptr_t)y & 3) || ((uintptr_t)td->ret & 3) || ((uintptr_t)td->discount & 3))
+      return fail(MPE_EINVAL, "%s: y, td->ret and td->discount must be 4-byte aligned", what);
+    a.y = y;
+    a.ret = td->ret;
+    a.done = td->done;
+    a.discount = td->discount;
+    a.gamma = td->gamma;
+  }
+  a.q = q;
+  if (M == 0) return 0;
+  return hip_result(mpe::launch_critic(a, static_cast<hipStream_t>(stream)), what);
 }
 
 // ---- the replay buffer (mpe_replay.hip) ---------------------------------------------------------------------------------------

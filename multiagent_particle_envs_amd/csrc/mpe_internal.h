@@ -111,6 +111,21 @@ struct ActorArgs {
   uint8_t nl[MPE_ACTOR_MAX_AGENTS], act[MPE_ACTOR_MAX_AGENTS], movable[MPE_ACTOR_MAX_AGENTS], speaks[MPE_ACTOR_MAX_AGENTS];
 };
 int launch_actor(const ActorArgs &a, hipStream_t stream);
+// the same kernel over M rows that also writes the critic's joint rows (mpe_actor_act_rows; B = M, world_offset = row_offset)
+struct ActorRowsArgs : ActorArgs {
+  float *joint;                                // [M][joint_stride] or nullptr (then moves is given)
+  uint64_t joint_stride;                       // floats from row to row, >= the set's joint width
+  int32_t col_obs[MPE_ACTOR_MAX_AGENTS], col_move[MPE_ACTOR_MAX_AGENTS], col_utter[MPE_ACTOR_MAX_AGENTS];      // first joint column
+};
+int launch_actor_rows(const ActorRowsArgs &a, hipStream_t stream);
+// ... and with a one-output last layer and no head: q and the TD target (mpe_critic_q; B = M)
+struct CriticArgs : ActorArgs {
+  float *q, *y;                                // [A][M]; y or nullptr
+  const float *ret, *discount;                 // [A][M]; [M] or nullptr (then gamma)
+  const uint8_t *done;                         // [A][M]
+  float gamma;
+};
+int launch_critic(const CriticArgs &a, hipStream_t stream);
 
 // the replay buffer (mpe_replay.hip): both launches' arguments, checked and filled by the caller (mpe_replay_push / _sample)
 constexpr int kReplayMaxSegs = 2 * MPE_REPLAY_MAX_AGENTS + 4;     // obs and next obs per agent, act, utter, rew, done

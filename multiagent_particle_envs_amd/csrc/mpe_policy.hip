@@ -16,6 +16,10 @@
 // LDS: the first layer's weights 32 input columns at a time (inputs wider than 32 stream through the k loop), the later
 // layers whole, a [64][17] logit / output tile per wave: 46.7 KB per workgroup.  The weight reads are ds_read_b32 of 32
 // distinct units of one [k] row per lane half: conflict-free.
+//
+// The kernel is a template over what follows the logits: the heads (mpe_actor_act), the heads plus the critic's
+// joint rows over M rows of any origin (mpe_actor_act_rows), or no head at all -- a one-output last layer read as q, and the TD
+// target y (mpe_critic_q).  The layers and the logits staging are the same code in all three.
 #include "mpe_device.h"
 #include "mpe_internal.h"
 
@@ -146,8 +150,23 @@ __device__ __forceinline__ void store_rows_n(float *stage, const float (&v)[N], 
   }
 }
 
+// the wave's 64 rows of n floats, as store_rows_n left them in the wave's tile -> n columns of the joint rows at g (row stride in
+// floats; g = row 0 of the wave, first column of the run): the very floats the contiguous run got
+__device__ __forceinline__ void store_rows_joint(const float *stage, int n, float *__restrict__ g, size_t stride, int nlive, int lane) {
+  for (int idx = lane; idx < nlive * n; idx += 64) {
+    const int r = idx / n;
+    g[(size_t)r * stride + (idx - r * n)] = stage[idx];
+  }
+}
+
+// What happens once lg[16] is in the lane.  kActHeads: mpe_actor_act, the heads.  kActRows: mpe_actor_act_rows,
+// the heads, and each row's observation / move / utterance columns of the critic's joint row.  kActValue: mpe_critic_q, no head:
+// the one output is q, and y = done ? ret : ret + d * q.
+enum { kActHeads = 0, kActRows = 1, kActValue = 2 };
+
+template <int KIND, class Args>
 __global__ void __launch_bounds__(kActThreads) __attribute__((amdgpu_waves_per_eu(2)))
-k_actor(const ActorArgs p) {
+k_actor(const Args p) {
   __shared__ __attribute__((aligned(16))) float sW0[kKC * kHW];
   __shared__ __attribute__((aligned(16))) float sB0[kHW];
   __shared__ __attribute__((aligned(16))) float sRest[(kHW + 1) * kHW + (kHW + 1) * kLW];      // [W1 | b1 |] WL | bL, as packed
@@ -199,6 +218,19 @@ k_actor(const ActorArgs p) {
   const int nlive = w0 < B ? (int)min((size_t)kActWaveWorlds, B - w0) : 0;
   const bool live = lane < nlive;
   const size_t row = (size_t)ag * B + w0;      // this wave's first [agent][world] row
+  if constexpr (KIND == kActValue) {
+    if (live) {
+      const float q = lg[0];
+      p.q[row + lane] = q;
+      if (p.y) {
+        const float r = p.ret[row + lane];
+        const float d = p.discount ? p.discount[w0 + lane] : p.gamma;
+        const float dq = d * q;      // (the product and the sum are rounded one by one: -ffp-contract=off)
+        p.y[row + lane] = p.done[row + lane] ? r : r + dq;
+      }
+    }
+    return;
+  }
   if (p.logits && live) {
     float4 *g = reinterpret_cast<float4 *>(p.logits + (row + lane) * kLW);
 #pragma unroll
@@ -217,7 +249,24 @@ k_actor(const ActorArgs p) {
     id_m = pol_head<MPE_ACTION_DIM>(z5, MPE_ACTION_DIM, p.mode, bits, mv, lp);
     logp = lp;
   }
-  store_rows_n<MPE_ACTION_DIM>(stage, mv, MPE_ACTION_DIM, p.moves + row * MPE_ACTION_DIM, nlive, lane);
+  float *gmoves = p.moves + row * MPE_ACTION_DIM;
+  if constexpr (KIND == kActRows)
+    if (!p.moves) gmoves = nullptr;
+  store_rows_n<MPE_ACTION_DIM>(stage, mv, MPE_ACTION_DIM, gmoves, nlive, lane);
+  float *jrow = nullptr;      // the wave's first joint row
+  if constexpr (KIND == kActRows) {
+    if (p.joint) {
+      jrow = p.joint + w0 * p.joint_stride;
+      if (movable) store_rows_joint(stage, MPE_ACTION_DIM, jrow + p.col_move[ag], p.joint_stride, nlive, lane);
+      // the observation columns: bit copies of the wave's nlive * D input floats
+      const uint32_t *src = reinterpret_cast<const uint32_t *>(obs + w0 * (size_t)D);
+      uint32_t *dst = reinterpret_cast<uint32_t *>(jrow + p.col_obs[ag]);
+      for (int idx = lane; idx < nlive * D; idx += 64) {
+        const int r = idx / D;
+        dst[(size_t)r * p.joint_stride + (idx - r * D)] = src[idx];
+      }
+    }
+  }
   // ---- the utterance head: the last dim_c logits (a silent agent's row is zeros)
   int id_c = -1;
   if (p.dim_c > 0 && (p.utter || speaks)) {
@@ -234,6 +283,8 @@ k_actor(const ActorArgs p) {
       logp = movable ? logp + lp : lp;
     }
     store_rows_n<kLW>(stage, ut, p.dim_c, p.utter ? p.utter + row * (size_t)p.dim_c : nullptr, nlive, lane);
+    if constexpr (KIND == kActRows)
+      if (jrow && speaks) store_rows_joint(stage, p.dim_c, jrow + p.col_utter[ag], p.joint_stride, nlive, lane);
   }
   if (live) {
     if (p.ids) {
@@ -246,12 +297,17 @@ k_actor(const ActorArgs p) {
 
 }  // namespace
 
-int launch_actor(const ActorArgs &a, hipStream_t stream) {
+template <int KIND, class Args>
+static int launch(const Args &a, hipStream_t stream) {
   const size_t tiles = (a.B + kActWgWorlds - 1) / kActWgWorlds;
   if (tiles == 0) return 0;
   if (tiles > 0x7fffffffull) return MPE_EINVAL;
-  hipLaunchKernelGGL(k_actor, dim3((unsigned)tiles, (unsigned)a.n_agents), dim3(kActThreads), 0, stream, a);
+  hipLaunchKernelGGL((k_actor<KIND, Args>), dim3((unsigned)tiles, (unsigned)a.n_agents), dim3(kActThreads), 0, stream, a);
   return (int)hipGetLastError();
 }
+
+int launch_actor(const ActorArgs &a, hipStream_t stream) { return launch<kActHeads>(a, stream); }
+int launch_actor_rows(const ActorRowsArgs &a, hipStream_t stream) { return launch<kActRows>(a, stream); }
+int launch_critic(const CriticArgs &a, hipStream_t stream) { return launch<kActValue>(a, stream); }
 
 }  // namespace mpe

@@ -35,6 +35,39 @@ def pack_actor16(module, n_out):
     return torch.cat(parts)
 
 
+def joint_layout(obs_widths, movable, speaks, dim_c):
+    """The columns of the centralised critic's joint row (include/mpe_hip.h, the joint-row rule; ReplayBatch.joint): every
+    observation first, in agent order, then per agent its move row [5] if movable, directly followed by its utterance row [dim_c]
+    if it speaks.  -> (off [A + 1], joint_width, col_move [A], col_utter [A]); a column an agent does not have is None."""
+    off = [0]
+    for d in obs_widths:
+        off.append(off[-1] + int(d))
+    col, col_move, col_utter = off[-1], [], []
+    for m, sp in zip(movable, speaks):
+        col_move.append(col if m else None)
+        col += _abi.MPE_ACTION_DIM if m else 0
+        col_utter.append(col if sp else None)
+        col += dim_c if sp else 0
+    return off, col, col_move, col_utter
+
+
+def env_joint_layout(env, who):
+    """joint_layout of an env's agents, read off the env as Actors and ReplayBuffer read it."""
+    w = env.world
+    off = getattr(env, "_obs_off", None)
+    if off is None:
+        raise _abi.MpeError("%s: this env has no device-side observation layout (env.fused is False)" % who)
+    A = len(w.agents)
+    speaks = [not a.silent for a in w.agents]
+    return joint_layout([int(off[i + 1] - off[i]) for i in range(A)], [bool(a.movable) for a in w.agents], speaks,
+                        int(w.dim_c) if any(speaks) else 0)
+
+
+class _Rows(object):
+    """The outputs of Actors.act_rows for one M."""
+    __slots__ = ("moves", "utter", "logp", "ids", "logits", "joint", "action")
+
+
 class Actors(object):
     """Per-agent MLP actors for any env: `modules` is one nn.Sequential per agent, or one module every agent shares (Linear layers
     with ReLU / Tanh between them, at most 3 Linear layers, hidden widths <= 64, float32).  Agent i's first Linear takes its
@@ -69,6 +102,9 @@ class Actors(object):
             raise _abi.MpeError("Actors: %d actors for %d agents" % (len(self.modules), self.A))
         self._want = (bool(logp), bool(ids), bool(logits))
         self.moves = self.utter = self.logp = self.ids = self.logits = None
+        self.off, self.joint_width, self.col_move, self.col_utter = joint_layout(self.obs_widths, self.movable, self.speaks, self.dim_c)
+        self.rows = self.joint_rows = None
+        self._rows = {}
         self._frozen = None
         self._ptrs = {}
         self._check()
@@ -182,6 +218,69 @@ class Actors(object):
         if moves is None:
             return self._action
         return (mv, self.utter) if self.dim_c else mv
+
+    def _rows_out(self, M, joint):
+        """act_rows' own output tensors, one set per M (the [B]-sized buffers of act() are not touched)."""
+        r = self._rows.get(M)
+        if r is None:
+            A, dev = self.A, self.world.device
+            r = _Rows()
+            r.moves = torch.zeros((A, M, _abi.MPE_ACTION_DIM), dtype=torch.float32, device=dev)
+            r.utter = torch.zeros((A, M, self.dim_c), dtype=torch.float32, device=dev) if self.dim_c else None
+            r.action = (r.moves, r.utter) if self.dim_c else r.moves
+            logp, ids, logits = self._want
+            r.logp = torch.zeros((A, M), dtype=torch.float32, device=dev) if logp else None
+            r.ids = torch.zeros((2, A, M), dtype=torch.int32, device=dev) if ids else None
+            r.logits = torch.zeros((A, M, _LW), dtype=torch.float32, device=dev) if logits else None
+            r.joint = None
+            if len(self._rows) >= 16:
+                self._rows.clear()
+            self._rows[M] = r
+        if joint and r.joint is None:
+            r.joint = torch.zeros((M, self.joint_width), dtype=torch.float32, device=self.world.device)
+        return r
+
+    def act_rows(self, obs_n, t=0, row_offset=0, joint=None):
+        """act() over M rows of any origin (M = obs_n[0].shape[0]: a sampled minibatch's next_obs_n) in one launch
+        (mpe_actor_act_rows): row m's SAMPLE draws are those of world row_offset + m at step t.  joint=True: the same launch also
+        writes the centralised critic's input rows [M, joint_width] -- every observation, then the action rows just decided, in
+        ReplayBatch.joint's columns (self.off, col_move, col_utter) -- into a tensor of this object's; joint=a contiguous float32
+        [M, >= joint_width] device tensor: into that one.  -> what act() returns, [A,M,...]; self.joint_rows is the joint tensor
+        (None without joint) and self.rows holds every output of the call (moves, utter, logp, ids, logits, joint).  The tensors
+        are cached per M and rewritten by the next act_rows of that M."""
+        if len(obs_n) != self.A:
+            raise _abi.MpeError("Actors.act_rows: %d observation blocks for %d agents" % (len(obs_n), self.A))
+        if not torch.is_tensor(obs_n[0]) or obs_n[0].dim() != 2:
+            raise _abi.MpeError("Actors.act_rows: obs_n[0] is a contiguous float32 [M, %d] tensor on the env's device" % self.obs_widths[0])
+        M, dev = int(obs_n[0].shape[0]), self.world.device
+        key = (M,) + tuple(o.data_ptr() if torch.is_tensor(o) else None for o in obs_n)
+        arr = self._ptrs.get(key)
+        if arr is None:
+            for i, o in enumerate(obs_n):
+                if not torch.is_tensor(o) or o.dtype != torch.float32 or not o.is_contiguous() or o.device != dev or \
+                        tuple(o.shape) != (M, self.obs_widths[i]):
+                    raise _abi.MpeError("Actors.act_rows: obs_n[%d] is a contiguous float32 [%d, %d] tensor on the env's device"
+                                        % (i, M, self.obs_widths[i]))
+            if len(self._ptrs) >= 64:
+                self._ptrs.clear()
+            arr = self._ptrs[key] = (C.c_void_p * self.A)(*key[1:])
+        own = joint is True
+        if joint is not None and joint is not False and not own:
+            if not torch.is_tensor(joint) or joint.dtype != torch.float32 or joint.dim() != 2 or joint.shape[0] != M or \
+                    joint.shape[1] < self.joint_width or not joint.is_contiguous() or joint.device != dev:
+                raise _abi.MpeError("Actors.act_rows: joint is True or a contiguous float32 [%d, >= %d] tensor on the env's device"
+                                    % (M, self.joint_width))
+        r = self._rows_out(M, own)
+        jt = r.joint if own else joint if torch.is_tensor(joint) else None
+        wts, aset = self._frozen if self._frozen is not None else self.pack(dev)
+        _abi.check(_abi.lib().mpe_actor_act_rows(
+            C.byref(aset), arr, M, int(t), int(row_offset), r.moves.data_ptr(), r.utter.data_ptr() if r.utter is not None else None,
+            r.ids.data_ptr() if r.ids is not None else None, r.logp.data_ptr() if r.logp is not None else None,
+            r.logits.data_ptr() if r.logits is not None else None, jt.data_ptr() if jt is not None else None,
+            int(jt.shape[1]) if jt is not None else 0, _abi.raw_stream(dev)), "mpe_actor_act_rows")
+        del wts
+        self.rows, self.joint_rows = r, jt
+        return r.action
 
     def reference(self, obs_n):
         """The fp64 torch forward pass, on whatever device the modules and obs_n are: per agent (move logits [B,5] or None,
