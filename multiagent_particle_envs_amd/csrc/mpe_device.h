@@ -63,6 +63,9 @@ __device__ __forceinline__ float dist2d(float dx, float dy) {
 // sqrt in all but a 1e-6-wide band around the threshold: if s2 < m^2 (1 - 4e-7) then
 // sqrt(s2) < m (1 - 2e-7) is more than an ulp below m, and symmetrically above; only inside the band is
 // the real sqrt evaluated.  Used for the integer outputs (collision counts) -- see DESIGN.md 4.
+// PRECONDITION: m >= 0 (a sum of sizes, a positive constant).  The test is made on m * m, which forgets m's sign: for m < 0 every
+// small s2 would be "surely less", although sqrt(s2) < m holds for no s2.  A caller whose threshold can be negative or NaN guards
+// the call with `m > 0.0f &&` (symtrace._emit does, for every threshold that is not a positive constant).
 __device__ __forceinline__ bool sqrt_lt(float s2, float m) {
   const float m2 = m * m;
   const bool below = s2 < m2 * 0.9999996f;                    // surely less

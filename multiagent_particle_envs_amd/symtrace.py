@@ -251,13 +251,22 @@ class Sym(object):
 
     # x // y as Python / NumPy compute it: (x - x % y) / y, an exact multiple of y up to rounding, to the nearest integer --
     # floor(x / y) is one too many where x / y rounds UP to an integer (1.0 // 0.1 is 9.0, floor(1.0 / 0.1) is 10.0)
+    # A zero divisor: NumPy answers x / y (+-inf, nan for 0 // 0), where (x - nan) / 0 would be nan for every x.
     def __floordiv__(self, o):
         m = self._b("mod", o)
-        return m if m is NotImplemented else ((self - m) / o).rint()
+        if m is NotImplemented:
+            return m
+        q = ((self - m) / o).rint()
+        if not isinstance(o, (Sym, SymBool)) and o != 0:
+            return q
+        g = _Ctx.graph
+        return Sym(_select_nodes(g.compare("eq", _lift(o), g.const(0.0)), (self / o).n, q.n))
 
     def __rfloordiv__(self, o):
         m = self._b("mod", o, True)
-        return m if m is NotImplemented else ((o - m) / self).rint()
+        if m is NotImplemented:
+            return m
+        return Sym(_select_nodes(_Ctx.graph.compare("eq", self.n, _Ctx.graph.const(0.0)), (o / self).n, ((o - m) / self).rint().n))
 
     # rounding: floor / ceil / rint are what math.floor, math.ceil, np.floor, np.ceil, np.rint, np.round and round() ask for
     def floor(self): return Sym(_Ctx.graph.unary("floor", self.n))
@@ -2657,9 +2666,14 @@ def _emit(roots, lines, names, shared=None):
             # `np.sqrt(np.sum(np.square(d))) < r`, the reference's contact test (simple_tag.py:69-73): decided as NumPy's float32
             # rounding sequence would (sqrt_lt: exact, without the correctly rounded sqrt outside a 1e-6 band around r)
             # (a square root that traced_shared computed is read through S: its argument does not exist here)
+            # sqrt_lt compares s2 with r * r: it needs r >= 0 (the built-in kernels pass sums of sizes).  Here r is whatever the file
+            # wrote right of `<` -- `d < x`, `d < 0.25 - abs(u)` with state x, u: for r <= 0 and for a NaN r, sqrt(s2) < r is false for
+            # every s2 (a NaN one included), so anything but a positive constant is guarded.
             own = [x.op == "sqrt" and x.uid not in stop for x in a]
             if op == "lt" and own[0]:
                 e = "sqrt_lt(%s, %s)" % (ref(a[0].args[0]), ref(a[1]))
+                if not (a[1].op == "const" and a[1].value > 0.0):
+                    e = "(%s > 0.0f && %s)" % (ref(a[1]), e)
             elif own[0] or own[1]:
                 l = "sqrtf(%s)" % ref(a[0].args[0]) if own[0] else ref(a[0])
                 r = "sqrtf(%s)" % ref(a[1].args[0]) if own[1] else ref(a[1])
@@ -2675,6 +2689,11 @@ def _emit(roots, lines, names, shared=None):
         elif op == "ite":
             e = "%s ? %s : %s" % (ref(a[0]), ref(a[1]), ref(a[2]))
         elif op == "sel":
+            # An index that matches no candidate falls through to the LAST value here, while evaluate / evaluate_torch clip it (a
+            # negative one gives the FIRST).  They cannot disagree: every caller of Graph.select (_Recorder.choice, PickProxy through
+            # _select_values, the enumeration of picks in _trace) passes a K node and one value per member of that pick's
+            # population, and a pick is drawn in [0, pops[k]) -- by the reset kernels, by verify, by PickLogger -- so the index
+            # always names a candidate.  (The parameter slots that share K's storage are read as numbers, never as an index.)
             kn = a[0]
             kv = "k%d" % kn.uid if kn.op == "K" else "(int)%s" % ref(kn)
             e = ref(a[-1])

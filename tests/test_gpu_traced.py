@@ -6,7 +6,9 @@
     reference's env recorded: seeded resets, per-world picks, every step's rows / rewards / state at 1e-5;
   * the fixture files of tests/refstyle/ traced here, against their reference-recorded goldens and against the HOST path
     (refstyle.py: the same file's callbacks per world) on the same worlds;
-  * episode ends / rollouts of row programs carry over; a traced program without its image refuses to run.
+  * episode ends / rollouts of row programs carry over; a traced program without its image refuses to run;
+  * every emitted node kind at its edges (tests/_traced_edges.py: dyadic inputs, so fp32 decides as fp64 does): all worlds compared,
+    none masked, the rewards of the decision program bit for bit.
 """
 import json
 import os
@@ -516,6 +518,83 @@ def test_every_node_kind_as_device_code_against_the_numpy_evaluation_of_the_trac
             worst = max(worst, close(obs[i][torch.as_tensor(ok)], want[ok], "obs%d t=%d" % (i, t)))
             worst = max(worst, close(rew[i][torch.as_tensor(ok)], vals[off[-1] + i][ok], "rew%d t=%d" % (i, t)))
     assert worst <= TOL
+
+
+def _edge_run(E, scenario, P, exact, host_twin):
+    """The traced env of `scenario` at the edge states P (tests/_traced_edges.py): landmark rows written after the reset, two steps
+    of random moves and words; every row and reward of every world against the fp64 evaluation of the trace on the state read
+    back -> per step (rows, rewards [B, A], wanted rewards [B, A], rewards of the host path or None)."""
+    B, A = E.B, len(scenario.make_world().agents)
+    a = refstyle.make_ref_env(scenario, batch_size=B, seed=3)
+    assert a.traced and a.program_compiled, a.trace_fallback
+    tr = a.scenario.t
+    a.reset()
+    a.world.pos[A:].copy_(torch.as_tensor(P[:, A:]).permute(1, 2, 0))
+    b = None
+    if host_twin:          # the host path of the same file (its callbacks per world, fp64) on the same state and moves
+        b = refstyle.make_ref_env(scenario, batch_size=B, seed=3, traced=False)
+        assert not b.traced
+        b.reset()
+        b.world.set_state(*a.world.get_state(all_entities=True))
+    rs = np.random.RandomState(11)
+    out = []
+    for t in range(2):
+        act = [torch.as_tensor(np.concatenate([np.eye(5, dtype=np.float32)[rs.randint(0, 5, B)]] + (
+            [np.eye(2, dtype=np.float32)[rs.randint(0, 2, B)]] if not ag.silent else []), axis=1)).cuda() for ag in a.agents]
+        obs, rew, _, _ = a.step(act)
+        obs, rew = [o.cpu().numpy().copy() for o in obs], np.stack([r.cpu().numpy() for r in rew], axis=1)
+        Pa, Va = a.world.get_state(all_entities=True)
+        assert np.array_equal(Pa[:, A:].view(np.uint32), P[:, A:].view(np.uint32)) and np.all(Va[:, A:] == 0)      # the landmarks stayed put, to the bit
+        assert np.abs(Va[:, :A]).max() > 0.1                                                                      # ... and the agents move
+        Cw = np.zeros((B, A, 2))
+        for i, ag in enumerate(a.agents):
+            if not ag.silent:
+                Cw[:, i] = a._comm[i].cpu().numpy()
+        want_rows, want_rew = E.reference(tr, Pa, Cw, V=Va)
+        for i in range(A):
+            E.check(obs[i], want_rows[i], exact, TOL, "%s obs%d t=%d" % (type(scenario).__name__, i, t))
+        host = None
+        if b is not None:
+            host = np.stack([r.cpu().numpy() for r in b.step(act)[1]], axis=1)
+        out.append((obs, rew, want_rew, host))
+    for i in range(A):          # the second step repeats the first in everything the landmarks decide
+        assert np.array_equal(out[0][0][i][:, E.ORDINARY:], out[1][0][i][:, E.ORDINARY:], equal_nan=True)
+    return tr, out
+
+
+def test_every_decision_node_at_its_edges_as_device_code_on_every_world():
+    """tests/_traced_edges.py's EdgeDecisions in the step kernel: comparisons on their boundary and 1 ulp off it, sqrt_lt with
+    thresholds of either sign, +-0 and tiny ones over whole waves and lane by lane, `%` / `//` / floor / rint / pow / argmin at
+    their special arguments.  The inputs are dyadic, so fp32 decides as the fp64 evaluation does: all 229 worlds are compared, none
+    masked; the reward (a sum of powers of two, one per test) bit for bit, also against the file's host path."""
+    import _traced_edges as E
+    P, kind = E.decision_states()
+    tr, out = _edge_run(E, E.EdgeDecisions(), P, E.exact_columns(E.DECISION_COLUMNS, floats=E.DECISION_FLOAT), host_twin=True)
+    assert {"add", "sub", "mul", "div", "abs", "min", "max", "sqrt", "lt", "ite", "le", "eq", "ne", "not", "and", "or", "mod", "floor", "rint",
+            "pow", "neg", "f32"} <= E.ops_of(tr), E.ops_of(tr)
+    for t, (obs, rew, want, host) in enumerate(out):
+        for i in range(rew.shape[1]):          # (said before it is asserted: which tests flipped, in which kinds of worlds, at which thresholds)
+            wrong = E.wrong_bits(rew[:, i], want[:, i])
+            if wrong:
+                print("EdgeDecisions t=%d agent %d: %d of %d rewards differ from the fp64 evaluation; tests that flipped: %s"
+                      % (t, i, int((rew[:, i] != want[:, i]).sum()), E.B, dict((k, (len(v), sorted(set(kind[v])), "x in [%g, %g]" % (
+                          P[v, 3, 0].min(), P[v, 3, 0].max()), "0.25 - |u| in [%g, %g]" % ((0.25 - np.abs(P[v, 4, 0])).min(), (0.25 - np.abs(P[v, 4, 0])).max())))
+                          for k, v in wrong.items())))
+        assert np.array_equal(rew.view(np.uint32), want.astype(np.float32).view(np.uint32)), "t=%d: see the printed tests" % t
+        assert np.array_equal(rew.view(np.uint32), host.astype(np.float32).view(np.uint32)), "t=%d: the host path of the same file" % t
+    assert np.array_equal(out[0][1], out[1][1])
+
+
+def test_the_function_nodes_at_their_special_values_as_device_code_on_every_world():
+    """tests/_traced_edges.py's EdgeFunctions in the step kernel: exp / log / sqrt / tanh / sin / cos / atan2 / division / hypot /
+    clip over {-60, -20, -1, -0, 0, 2^-10, 1, 20, 60}^2 -- NaN where the fp64 evaluation has NaN, the same signed infinity,
+    numbers at 1e-5; the comparisons on NaN and -inf in the reward; all 229 worlds."""
+    import _traced_edges as E
+    tr, out = _edge_run(E, E.EdgeFunctions(), E.function_states(), E.exact_columns(E.FUNCTION_COLUMNS, exact=E.FUNCTION_EXACT), host_twin=False)
+    assert {"exp", "log", "sqrt", "tanh", "sin", "cos", "atan2", "div", "min", "max", "lt", "eq", "ite"} <= E.ops_of(tr), E.ops_of(tr)
+    for t, (obs, rew, want, _) in enumerate(out):
+        E.check(rew, want, False, TOL, "EdgeFunctions rewards t=%d" % t)
+    assert np.array_equal(out[0][1], out[1][1])
 
 
 def test_traced_file_at_full_size_against_the_numpy_evaluation_and_shard_invariance():

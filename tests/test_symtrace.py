@@ -7,7 +7,8 @@
     the trace reproduces the file's own reset_world / observation / reward on random worlds (fp64, to the last bit);
   * the COMMITTED traces of the nine (tests/golden/traced_*.json, tests/golden/gen_traced.py) evaluated with NumPy on the states
     the reference's own env recorded (tests/golden/*.npz) against the rows and rewards it recorded -- no reference tree needed;
-  * the generated device code compiles (hipcc --genco needs no GPU).
+  * the generated device code compiles (hipcc --genco needs no GPU), and -- compiled for the host -- reproduces the NumPy evaluation,
+    at the edges of every node kind (tests/_traced_edges.py) on every world and against the file's own callbacks.
 """
 import json
 import math
@@ -1207,6 +1208,87 @@ def test_generated_code_on_the_host_against_the_numpy_evaluation(name, tmp_path)
         assert (np.abs(rows[i][ok] - want[ok]) / np.maximum(1.0, np.abs(want[ok]))).max(initial=0.0) <= 1e-5, (name, "obs", i)
         w = vals[off[-1] + i]
         assert (np.abs(rew[ok, i] - w[ok]) / np.maximum(1.0, np.abs(w[ok]))).max() <= 1e-5, (name, "rew", i)
+
+
+def _device_sqrt_lt(s2, m):
+    """csrc/mpe_device.h's sqrt_lt restated in NumPy fp32 (the band's sqrtf is np.sqrt: both correctly rounded)."""
+    s2, m = np.asarray(s2, np.float32), np.asarray(m, np.float32)
+    with np.errstate(all="ignore"):
+        m2 = m * m
+        below = s2 < m2 * np.float32(0.9999996)
+        above = (s2 > m2 * np.float32(1.0000004)) & (m2 > np.float32(1e-30))
+        return np.where(~below & ~above, np.sqrt(s2) < m, below)
+
+
+def test_generated_code_of_every_decision_node_at_its_edges_on_the_host(tmp_path):
+    """tests/_traced_edges.py's EdgeDecisions: comparisons ON their boundary and 1 ulp off it, thresholds of either sign, +-0 and
+    tiny, `%` / `//` with negative and zero divisors, floor / rint / ceil / trunc of integers and halves, ties of min / max /
+    argmin -- the generated code (g++) against the fp64 evaluation of the trace AND against the file's own callbacks run
+    concretely, on EVERY world: the inputs are dyadic, so fp32 decides as fp64 does and no decision-margin mask is used."""
+    import _traced_edges as E
+    tr = symtrace.trace(E.EdgeDecisions())
+    assert {"le", "eq", "ne", "not", "and", "or", "mod", "floor", "rint", "pow", "neg", "f32", "lt", "ite", "sqrt", "abs", "min", "max",
+            "add", "sub", "mul", "div"} <= E.ops_of(tr), E.ops_of(tr)
+    src = symtrace.hip_source(tr)
+    # the three square-root comparisons; a threshold that is state is guarded, a positive constant is not
+    assert "sqrtf(" in src and " <= " in src and " < sqrtf(" in src
+    import re
+    guarded = re.findall(r"\((\w+) > 0\.0f && sqrt_lt\(\w+, (\w+)\)\)", src)
+    assert guarded and all(a == b for a, b in guarded) and src.count("sqrt_lt(") == len(guarded)
+    P, kind = E.decision_states()
+    Cw = E.utterances(3, 1)
+    assert set(kind) == {"far", "boundary", "below", "above", "+1ulp", "-1ulp", "negative", "zero", "tiny"}
+    # the device's own rule on these states (a restatement: the device itself is tests/test_gpu_traced.py's): as it stands it is
+    # wrong for negative thresholds and only for them; guarded as the generator guards it, it is the specification
+    d2 = ((P[:, 5] - P[:, 6]) ** 2).sum(axis=1).astype(np.float32)
+    for m in (P[:, 3, 0], np.float32(0.25) - np.abs(P[:, 4, 0])):
+        spec = np.sqrt(d2) < m
+        bare = _device_sqrt_lt(d2, m)
+        assert (m < 0).sum() >= 10 and (m == 0).sum() >= 8 and ((m > 0) & (m < 1e-6)).sum() >= 3
+        assert np.array_equal((m > 0) & bare, spec) and (bare != spec).any() and np.all(m[bare != spec] < 0)
+    rows, rew, _ = _host_run_generated(tr, P, np.zeros_like(P), Cw, np.zeros((E.B, 0), np.int64), tmp_path, "edge_decisions")
+    want_rows, want_rew = E.reference(tr, P, Cw)
+    own_rows, own_rew = E.run_callbacks(E.EdgeDecisions(), P, Cw)
+    exact = E.exact_columns(E.DECISION_COLUMNS, floats=E.DECISION_FLOAT)
+    for i in range(tr.A):
+        assert np.array_equal(rows[i][:, :4], np.concatenate([np.zeros((E.B, 2)), P[:, i]], axis=1))
+        assert np.array_equal(rows[i][:, 4:6], Cw[:, 1])
+        E.check(rows[i], want_rows[i], exact, 1e-5, "EdgeDecisions obs%d vs evaluate" % i)
+        E.check(rows[i], own_rows[i], exact, 1e-5, "EdgeDecisions obs%d vs the file's callbacks" % i)
+        assert np.array_equal(rew[:, i], want_rew[:, i]), E.wrong_bits(rew[:, i], want_rew[:, i])
+        assert np.array_equal(rew[:, i], own_rew[:, i]), E.wrong_bits(rew[:, i], own_rew[:, i])
+    # every test was seen both ways, every special result occurred
+    for bit, test in E.DECISION_BITS:
+        on = (want_rew[:, 0].astype(np.int64) & int(bit)) != 0
+        assert 8 <= on.sum() <= E.B - 8, (test, on.sum())
+    edge = want_rows[0][:, E.ORDINARY:]
+    assert np.isnan(edge[:, 0]).sum() >= 8 and np.isinf(edge[:, 1]).sum() >= 4 and np.isinf(edge[:, 6]).sum() >= 1
+    assert set(np.unique(edge[:, 12])) == {0.0, 1.0, 2.0, 3.0}
+
+
+def test_generated_code_of_the_function_nodes_at_their_special_values_on_the_host(tmp_path):
+    """tests/_traced_edges.py's EdgeFunctions: exp / log / sqrt / tanh / sin / cos / atan2 / division / hypot / clip over the grid
+    {-60, -20, -1, -0, 0, 2^-10, 1, 20, 60}^2: NaN where NaN, the same signed infinity, numbers at 1e-5 -- every world."""
+    import _traced_edges as E
+    tr = symtrace.trace(E.EdgeFunctions())
+    assert {"exp", "log", "sqrt", "tanh", "sin", "cos", "atan2", "div", "min", "max", "lt", "eq", "ite"} <= E.ops_of(tr), E.ops_of(tr)
+    P = E.function_states()
+    Cw = E.utterances(2, -1)
+    rows, rew, _ = _host_run_generated(tr, P, np.zeros_like(P), Cw, np.zeros((E.B, 0), np.int64), tmp_path, "edge_functions")
+    want_rows, want_rew = E.reference(tr, P, Cw)
+    own_rows, own_rew = E.run_callbacks(E.EdgeFunctions(), P, Cw)
+    exact = E.exact_columns(E.FUNCTION_COLUMNS, exact=E.FUNCTION_EXACT)
+    for i in range(tr.A):
+        E.check(rows[i], want_rows[i], exact, 1e-5, "EdgeFunctions obs%d vs evaluate" % i)
+        E.check(rows[i], own_rows[i], exact, 1e-5, "EdgeFunctions obs%d vs the file's callbacks" % i)
+        E.check(rew[:, i], want_rew[:, i], False, 1e-5, "EdgeFunctions rew%d vs evaluate" % i)
+        E.check(rew[:, i], own_rew[:, i], False, 1e-5, "EdgeFunctions rew%d vs the file's callbacks" % i)
+    edge = want_rows[0][:, E.ORDINARY:]
+    col = dict((c, edge[:, k]) for k, c in enumerate(E.FUNCTION_COLUMNS))
+    assert np.isnan(col["log(a)"]).any() and np.isneginf(col["log(a)"]).any() and np.isnan(col["sqrt(a)"]).any()
+    assert np.isposinf(col["a / b"]).any() and np.isneginf(col["a / b"]).any() and np.isnan(col["a / b"]).any()
+    assert (col["arctan2(a, b)"] == np.pi).any() and (col["arctan2(a, b)"] == -np.pi).any()
+    assert set(np.unique(np.round(want_rew[:, 0] - np.tanh(P[:, 2, 0].astype(np.float64)) - np.clip(P[:, 2, 1], -1, 1)))) == {0.0, 4.0, 8.0}
 
 
 _MATH_FILE = '''
