@@ -32,6 +32,13 @@ int hip_result(int rc, const char *what) {
 // mpe_step_thread -- an explicit argument of the call, not process state.  Both give bit-identical results.
 enum class StepImpl { Split, Thread };
 
+// the first movable landmark, or -1
+int first_movable_landmark(const MpeScenarioDesc *d) {
+  for (int e = d->n_agents; e < d->n_agents + d->n_landmarks; ++e)
+    if (d->movable[e]) return e;
+  return -1;
+}
+
 int check_desc(const MpeScenarioDesc *d, const char *what) {
   if (!d) return fail(MPE_EINVAL, "%s: desc is NULL", what);
   if (d->n_agents < 1 || d->n_landmarks < 0 || d->n_agents + d->n_landmarks > MPE_MAX_ENTITIES)
@@ -42,9 +49,8 @@ int check_desc(const MpeScenarioDesc *d, const char *what) {
   // on the physics path only -- kind GENERIC, i.e. mpe_world_step and the phase-free generic path above it; the built-in
   // scenarios' fused output stages read agent velocities only, so for them a movable landmark is "no kernel for this"
   // (mpe_step_supported < 1: the env steps such a world through mpe_world_step + the scenario's callbacks).
-  for (int e = d->n_agents; e < d->n_agents + d->n_landmarks; ++e)
-    if (d->movable[e] && d->kind != MPE_SCN_GENERIC)
-      return fail(MPE_EUNSUPPORTED, "%s: a movable landmark (entity %d) is stepped by mpe_world_step (kind GENERIC) only", what, e);
+  if (const int e = first_movable_landmark(d); e >= 0 && d->kind != MPE_SCN_GENERIC)
+    return fail(MPE_EUNSUPPORTED, "%s: a movable landmark (entity %d) is stepped by mpe_world_step (kind GENERIC) only", what, e);
   for (int e = 0; e < d->n_agents + d->n_landmarks; ++e)
     if ((e < d->n_agents || d->movable[e]) && !(d->mass[e] > 0.f)) return fail(MPE_EINVAL, "%s: mass[%d] must be > 0", what, e);
   const bool teams = d->kind == MPE_SCN_TAG || d->kind == MPE_SCN_ADVERSARY || d->kind == MPE_SCN_PUSH ||
@@ -74,9 +80,16 @@ int check_desc(const MpeScenarioDesc *d, const char *what) {
   return 0;
 }
 
-bool use_narrow(const MpeScenarioDesc *d) {
-  return d->n_agents + d->n_landmarks <= mpe::kNarrowMaxE &&
-         mpe::narrow_supports(d->kind, d->n_agents, d->n_landmarks, d->n_adversaries);
+// "this shape has a kernel of the small-entity families": A + L fits their descriptor and `supports` (narrow_supports, split_supports,
+// split_policy_supports, serve_supports) has an entry for it
+bool has_kernel(const MpeScenarioDesc *d, bool (*supports)(int kind, int A, int L, int nadv)) {
+  return d->n_agents + d->n_landmarks <= mpe::kNarrowMaxE && supports(d->kind, d->n_agents, d->n_landmarks, d->n_adversaries);
+}
+bool use_narrow(const MpeScenarioDesc *d) { return has_kernel(d, mpe::narrow_supports); }
+
+// the populations the picks of reset_world are drawn from: pick k has choice_pop[k], the picks beyond n_choices 1
+void choice_pops(const MpeScenarioDesc *d, int32_t out[MPE_MAX_CHOICES]) {
+  for (int k = 0; k < MPE_MAX_CHOICES; ++k) out[k] = k < d->n_choices ? d->choice_pop[k] : 1;
 }
 
 mpe::NarrowDesc make_narrow(const MpeScenarioDesc *d, const MpeBuffers *b, size_t B) {
@@ -104,7 +117,7 @@ mpe::NarrowDesc make_narrow(const MpeScenarioDesc *d, const MpeBuffers *b, size_
   n.collaborative = d->collaborative;
   n.vec4 = vec4 ? 1 : 0;
   n.n_choices = d->n_choices;
-  for (int k = 0; k < MPE_MAX_CHOICES; ++k) n.choice_pop[k] = k < d->n_choices ? d->choice_pop[k] : 1;
+  choice_pops(d, n.choice_pop);
   return n;
 }
 
@@ -161,6 +174,76 @@ int check_info(const MpeScenarioDesc *d, const MpeBuffers *b, const char *what) 
       !(b->info_collisions && b->info_min_dists && b->info_occupied))
     return fail(MPE_EINVAL, "%s: spread benchmark_data needs all four info_* buffers", what);
   return 0;
+}
+
+// what every entry point with an output stage checks first, in this order: the descriptor, the state, obs, the info buffers
+int check_outputs(const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B, const char *what) {
+  if (int rc = check_desc(d, what)) return rc;
+  if (int rc = check_state(b, B, what)) return rc;
+  if (int rc = need(b->obs, what, "obs")) return rc;
+  return check_info(d, b, what);
+}
+
+// the picks of reset_world: the built-in output stages read them from ADVERSARY on, a row program whenever the descriptor has any
+int need_choice(const MpeScenarioDesc *d, const MpeBuffers *b, const char *what, bool builtin) {
+  if (d->n_choices > 0 && (!builtin || d->kind >= MPE_SCN_ADVERSARY))
+    return need(b->choice, what, "choice (the per-world picks of reset_world)");
+  return 0;
+}
+
+// the communication scenarios' comm rows; `why` is the caller's own account of what they hold
+int need_comm(const MpeScenarioDesc *d, const MpeBuffers *b, const char *what, const char *why) {
+  if (d->kind >= MPE_SCN_SPEAKER_LISTENER && !b->comm) return fail(MPE_EINVAL, "%s: bufs->comm (%s) is NULL", what, why);
+  return 0;
+}
+
+// what the three resets check (desc, state, the entity bound of the caller, choice), and the populations they draw the picks from
+int check_reset(const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B, int max_entities, const char *what,
+                int32_t pop[MPE_MAX_CHOICES]) {
+  if (int rc = check_desc(d, what)) return rc;
+  if (int rc = check_state(b, B, what)) return rc;
+  if (d->n_agents + d->n_landmarks > max_entities) return fail(MPE_EINVAL, "%s: more than %d entities", what, max_entities);
+  if (d->n_choices > 0 && b->choice == nullptr)
+    return fail(MPE_EINVAL, "%s: desc->n_choices = %d but bufs->choice is NULL", what, d->n_choices);
+  choice_pops(d, pop);
+  return 0;
+}
+
+mpe::RollArgs roll_args(int32_t T, int32_t episode_len, int32_t trajectory, float landmark_range, uint64_t seed, uint64_t step0,
+                        int64_t world_offset, const float *act_seq) {
+  mpe::RollArgs ra;
+  std::memset(&ra, 0, sizeof(ra));
+  ra.T = T;
+  ra.episode_len = episode_len;
+  ra.trajectory = trajectory ? 1 : 0;
+  ra.landmark_range = landmark_range;
+  ra.seed = seed;
+  ra.step0 = step0;
+  ra.world_offset = (uint64_t)world_offset;
+  ra.act_seq = act_seq;
+  return ra;
+}
+
+// a row call's episode block with the episodes off: the picks' populations and the world numbering the in-kernel resets draw
+// with, and the agents that say a drawn word every step
+mpe::RowEpisode row_episode(const MpeScenarioDesc *d, int64_t world_offset, uint32_t speakers) {
+  mpe::RowEpisode ep;
+  std::memset(&ep, 0, sizeof(ep));
+  ep.n_choices = d->n_choices;
+  choice_pops(d, ep.choice_pop);
+  ep.world_offset = (uint64_t)world_offset;
+  ep.speakers = speakers;
+  return ep;
+}
+
+// the speakers mask of the row rollouts.  `beyond_A`: refuse a mask that names agents the descriptor does not have --
+// mpe_rollout_rows does, mpe_rollout_rows_episode never did (kept as it was: whether it should is a change of its own)
+int check_speakers(const MpeScenarioDesc *d, const MpeBuffers *b, uint32_t speakers, bool beyond_A, const char *what) {
+  if (speakers == 0) return 0;
+  if (d->dim_c <= 0) return fail(MPE_EINVAL, "%s: speakers 0x%x but desc->dim_c = %d", what, speakers, d->dim_c);
+  if (beyond_A && d->n_agents < 32 && (speakers >> d->n_agents) != 0)
+    return fail(MPE_EINVAL, "%s: speakers 0x%x names agents beyond %d", what, speakers, d->n_agents);
+  return need(b ? b->comm : nullptr, what, "comm (receives the speaking agents' last words)");
 }
 
 }  // namespace
@@ -234,10 +317,8 @@ static int run(const char *what, bool phys, bool out, const MpeScenarioDesc *d, 
     if (d->kind == MPE_SCN_GENERIC) return fail(MPE_EINVAL, "%s: kind GENERIC has no output stage", what);
     if (int rc = need(b->obs, what, "obs")) return rc;
     if (int rc = check_info(d, b, what)) return rc;
-    if (d->n_choices > 0 && d->kind >= MPE_SCN_ADVERSARY)
-      if (int rc = need(b->choice, what, "choice (the per-world picks of reset_world)")) return rc;
-    if (d->kind >= MPE_SCN_SPEAKER_LISTENER)
-      if (int rc = need(b->comm, what, "comm (communication action rows / current comm state)")) return rc;
+    if (int rc = need_choice(d, b, what, true)) return rc;
+    if (int rc = need_comm(d, b, what, "communication action rows / current comm state")) return rc;
   }
   if (B == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -254,10 +335,10 @@ static int run(const char *what, bool phys, bool out, const MpeScenarioDesc *d, 
   // with n_dyn = (index of the last movable entity) + 1, entities [A, n_dyn) enter the physics kernels as agents whose
   // action force is zero -- same entity order, so every force is summed in the reference's order (Q9) -- and entities
   // [n_dyn, E) stay landmarks.  The caller's vel and u are [n_dyn][2][B] (rows [A, n_dyn) of u must be zero).
-  int n_dyn = d->n_agents;
-  for (int e = d->n_agents; e < d->n_agents + d->n_landmarks; ++e)
-    if (d->movable[e]) n_dyn = e + 1;
-  if (n_dyn > d->n_agents) {
+  if (first_movable_landmark(d) >= 0) {
+    int n_dyn = 0;
+    for (int e = d->n_agents; e < d->n_agents + d->n_landmarks; ++e)
+      if (d->movable[e]) n_dyn = e + 1;
     if (out) return fail(MPE_EUNSUPPORTED, "%s: movable landmarks are stepped by mpe_world_step only", what);
     if (!b->u) return fail(MPE_EINVAL, "%s: movable landmarks need bufs->u ([n_dyn][2][B], n_dyn = %d: zero rows for the landmarks)", what, n_dyn);
     if (use != &dd) dd = *d;
@@ -269,14 +350,11 @@ static int run(const char *what, bool phys, bool out, const MpeScenarioDesc *d, 
   const bool comm_kind = kind >= MPE_SCN_SPEAKER_LISTENER;   // these exist as wave-per-agent kernels only
   // (an observe-only call goes to the thread-per-world kernel where one exists -- no barrier, no exchange block needed --
   //  and to the wave-per-agent kernel's observe half for the shapes that exist there only)
-  if (out && (phys || comm_kind || !use_narrow(use)) && d->n_agents + d->n_landmarks <= mpe::kNarrowMaxE &&
-      (comm_kind || impl != StepImpl::Thread) &&
-      mpe::split_supports(kind, d->n_agents, d->n_landmarks, d->n_adversaries)) {
+  if (out && (phys || comm_kind || !use_narrow(use)) && (comm_kind || impl != StepImpl::Thread) &&
+      has_kernel(d, mpe::split_supports)) {
     // the fused step: wave-per-agent / lane-per-world (mpe_split.hip)
     const mpe::NarrowDesc n = make_narrow(use, b, (size_t)B);
-    mpe::RollArgs ra;
-    std::memset(&ra, 0, sizeof(ra));
-    ra.T = 1;
+    mpe::RollArgs ra = roll_args(1, 0, 0, 0.f, 0, 0, 0, nullptr);
     ra.observe_only = phys ? 0 : 1;
     return hip_result(mpe::launch_split(false, kind, d->n_agents, d->n_landmarks, d->n_adversaries, n, *b, (size_t)B,
                                         ra, s), what);
@@ -299,8 +377,7 @@ static int run(const char *what, bool phys, bool out, const MpeScenarioDesc *d, 
 int mpe_step_supported(const MpeScenarioDesc *d) {
   if (int rc = check_desc(d, "mpe_step_supported")) return rc;
   if (d->kind == MPE_SCN_GENERIC) return 0;   // World.step only (mpe_world_step); callbacks stay with the caller
-  const int A = d->n_agents, L = d->n_landmarks;
-  if (A + L <= mpe::kNarrowMaxE && mpe::split_supports(d->kind, A, L, d->n_adversaries)) return 1;
+  if (has_kernel(d, mpe::split_supports)) return 1;
   if (d->kind >= MPE_SCN_SPEAKER_LISTENER) return 0;
   if (use_narrow(d)) return 1;
   if (d->kind != MPE_SCN_SPREAD && d->kind != MPE_SCN_TAG) return 0;   // the wave-per-world kernel: any team sizes
@@ -348,13 +425,9 @@ int mpe_integrate_state(const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B
 int mpe_reset(const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B, const uint8_t *mask, float landmark_range,
               uint64_t seed, uint64_t episode, int64_t world_offset, void *stream) {
   const char *what = "mpe_reset";
-  if (int rc = check_desc(d, what)) return rc;
-  if (int rc = check_state(b, B, what)) return rc;
-  if (d->n_choices > 0 && b->choice == nullptr)
-    return fail(MPE_EINVAL, "%s: desc->n_choices = %d but bufs->choice is NULL", what, d->n_choices);
+  int32_t pop[MPE_MAX_CHOICES];
+  if (int rc = check_reset(d, b, B, MPE_MAX_ENTITIES, what, pop)) return rc;
   if (B == 0) return 0;
-  int32_t pop[MPE_MAX_CHOICES] = {1, 1, 1, 1};
-  for (int k = 0; k < d->n_choices; ++k) pop[k] = d->choice_pop[k];
   return hip_result(mpe::launch_reset(d->n_agents, d->n_landmarks, *b, (size_t)B, mask, landmark_range, seed,
                                       episode, (uint64_t)world_offset, d->n_choices, pop,
                                       static_cast<hipStream_t>(stream)), what);
@@ -365,14 +438,9 @@ int mpe_reset_rows(const MpeScenarioDesc *d, const MpeBuffers *b, const MpeRowPr
   const char *what = "mpe_reset_rows";
   if (!p) return fail(MPE_EINVAL, "%s: prog is NULL", what);
   if (!p->reset_boxes) return mpe_reset(d, b, B, mask, landmark_range, seed, episode, world_offset, stream);
-  if (int rc = check_desc(d, what)) return rc;
-  if (int rc = check_state(b, B, what)) return rc;
-  if (d->n_agents + d->n_landmarks > MPE_ROWS_MAX_ENTITIES) return fail(MPE_EINVAL, "%s: more than %d entities", what, MPE_ROWS_MAX_ENTITIES);
-  if (d->n_choices > 0 && b->choice == nullptr)
-    return fail(MPE_EINVAL, "%s: desc->n_choices = %d but bufs->choice is NULL", what, d->n_choices);
+  int32_t pop[MPE_MAX_CHOICES];
+  if (int rc = check_reset(d, b, B, MPE_ROWS_MAX_ENTITIES, what, pop)) return rc;
   if (B == 0) return 0;
-  int32_t pop[MPE_MAX_CHOICES] = {1, 1, 1, 1};
-  for (int k = 0; k < d->n_choices; ++k) pop[k] = d->choice_pop[k];
   mpe::ResetBoxes boxes;
   std::memset(&boxes, 0, sizeof(boxes));
   for (int e = 0; e < d->n_agents + d->n_landmarks; ++e)
@@ -385,15 +453,11 @@ int mpe_reset_random_actions_block(const MpeScenarioDesc *d, const MpeBuffers *b
                                    float *act, int32_t *ids, uint64_t seed, uint64_t step0, int32_t T, int64_t world_offset,
                                    void *stream) {
   const char *what = "mpe_reset_random_actions_block";
-  if (int rc = check_desc(d, what)) return rc;
-  if (int rc = check_state(b, B, what)) return rc;
-  if (d->n_choices > 0 && b->choice == nullptr)
-    return fail(MPE_EINVAL, "%s: desc->n_choices = %d but bufs->choice is NULL", what, d->n_choices);
+  int32_t pop[MPE_MAX_CHOICES];
+  if (int rc = check_reset(d, b, B, MPE_MAX_ENTITIES, what, pop)) return rc;
   if (!act && !ids) return fail(MPE_EINVAL, "%s: act and ids are both NULL", what);
   if (T < 1 || T > 65535) return fail(MPE_EINVAL, "%s: T = %d (the reset rides on the block's first step: 1..65535)", what, T);
   if (B == 0) return 0;
-  int32_t pop[MPE_MAX_CHOICES] = {1, 1, 1, 1};
-  for (int k = 0; k < d->n_choices; ++k) pop[k] = d->choice_pop[k];
   return hip_result(mpe::launch_reset_random_actions(d->n_agents, d->n_landmarks, *b, (size_t)B, landmark_range, episode,
                                                      d->n_choices, pop, act, ids, seed, step0, T, (uint64_t)world_offset,
                                                      static_cast<hipStream_t>(stream)), what);
@@ -437,44 +501,16 @@ int mpe_episode_tick(int32_t *episode_step, uint8_t *done, int32_t n_agents, int
 
 static int rollout_fused(const char *what, const float *act_seq, const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B, int32_t T,
                          int32_t episode_len, float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset,
-                         int32_t trajectory, void *stream);
-int mpe_rollout_random(const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B, int32_t T, int32_t episode_len,
-                       float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset,
-                       int32_t trajectory, void *stream) {
-  return rollout_fused("mpe_rollout_random", nullptr, d, b, B, T, episode_len, landmark_range, seed, step0, world_offset, trajectory, stream);
-}
-int mpe_rollout_actions(const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B, int32_t T, int32_t episode_len,
-                        float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset,
-                        int32_t trajectory, const float *act_seq, void *stream) {
-  if (!act_seq) return fail(MPE_EINVAL, "mpe_rollout_actions: act_seq is NULL");
-  return rollout_fused("mpe_rollout_actions", act_seq, d, b, B, T, episode_len, landmark_range, seed, step0, world_offset, trajectory, stream);
-}
-static int rollout_fused(const char *what, const float *act_seq, const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B, int32_t T,
-                         int32_t episode_len, float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset,
                          int32_t trajectory, void *stream) {
-  if (int rc = check_desc(d, what)) return rc;
-  if (int rc = check_state(b, B, what)) return rc;
-  if (int rc = need(b->obs, what, "obs")) return rc;
-  if (int rc = check_info(d, b, what)) return rc;
-  if (d->n_choices > 0 && d->kind >= MPE_SCN_ADVERSARY)
-    if (int rc = need(b->choice, what, "choice (the per-world picks of reset_world)")) return rc;
-  if (d->kind >= MPE_SCN_SPEAKER_LISTENER)   // the speaking agents' words are drawn in-kernel; their last words are left in comm
-    if (int rc = need(b->comm, what, "comm (receives the agents' comm state after the last step)")) return rc;
+  if (int rc = check_outputs(d, b, B, what)) return rc;
+  if (int rc = need_choice(d, b, what, true)) return rc;
+  // (the speaking agents' words are drawn in-kernel; their last words are left in comm)
+  if (int rc = need_comm(d, b, what, "receives the agents' comm state after the last step")) return rc;
   if (T < 0 || episode_len < 0) return fail(MPE_EINVAL, "%s: T, episode_len must be >= 0", what);
   if (B == 0 || T == 0) return 0;
-  mpe::RollArgs ra;
-  std::memset(&ra, 0, sizeof(ra));
-  ra.T = T;
-  ra.episode_len = episode_len;
-  ra.trajectory = trajectory ? 1 : 0;
-  ra.landmark_range = landmark_range;
-  ra.seed = seed;
-  ra.step0 = step0;
-  ra.world_offset = (uint64_t)world_offset;
-  ra.act_seq = act_seq;
+  const mpe::RollArgs ra = roll_args(T, episode_len, trajectory, landmark_range, seed, step0, world_offset, act_seq);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (d->n_agents + d->n_landmarks > mpe::kNarrowMaxE ||
-      !mpe::split_supports(d->kind, d->n_agents, d->n_landmarks, d->n_adversaries)) {
+  if (!has_kernel(d, mpe::split_supports)) {
     if (d->kind != MPE_SCN_SPREAD && d->kind != MPE_SCN_TAG)
       return fail(MPE_EUNSUPPORTED, "%s: the fused rollout exists for the wave-per-agent shapes and for simple_spread / simple_tag of any size", what);
     if (int rc = need(b->entity_table, what, "entity_table (required by the wave-per-world kernel)")) return rc;
@@ -487,6 +523,17 @@ static int rollout_fused(const char *what, const float *act_seq, const MpeScenar
   const mpe::NarrowDesc n = make_narrow(d, b, (size_t)B);
   return hip_result(mpe::launch_split(true, d->kind, d->n_agents, d->n_landmarks, d->n_adversaries, n, *b, (size_t)B,
                                       ra, s), what);
+}
+int mpe_rollout_random(const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B, int32_t T, int32_t episode_len,
+                       float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset,
+                       int32_t trajectory, void *stream) {
+  return rollout_fused("mpe_rollout_random", nullptr, d, b, B, T, episode_len, landmark_range, seed, step0, world_offset, trajectory, stream);
+}
+int mpe_rollout_actions(const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B, int32_t T, int32_t episode_len,
+                        float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset,
+                        int32_t trajectory, const float *act_seq, void *stream) {
+  if (!act_seq) return fail(MPE_EINVAL, "mpe_rollout_actions: act_seq is NULL");
+  return rollout_fused("mpe_rollout_actions", act_seq, d, b, B, T, episode_len, landmark_range, seed, step0, world_offset, trajectory, stream);
 }
 
 // ---- policy rollouts (mpe_split.hip, POL) --------------------------------------------------------------------------------
@@ -514,8 +561,7 @@ static int check_policy(const MpeScenarioDesc *d, const MpePolicy *p, const char
 static int policy_shape(const MpeScenarioDesc *d) {
   const bool kind_ok = d->kind == MPE_SCN_SIMPLE || d->kind == MPE_SCN_SPREAD || d->kind == MPE_SCN_TAG || d->kind == MPE_SCN_ADVERSARY ||
                        d->kind == MPE_SCN_PUSH;
-  return kind_ok && d->n_agents + d->n_landmarks <= mpe::kNarrowMaxE &&
-         mpe::split_policy_supports(d->kind, d->n_agents, d->n_landmarks, d->n_adversaries);
+  return kind_ok && has_kernel(d, mpe::split_policy_supports);
 }
 int mpe_rollout_policy_supported(const MpeScenarioDesc *d, const MpePolicy *p, int64_t B) {
   const char *what = "mpe_rollout_policy_supported";
@@ -527,13 +573,9 @@ int mpe_rollout_policy(const MpeScenarioDesc *d, const MpeBuffers *b, const MpeP
                        float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset, int32_t trajectory, float *act_out,
                        float *obs_in_out, float *logp_out, void *stream) {
   const char *what = "mpe_rollout_policy";
-  if (int rc = check_desc(d, what)) return rc;
-  if (int rc = check_state(b, B, what)) return rc;
-  if (int rc = need(b->obs, what, "obs")) return rc;
-  if (int rc = check_info(d, b, what)) return rc;
+  if (int rc = check_outputs(d, b, B, what)) return rc;
   if (int rc = check_policy(d, p, what)) return rc;
-  if (d->n_choices > 0 && d->kind >= MPE_SCN_ADVERSARY)
-    if (int rc = need(b->choice, what, "choice (the per-world picks of reset_world)")) return rc;
+  if (int rc = need_choice(d, b, what, true)) return rc;
   if (!p->weights) return fail(MPE_EINVAL, "%s: policy->weights is NULL", what);
   if (!act_out) return fail(MPE_EINVAL, "%s: act_out is NULL", what);
   if (logp_out && p->mode == MPE_POLICY_SOFTMAX) return fail(MPE_EINVAL, "%s: logp_out needs a chosen index (GREEDY / SAMPLE)", what);
@@ -547,15 +589,7 @@ int mpe_rollout_policy(const MpeScenarioDesc *d, const MpeBuffers *b, const MpeP
   if ((int64_t)T * B * d->n_agents > MPE_POLICY_MAX_LAUNCH_WORK)
     return fail(MPE_EINVAL, "%s: T * B * A = %lld agent-world-steps in one launch (at most %lld: split the rollout into launches "
                 "with step0 advanced)", what, (long long)T * B * d->n_agents, (long long)MPE_POLICY_MAX_LAUNCH_WORK);
-  mpe::RollArgs ra;
-  std::memset(&ra, 0, sizeof(ra));
-  ra.T = T;
-  ra.episode_len = episode_len;
-  ra.trajectory = trajectory ? 1 : 0;
-  ra.landmark_range = landmark_range;
-  ra.seed = seed;
-  ra.step0 = step0;
-  ra.world_offset = (uint64_t)world_offset;
+  const mpe::RollArgs ra = roll_args(T, episode_len, trajectory, landmark_range, seed, step0, world_offset, nullptr);
   mpe::PolArgs pa;
   std::memset(&pa, 0, sizeof(pa));
   pa.w = p->weights;
@@ -582,35 +616,22 @@ static int check_server(const MpeStepServer *srv, const char *what) {
 }
 int mpe_step_server_supported(const MpeScenarioDesc *d, int64_t B) {
   if (int rc = check_desc(d, "mpe_step_server_supported")) return rc;
-  if (B <= 0 || d->n_agents + d->n_landmarks > mpe::kNarrowMaxE) return 0;
-  return mpe::serve_supports(d->kind, d->n_agents, d->n_landmarks, d->n_adversaries) ? 1 : 0;
+  return B > 0 && has_kernel(d, mpe::serve_supports) ? 1 : 0;
 }
 int64_t mpe_step_server_flags(int64_t B) { return B > 0 ? (int64_t)mpe::serve_grid((size_t)B) : 0; }
 int mpe_step_server_start(const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B, int32_t T, int32_t episode_len,
                           float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset, const MpeStepServer *srv,
                           void *stream) {
   const char *what = "mpe_step_server_start";
-  if (int rc = check_desc(d, what)) return rc;
-  if (int rc = check_state(b, B, what)) return rc;
-  if (int rc = need(b->obs, what, "obs")) return rc;
-  if (int rc = check_info(d, b, what)) return rc;
+  if (int rc = check_outputs(d, b, B, what)) return rc;
   if (int rc = check_server(srv, what)) return rc;
-  if (d->n_choices > 0 && d->kind >= MPE_SCN_ADVERSARY)
-    if (int rc = need(b->choice, what, "choice (the per-world picks of reset_world)")) return rc;
+  if (int rc = need_choice(d, b, what, true)) return rc;
   if (!srv->act_ring || srv->ring < 1 || srv->slots < 1) return fail(MPE_EINVAL, "%s: srv->act_ring, ring >= 1, slots >= 1", what);
   if (T < 0 || episode_len < 0) return fail(MPE_EINVAL, "%s: T, episode_len must be >= 0", what);
   if (B == 0 || T == 0) return 0;
-  if (d->n_agents + d->n_landmarks > mpe::kNarrowMaxE || !mpe::serve_supports(d->kind, d->n_agents, d->n_landmarks, d->n_adversaries))
+  if (!has_kernel(d, mpe::serve_supports))
     return fail(MPE_EUNSUPPORTED, "%s: the step server exists for the shapes with a wave-per-agent kernel", what);
-  mpe::RollArgs ra;
-  std::memset(&ra, 0, sizeof(ra));
-  ra.T = T;
-  ra.episode_len = episode_len;
-  ra.trajectory = 1;
-  ra.landmark_range = landmark_range;
-  ra.seed = seed;
-  ra.step0 = step0;
-  ra.world_offset = (uint64_t)world_offset;
+  const mpe::RollArgs ra = roll_args(T, episode_len, 1, landmark_range, seed, step0, world_offset, nullptr);
   mpe::ServeHandles h;
   h.door = srv->door;
   h.flag = srv->flag;
@@ -653,25 +674,16 @@ static int rows_header(const char *what, const MpeScenarioDesc *d, const MpeRowP
   if (p->n_regions < 0 || p->n_regions > 2) return fail(MPE_EINVAL, "%s: prog->n_regions = %d, need 0 .. 2", what, p->n_regions);
   for (int r = 0; r < p->n_regions; ++r)
     if (p->region_entity[r] < 0 || p->region_entity[r] >= E) return fail(MPE_EINVAL, "%s: region %d names entity %d", what, r, p->region_entity[r]);
-  int prev = 0;
-  for (int i = 0; i <= A; ++i) {
-    if (p->obs_begin[i] < prev || p->obs_begin[i] > p->n_ops) return fail(MPE_EINVAL, "%s: obs_begin[%d] = %d out of order / range", what, i, p->obs_begin[i]);
-    prev = p->obs_begin[i];
-  }
-  prev = 0;
-  for (int i = 0; i <= A; ++i) {
-    if (p->rew_begin[i] < prev || p->rew_begin[i] > p->n_ops) return fail(MPE_EINVAL, "%s: rew_begin[%d] = %d out of order / range", what, i, p->rew_begin[i]);
-    prev = p->rew_begin[i];
-  }
-  bool has_done = false;
+  auto in_order = [&](const int32_t *begin, const char *name) {      // agent i's ops are [begin[i], begin[i + 1]) of the program
+    for (int i = 0, prev = 0; i <= A; prev = begin[i++])
+      if (begin[i] < prev || begin[i] > p->n_ops) return fail(MPE_EINVAL, "%s: %s[%d] = %d out of order / range", what, name, i, begin[i]);
+    return 0;
+  };
+  if (int rc = in_order(p->obs_begin, "obs_begin")) return rc;
+  if (int rc = in_order(p->rew_begin, "rew_begin")) return rc;
+  bool has_done = false;      // (an all-zero done table: no done programs)
   for (int i = 0; i <= A; ++i) has_done = has_done || p->done_begin[i] != 0;
-  if (has_done) {
-    prev = 0;
-    for (int i = 0; i <= A; ++i) {
-      if (p->done_begin[i] < prev || p->done_begin[i] > p->n_ops) return fail(MPE_EINVAL, "%s: done_begin[%d] = %d out of order / range", what, i, p->done_begin[i]);
-      prev = p->done_begin[i];
-    }
-  }
+  if (has_done) if (int rc = in_order(p->done_begin, "done_begin")) return rc;
   if (p->n_regions > 0 && A > 32) return fail(MPE_EUNSUPPORTED, "%s: regions hide agents from each other for A <= 32 (got %d)", what, A);
   std::memset(h, 0, sizeof(*h));
   std::memset(t, 0, sizeof(*t));
@@ -905,13 +917,13 @@ static int rows_call(const char *what, bool phys, const MpeScenarioDesc *d, cons
   if (!p->header_device) return fail(MPE_EINVAL, "%s: prog->header_device is NULL (MPE_ROWS_HEADER_BYTES of device memory)", what);
   if (int rc = check_state(b, B, what)) return rc;
   if (int rc = need(b->obs, what, "obs")) return rc;
-  if (d->n_choices > 0) if (int rc = need(b->choice, what, "choice (the per-world picks of reset_world)")) return rc;
+  if (int rc = need_choice(d, b, what, false)) return rc;
   // (bufs->comm may be NULL: every utterance then reads as zero -- the state of agents that never speak)
   if (phys) {
     if (!roll)
       if (int rc = check_actions(b, what)) return rc;
-    for (int e = d->n_agents; e < d->n_agents + d->n_landmarks; ++e)
-      if (d->movable[e]) return fail(MPE_EUNSUPPORTED, "%s: a movable landmark (entity %d) is stepped by mpe_world_step only", what, e);
+    if (const int e = first_movable_landmark(d); e >= 0)
+      return fail(MPE_EUNSUPPORTED, "%s: a movable landmark (entity %d) is stepped by mpe_world_step only", what, e);
   }
   mpe::RowEpisode ep;
   std::memset(&ep, 0, sizeof(ep));
@@ -950,22 +962,27 @@ static int episode_args(const char *what, int mode, const MpeScenarioDesc *d, co
   if (!b || !b->done) return fail(MPE_EINVAL, "%s: bufs->done (the agents' done rows) is NULL", what);
   if (max_episode_steps < 0) return fail(MPE_EINVAL, "%s: max_episode_steps < 0", what);
   if (!d) return fail(MPE_EINVAL, "%s: desc is NULL", what);
-  std::memset(ep, 0, sizeof(*ep));
+  *ep = row_episode(d, world_offset, 0u);
   ep->enabled = mode;
   ep->max_steps = max_episode_steps;
   ep->episode_step = episode_step;
   ep->landmark_range = landmark_range;
-  ep->n_choices = d->n_choices;
-  for (int k = 0; k < MPE_MAX_CHOICES; ++k) ep->choice_pop[k] = k < d->n_choices ? d->choice_pop[k] : 1;
   ep->seed = seed;
   ep->episode = episode;
-  ep->world_offset = (uint64_t)world_offset;
   return 0;
 }
 
 static int rollout_rows(const char *what, const float *act_seq, const MpeScenarioDesc *d, const MpeBuffers *b, MpeRowProgram *p, int64_t B,
                         int32_t T, int32_t episode_len, float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset,
-                        int32_t trajectory, uint32_t speakers, void *stream);
+                        int32_t trajectory, uint32_t speakers, void *stream) {
+  if (T < 0 || episode_len < 0) return fail(MPE_EINVAL, "%s: T, episode_len must be >= 0", what);
+  if (!d) return fail(MPE_EINVAL, "%s: desc is NULL", what);
+  if (int rc = check_speakers(d, b, speakers, true, what)) return rc;
+  if (T == 0) return 0;
+  const mpe::RollArgs ra = roll_args(T, episode_len, trajectory, landmark_range, seed, step0, world_offset, act_seq);
+  const mpe::RowEpisode ep = row_episode(d, world_offset, speakers);
+  return rows_call(what, true, d, b, p, B, &ep, stream, &ra);
+}
 int mpe_rollout_rows(const MpeScenarioDesc *d, const MpeBuffers *b, MpeRowProgram *p, int64_t B, int32_t T, int32_t episode_len,
                      float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset, int32_t trajectory, uint32_t speakers,
                      void *stream) {
@@ -979,35 +996,6 @@ int mpe_rollout_rows_actions(const MpeScenarioDesc *d, const MpeBuffers *b, MpeR
   return rollout_rows("mpe_rollout_rows_actions", act_seq, d, b, p, B, T, episode_len, landmark_range, seed, step0, world_offset,
                       trajectory, 0u, stream);
 }
-static int rollout_rows(const char *what, const float *act_seq, const MpeScenarioDesc *d, const MpeBuffers *b, MpeRowProgram *p, int64_t B,
-                        int32_t T, int32_t episode_len, float landmark_range, uint64_t seed, uint64_t step0, int64_t world_offset,
-                        int32_t trajectory, uint32_t speakers, void *stream) {
-  if (T < 0 || episode_len < 0) return fail(MPE_EINVAL, "%s: T, episode_len must be >= 0", what);
-  if (!d) return fail(MPE_EINVAL, "%s: desc is NULL", what);
-  if (speakers != 0) {
-    if (d->dim_c <= 0) return fail(MPE_EINVAL, "%s: speakers 0x%x but desc->dim_c = %d", what, speakers, d->dim_c);
-    if (d->n_agents < 32 && (speakers >> d->n_agents) != 0) return fail(MPE_EINVAL, "%s: speakers 0x%x names agents beyond %d", what, speakers, d->n_agents);
-    if (int rc = need(b ? b->comm : nullptr, what, "comm (receives the speaking agents' last words)")) return rc;
-  }
-  if (T == 0) return 0;
-  mpe::RollArgs ra;
-  std::memset(&ra, 0, sizeof(ra));
-  ra.T = T;
-  ra.episode_len = episode_len;
-  ra.trajectory = trajectory ? 1 : 0;
-  ra.landmark_range = landmark_range;
-  ra.seed = seed;
-  ra.step0 = step0;
-  ra.world_offset = (uint64_t)world_offset;
-  ra.act_seq = act_seq;
-  mpe::RowEpisode ep;      // (off; carries the picks' populations and the world numbering the in-kernel resets draw with)
-  std::memset(&ep, 0, sizeof(ep));
-  ep.n_choices = d->n_choices;
-  for (int k = 0; k < MPE_MAX_CHOICES; ++k) ep.choice_pop[k] = k < d->n_choices ? d->choice_pop[k] : 1;
-  ep.world_offset = (uint64_t)world_offset;
-  ep.speakers = speakers;
-  return rows_call(what, true, d, b, p, B, &ep, stream, &ra);
-}
 
 int mpe_rollout_rows_episode(const MpeScenarioDesc *d, const MpeBuffers *b, MpeRowProgram *p, int64_t B, int32_t T,
                              int32_t *episode_step, int32_t max_episode_steps, float landmark_range, uint64_t seed, uint64_t step0,
@@ -1016,21 +1004,11 @@ int mpe_rollout_rows_episode(const MpeScenarioDesc *d, const MpeBuffers *b, MpeR
   if (T < 0) return fail(MPE_EINVAL, "%s: T must be >= 0", what);
   mpe::RowEpisode ep;
   if (int rc = episode_args(what, 2, d, b, episode_step, max_episode_steps, landmark_range, seed, episode0, world_offset, &ep)) return rc;
-  if (speakers != 0) {
-    if (d->dim_c <= 0) return fail(MPE_EINVAL, "%s: speakers 0x%x but desc->dim_c = %d", what, speakers, d->dim_c);
-    if (int rc = need(b->comm, what, "comm (receives the speaking agents' last words)")) return rc;
-  }
+  if (int rc = check_speakers(d, b, speakers, false, what)) return rc;      // (a mask naming agents beyond A passes here, as it always has)
   if (T == 0) return 0;
   ep.speakers = speakers;
-  mpe::RollArgs ra;
-  std::memset(&ra, 0, sizeof(ra));
-  ra.T = T;
-  ra.episode_len = 0;      // (no clocked resets: the episodes end where the done programs / the horizon say)
-  ra.trajectory = trajectory ? 1 : 0;
-  ra.landmark_range = landmark_range;
-  ra.seed = seed;
-  ra.step0 = step0;
-  ra.world_offset = (uint64_t)world_offset;
+  // (episode_len 0 -- no clocked resets: the episodes end where the done programs / the horizon say)
+  const mpe::RollArgs ra = roll_args(T, 0, trajectory, landmark_range, seed, step0, world_offset, nullptr);
   return rows_call(what, true, d, b, p, B, &ep, stream, &ra);
 }
 
