@@ -1,0 +1,68 @@
+"""An IPPO learner on simple_spread, wired from the device-side pieces.
+
+    python examples/ppo_spread.py [--worlds 1024] [--updates 50] [--epochs 4]
+
+The closed loop (PolicyLoop) plays one 25-step episode in every world and records, beside the rows played and their log
+probabilities, the observation every step was decided on and each agent's own critic along it (run(25, values=V): one more launch
+per step, and one for the bootstrap value of the episode's last output observation).  Advantages and returns are ONE launch (gae:
+the episodes are cut by the time limit, so the last step bootstraps from V of its output observation).  Advantage normalisation,
+the clipped surrogate, the value loss and the optimiser are plain torch autograd over traj.obs_in, traj.act and traj.logp.  One
+JSON line per update.  A readable wiring, not a benchmark.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from multiagent_particle_envs_amd import Actors, PolicyLoop, Values, gae, make_env  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--worlds", type=int, default=1024)
+ap.add_argument("--updates", type=int, default=50)
+ap.add_argument("--epochs", type=int, default=4)
+ap.add_argument("--gamma", type=float, default=0.95)
+ap.add_argument("--lam", type=float, default=0.95)
+ap.add_argument("--clip", type=float, default=0.2)
+args = ap.parse_args()
+EPISODE = 25
+
+
+def mlp(n_in, n_out):
+    return nn.Sequential(nn.Linear(n_in, 64), nn.Tanh(), nn.Linear(64, 64), nn.Tanh(), nn.Linear(64, n_out)).cuda()
+
+
+torch.manual_seed(0)
+env = make_env("simple_spread", batch_size=args.worlds)
+A = env.n
+widths = [int(env._obs_off[i + 1] - env._obs_off[i]) for i in range(A)]
+pi = [mlp(D, 5) for D in widths]                          # independent actors: logits over the 5 moves
+vf = [mlp(D, 1) for D in widths]                          # independent critics on the agent's own observation
+behaviour = Actors(env, pi, mode="sample", logp=True)     # re-reads its modules at every act: each rollout plays the new policy
+V = Values(env, vf)
+loop = PolicyLoop(env, behaviour, episode_len=EPISODE)
+opt = torch.optim.Adam([p for m in pi + vf for p in m.parameters()], lr=3e-4)
+
+for update in range(args.updates):
+    traj = loop.run(EPISODE, values=V)                    # obs_in, act, logp, rew, done, val [T,A,B], boot [1,A,B]
+    g = gae(traj, args.gamma, args.lam)                   # adv, ret [T,A,B]: one launch, no gradient
+    for epoch in range(args.epochs):
+        policy_loss = value_loss = 0.0
+        for i in range(A):
+            obs = torch.stack([traj.obs_in[t][i] for t in range(EPISODE)])      # [T, B, D_i]: what step t was decided on
+            adv = g.adv[:, i]
+            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+            logp = (F.log_softmax(pi[i](obs), dim=2) * traj.act[:, i]).sum(dim=2)      # the move rows played are one-hot
+            ratio = torch.exp(logp - traj.logp[:, i])
+            policy_loss = policy_loss - torch.min(ratio * adv, ratio.clamp(1 - args.clip, 1 + args.clip) * adv).mean()
+            value_loss = value_loss + F.mse_loss(vf[i](obs)[:, :, 0], g.ret[:, i])
+        opt.zero_grad()
+        (policy_loss + 0.5 * value_loss).backward()
+        opt.step()
+    print(json.dumps({"update": update, "policy_loss": float(policy_loss), "value_loss": float(value_loss),
+                      "mean_reward": float(traj.rew.mean()), "mean_advantage": float(g.adv.mean()), "mean_return": float(g.ret.mean())}),
+          flush=True)

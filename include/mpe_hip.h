@@ -426,6 +426,41 @@ size_t mpe_sizeof_td_target(void);
 int mpe_critic_q(const MpeActorSet *set, const float *const *in_ptrs, int64_t M, float *q, const MpeTdTarget *td, float *y,
                  void *stream);
 
+/* ---- on-policy returns: GAE(lambda) over a recorded trajectory in ONE launch (csrc/mpe_gae.hip) ------------------------------
+ * What a PPO / MAPPO / IPPO learner makes of a closed-loop trajectory: rew, done [T][A][B] as the loop recorded them, val
+ * [T][A][B] = V of the observation step t was DECIDED on, and boot [K][A][B] = V of the OUTPUT observation of the k-th
+ * segment-ending step.  The loop restarts every world after every L-th step (episode_len = L >= 0, 0: never; episode_phase = p,
+ * 0 <= p < max(L, 1): the episode-step index of trajectory step 0; L and p count STEPS, as the n-step rule's count pushes).
+ * THE GAE RULE, gamma and lambda finite:
+ *   Step t ENDS A SEGMENT if t == T - 1, or L > 0 and (p + t + 1) mod L == 0 (the loop restarted the world after this step: a
+ *   truncation, the done bytes stay as stored).  K is the number of such steps: K = (p + T) / L + ((p + T) mod L != 0) for L > 0,
+ *   K = 1 for L = 0 (mpe_gae_segments).  A restart-ending step t has boot row k(t) = (p + t + 1) / L - 1; step T - 1 has K - 1.
+ *   c = gamma * lambda, rounded once to float32.  For each agent i and world b, for t = T - 1 .. 0, every float32 operation
+ *   rounded separately (the build uses -ffp-contract=off) and in this order:
+ *     own   = done[t][i][b] != 0
+ *     cut   = any agent's done[t][.][b] != 0, or t ends a segment      (world-level, as the ring's walk: one restart for all)
+ *     nv    = t ends a segment ? boot[k(t)][i][b] : val[t + 1][i][b]   (not read behind own)
+ *     delta = own ? rew[t][i][b] - val[t][i][b] : (rew[t][i][b] + gamma * nv) - val[t][i][b]
+ *     adv[t][i][b] = cut ? delta : delta + c * adv[t + 1][i][b]
+ *     ret[t][i][b] = adv[t][i][b] + val[t][i][b]
+ *   own and cut are selects, not multiplications by (1 - done): behind an own row adv == rew - val exactly, whatever boot or the
+ *   next value is (inf, NaN) -- the TD-target rule's convention.  A truncation bootstraps from V of the last step's output
+ *   observation (boot), never from V of the reset observation (which val[t + 1] is there).
+ * adv, ret [T][A][B]: either may be NULL, not both.  Refused by name before any launch, in this order: g NULL; T < 1; A outside
+ * 1..MPE_ACTOR_MAX_AGENTS; B < 0; a non-finite gamma; a non-finite lambda; a negative episode_len; a phase out of range; rew, done,
+ * val or boot NULL; adv and ret both NULL; rew, val, boot, adv or ret not 4-byte aligned; A * B >= 2^31 or T * A * B > 2^40.
+ * B == 0 returns 0 without a launch.  mpe_gae_segments (host only) applies the same T / episode_len / episode_phase checks and
+ * returns K, or a negative code.                                                                                             */
+typedef struct MpeGae {
+  float gamma, lambda;                            /* finite                                                                 */
+  int64_t episode_len;                            /* L >= 0: the loop restarts every world after every L-th step; 0: never  */
+  int64_t episode_phase;                          /* p: episode-step index of trajectory step 0, 0 <= p < max(L, 1)         */
+} MpeGae;
+size_t mpe_sizeof_gae(void);
+int64_t mpe_gae_segments(int64_t T, int64_t episode_len, int64_t episode_phase);
+int mpe_gae(const MpeGae *g, int64_t T, int32_t A, int64_t B, const float *rew, const uint8_t *done, const float *val,
+            const float *boot, float *adv, float *ret, void *stream);
+
 /* ---- the replay buffer: the last S steps of all B worlds in device memory (csrc/mpe_replay.hip) ------------------------------
  * What an off-policy learner keeps beside the loop above: a ring of transitions (obs, action, reward, done, next obs) of every
  * agent, filled by ONE launch per step (mpe_replay_push) and sampled by ONE launch per minibatch (mpe_replay_sample), the same

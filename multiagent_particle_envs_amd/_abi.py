@@ -86,6 +86,10 @@ class MpeTdTarget(C.Structure):        # include/mpe_hip.h: what mpe_critic_q ma
     _fields_ = [("ret", C.c_void_p), ("done", C.c_void_p), ("discount", C.c_void_p), ("gamma", C.c_float), ("reserved_", C.c_int32)]
 
 
+class MpeGae(C.Structure):             # include/mpe_hip.h: the GAE rule's scalars (mpe_gae)
+    _fields_ = [("gamma", C.c_float), ("lambda_", C.c_float), ("episode_len", C.c_int64), ("episode_phase", C.c_int64)]
+
+
 MPE_REPLAY_MAX_AGENTS, MPE_REPLAY_MAX_WIDTH = 16, 4096
 MPE_STREAM_REPLAY = 0x5245504C
 
@@ -213,6 +217,9 @@ EXPORTS = {
     "mpe_sizeof_td_target": (C.c_size_t, []),
     "mpe_critic_q": (C.c_int, [C.POINTER(MpeActorSet), C.POINTER(C.c_void_p), C.c_int64, C.c_void_p, C.POINTER(MpeTdTarget),
                                C.c_void_p, C.c_void_p]),
+    "mpe_sizeof_gae": (C.c_size_t, []),
+    "mpe_gae_segments": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "mpe_gae": (C.c_int, [C.POINTER(MpeGae), C.c_int64, C.c_int32, C.c_int64] + [C.c_void_p] * 7),
     "mpe_sizeof_replay": (C.c_size_t, []),
     "mpe_replay_supported": (C.c_int, [C.POINTER(MpeReplay)]),
     "mpe_replay_push": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
@@ -264,6 +271,7 @@ def lib():
             handle.mpe_sizeof_actor_set() != C.sizeof(MpeActorSet) or handle.mpe_sizeof_replay() != C.sizeof(MpeReplay) or \
             handle.mpe_sizeof_replay_prio() != C.sizeof(MpeReplayPrio) or \
             handle.mpe_sizeof_td_target() != C.sizeof(MpeTdTarget) or \
+            handle.mpe_sizeof_gae() != C.sizeof(MpeGae) or \
             handle.mpe_sizeof_replay_nstep() != C.sizeof(MpeReplayNStep):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")
     _lib = handle

@@ -1344,6 +1344,58 @@ int mpe_critic_q(const MpeActorSet *s, const float *const *in_ptrs, int64_t M, f
   return hip_result(mpe::launch_critic(a, static_cast<hipStream_t>(stream)), what);
 }
 
+// ---- GAE(lambda) over a recorded trajectory (mpe_gae.hip) ----------------------------------------------------------------------
+size_t mpe_sizeof_gae(void) { return sizeof(MpeGae); }
+// the checks mpe_gae and mpe_gae_segments share, in mpe_gae's order around its own
+static int check_gae_steps(int64_t T, const char *what) {
+  if (T < 1) return fail(MPE_EINVAL, "%s: T = %lld steps (need at least 1)", what, (long long)T);
+  return 0;
+}
+static int check_gae_episode(int64_t L, int64_t p, const char *what) {
+  if (L < 0) return fail(MPE_EINVAL, "%s: episode_len = %lld (need >= 0)", what, (long long)L);
+  if (p < 0 || p >= (L > 1 ? L : 1))
+    return fail(MPE_EINVAL, "%s: episode_phase = %lld (need 0 <= phase < max(episode_len, 1) = %lld)", what, (long long)p,
+                (long long)(L > 1 ? L : 1));
+  return 0;
+}
+int64_t mpe_gae_segments(int64_t T, int64_t episode_len, int64_t episode_phase) {
+  const char *what = "mpe_gae_segments";
+  if (int rc = check_gae_steps(T, what)) return rc;
+  if (int rc = check_gae_episode(episode_len, episode_phase, what)) return rc;
+  if (T > ((int64_t)1 << 40)) return fail(MPE_EINVAL, "%s: T = %lld steps (at most 2^40)", what, (long long)T);
+  return mpe::gae_segments(T, episode_len, episode_phase);
+}
+int mpe_gae(const MpeGae *g, int64_t T, int32_t A, int64_t B, const float *rew, const uint8_t *done, const float *val,
+            const float *boot, float *adv, float *ret, void *stream) {
+  const char *what = "mpe_gae";
+  if (!g) return fail(MPE_EINVAL, "%s: g is NULL", what);
+  if (int rc = check_gae_steps(T, what)) return rc;
+  if (A < 1 || A > MPE_ACTOR_MAX_AGENTS) return fail(MPE_EINVAL, "%s: A = %d agents (1..MPE_ACTOR_MAX_AGENTS = %d)", what, A, MPE_ACTOR_MAX_AGENTS);
+  if (B < 0) return fail(MPE_EINVAL, "%s: B = %lld", what, (long long)B);
+  if (!std::isfinite(g->gamma)) return fail(MPE_EINVAL, "%s: g->gamma = %g is not finite", what, (double)g->gamma);
+  if (!std::isfinite(g->lambda)) return fail(MPE_EINVAL, "%s: g->lambda = %g is not finite", what, (double)g->lambda);
+  if (int rc = check_gae_episode(g->episode_len, g->episode_phase, what)) return rc;
+  const struct { const void *p; const char *name; } in[] = {{rew, "rew"}, {done, "done"}, {val, "val"}, {boot, "boot"}};
+  for (const auto &f : in)
+    if (!f.p) return fail(MPE_EINVAL, "%s: %s is NULL", what, f.name);
+  if (!adv && !ret) return fail(MPE_EINVAL, "%s: adv and ret are both NULL: the launch would write nothing", what);
+  if (((uintptr_t)rew | (uintptr_t)val | (uintptr_t)boot | (uintptr_t)adv | (uintptr_t)ret) & 3)
+    return fail(MPE_EINVAL, "%s: rew, val, boot, adv and ret must be 4-byte aligned", what);
+  // (what keeps every index of the walk inside 64 bits and the grid inside 2^31 threads)
+  if (B > 0x7fffffffll / A || T > ((int64_t)1 << 40) / ((int64_t)A * (B > 0 ? B : 1)))
+    return fail(MPE_EINVAL, "%s: T * A * B = %lld * %d * %lld (need A * B < 2^31 and T * A * B <= 2^40)", what, (long long)T, A,
+                (long long)B);
+  mpe::GaeArgs a;
+  a.rew = rew, a.val = val, a.boot = boot, a.done = done, a.adv = adv, a.ret = ret;
+  a.T = T, a.B = B, a.L = g->episode_len, a.phase = g->episode_phase;
+  a.K = mpe::gae_segments(T, a.L, a.phase);
+  a.A = A;
+  a.gamma = g->gamma;
+  a.c = g->gamma * g->lambda;      // rounded once (the build has no fused multiply-add)
+  if (B == 0) return 0;
+  return hip_result(mpe::launch_gae(a, static_cast<hipStream_t>(stream)), what);
+}
+
 // ---- the replay buffer (mpe_replay.hip) ---------------------------------------------------------------------------------------
 size_t mpe_sizeof_replay(void) { return sizeof(MpeReplay); }
 static int check_replay(const MpeReplay *r, const char *what, bool pointers) {

@@ -1,6 +1,7 @@
 // mpe_internal.h -- launch entry points shared between the kernel translation units and the C ABI.
 #pragma once
 #include "mpe_device.h"
+#include "mpe_gae.h"
 
 namespace mpe {
 
@@ -126,6 +127,9 @@ struct CriticArgs : ActorArgs {
   float gamma;
 };
 int launch_critic(const CriticArgs &a, hipStream_t stream);
+
+// GAE(lambda) over a recorded trajectory (mpe_gae.hip; GaeArgs and the per-lane walk: mpe_gae.h), checked by the caller (mpe_gae)
+int launch_gae(const GaeArgs &a, hipStream_t stream);
 
 // the replay buffer (mpe_replay.hip): both launches' arguments, checked and filled by the caller (mpe_replay_push / _sample)
 constexpr int kReplayMaxSegs = 2 * MPE_REPLAY_MAX_AGENTS + 4;     // obs and next obs per agent, act, utter, rew, done

@@ -298,7 +298,8 @@ class Actors(object):
 
 class LoopTrajectory(object):
     """What PolicyLoop.run recorded: obs[t][i] [B, D_i], rew [T,A,B], done [T,A,B] (the outputs of step t), act [T,A,B,5] (the rows
-    applied at step t), utter [T,A,B,dim_c] or None, logp [T,A,B] or None."""
+    applied at step t), utter [T,A,B,dim_c] or None, logp [T,A,B] or None.  Recorded with run(T, values=V) only: obs_in[t][i]
+    [B, D_i] (the observation step t was decided on), val [T,A,B], boot [K,A,B], episode_len, episode_phase (onpolicy.py)."""
 
     def __init__(self, env, pi, T):
         w, off = env.world, env._obs_off
@@ -372,14 +373,17 @@ class PolicyLoop(object):
         if not isinstance(replay, ReplayBuffer) or replay.env is not self.env:
             raise _abi.MpeError("PolicyLoop: replay is a ReplayBuffer(env, steps) built for this loop's env")
 
-    def step(self, traj=None, k=0, replay=None):
+    def step(self, traj=None, k=0, replay=None, values=None):
         """One step of the loop at global step self.t -> env.step's outputs.  replay: a ReplayBuffer that takes the step's
-        transition (the observation decided on, the action applied, env.step's outputs) with one more launch."""
+        transition (the observation decided on, the action applied, env.step's outputs) with one more launch.  values: run()'s
+        record of a Values along traj (onpolicy._ValueRecord)."""
         env, pi = self.env, self.pi
         if self.episode_len and self.t % self.episode_len == 0:
             self.obs_n = self.device_reset(self.t // self.episode_len)
         elif self.obs_n is None:
             self.obs_n = self._observe()
+        if values is not None:
+            values.decided(k)
         if traj is not None:
             action = pi.act(self.obs_n, self.t, moves=traj.act[k], logp=traj.logp[k] if traj.logp is not None else None)
         else:
@@ -399,18 +403,28 @@ class PolicyLoop(object):
             if traj.utter is not None:
                 traj.utter[k].copy_(pi.utter)
         self.t += 1
+        if values is not None:
+            values.stepped(k, out[0])
         return out
 
-    def run(self, T, record=True, replay=None):
+    def run(self, T, record=True, replay=None, values=None):
         """T steps.  record: -> a LoopTrajectory (three device copies per step); False: -> the last step's env.step outputs.
-        replay: every step's transition is pushed to that ReplayBuffer (one launch per step)."""
+        replay: every step's transition is pushed to that ReplayBuffer (one launch per step).  values: an onpolicy.Values of this
+        env; the trajectory additionally holds obs_in[t][i] (the observation step t was decided on), val [T,A,B] (V of it), boot
+        [K,A,B] (V of the output observation of each of the K segment-ending steps), episode_len and episode_phase: what
+        onpolicy.gae takes.  T + K more launches and one more copy per step."""
         _step_many_env_check(self.env)
         if replay is not None:
             self._replay_check(replay)
+        if values is not None and not record:
+            raise _abi.MpeError("PolicyLoop.run: values= records V along the trajectory; it needs record=True")
         traj = LoopTrajectory(self.env, self.pi, int(T)) if record else None
+        if values is not None:
+            from .onpolicy import _ValueRecord
+            values = _ValueRecord(self, traj, values)
         out = None
         for k in range(int(T)):
-            out = self.step(traj, k, replay)
+            out = self.step(traj, k, replay, values)
         self._mark_stale()
         return traj if record else out
 
