@@ -1,13 +1,16 @@
 """An IPPO learner on simple_spread, wired from the device-side pieces.
 
-    python examples/ppo_spread.py [--worlds 1024] [--updates 50] [--epochs 4]
+    python examples/ppo_spread.py [--worlds 1024] [--updates 50] [--epochs 4] [--minibatch M]
 
 The closed loop (PolicyLoop) plays one 25-step episode in every world and records, beside the rows played and their log
 probabilities, the observation every step was decided on and each agent's own critic along it (run(25, values=V): one more launch
 per step, and one for the bootstrap value of the episode's last output observation).  Advantages and returns are ONE launch (gae:
 the episodes are cut by the time limit, so the last step bootstraps from V of its output observation).  Advantage normalisation,
-the clipped surrogate, the value loss and the optimiser are plain torch autograd over traj.obs_in, traj.act and traj.logp.  One
-JSON line per update.  A readable wiring, not a benchmark.
+the clipped surrogate, the value loss and the optimiser are plain torch autograd over traj.obs_in, traj.act and traj.logp.  With
+--minibatch M every epoch is a shuffled pass over minibatches of M (step, world) pairs instead (Minibatches: the advantage
+statistics once per rollout, then ONE launch per minibatch that draws its rows from a keyed permutation and gathers every agent's
+observation, move, log probability, normalised advantage and return).  One JSON line per update.  A readable wiring, not a
+benchmark.
 """
 import argparse
 import json
@@ -19,7 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from multiagent_particle_envs_amd import Actors, PolicyLoop, Values, gae, make_env  # noqa: E402
+from multiagent_particle_envs_amd import Actors, Minibatches, PolicyLoop, Values, gae, make_env  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--worlds", type=int, default=1024)
@@ -28,6 +31,7 @@ ap.add_argument("--epochs", type=int, default=4)
 ap.add_argument("--gamma", type=float, default=0.95)
 ap.add_argument("--lam", type=float, default=0.95)
 ap.add_argument("--clip", type=float, default=0.2)
+ap.add_argument("--minibatch", type=int, default=0, help="rows per shuffled minibatch; 0: one full-batch step per epoch")
 args = ap.parse_args()
 EPISODE = 25
 
@@ -47,10 +51,29 @@ V = Values(env, vf)
 loop = PolicyLoop(env, behaviour, episode_len=EPISODE)
 opt = torch.optim.Adam([p for m in pi + vf for p in m.parameters()], lr=3e-4)
 
+
+def losses(i, obs, act, old_logp, adv, ret):
+    """agent i's clipped surrogate and value loss over rows of any leading shape"""
+    logp = (F.log_softmax(pi[i](obs), dim=-1) * act).sum(dim=-1)      # the move rows played are one-hot
+    ratio = torch.exp(logp - old_logp)
+    return -torch.min(ratio * adv, ratio.clamp(1 - args.clip, 1 + args.clip) * adv).mean(), F.mse_loss(vf[i](obs)[..., 0], ret)
+
+
 for update in range(args.updates):
     traj = loop.run(EPISODE, values=V)                    # obs_in, act, logp, rew, done, val [T,A,B], boot [1,A,B]
     g = gae(traj, args.gamma, args.lam)                   # adv, ret [T,A,B]: one launch, no gradient
+    mbs = Minibatches(traj, g, args.minibatch, seed=update) if args.minibatch else None      # + the advantage statistics, once
     for epoch in range(args.epochs):
+        if mbs is not None:
+            for batch in mbs.epoch(epoch):                # one launch each: rows of a keyed shuffle, adv already normalised
+                policy_loss = value_loss = 0.0
+                for i in range(A):
+                    pl, vl = losses(i, batch.obs_n[i], batch.act[i], batch.logp[i], batch.adv[i], batch.ret[i])
+                    policy_loss, value_loss = policy_loss + pl, value_loss + vl
+                opt.zero_grad()
+                (policy_loss + 0.5 * value_loss).backward()
+                opt.step()
+            continue
         policy_loss = value_loss = 0.0
         for i in range(A):
             obs = torch.stack([traj.obs_in[t][i] for t in range(EPISODE)])      # [T, B, D_i]: what step t was decided on

@@ -461,6 +461,69 @@ int64_t mpe_gae_segments(int64_t T, int64_t episode_len, int64_t episode_phase);
 int mpe_gae(const MpeGae *g, int64_t T, int32_t A, int64_t B, const float *rew, const uint8_t *done, const float *val,
             const float *boot, float *adv, float *ret, void *stream);
 
+/* ---- on-policy minibatches: advantage statistics and a shuffled gather in ONE launch (csrc/mpe_onpolicy.hip) -------------------
+ * What a PPO / IPPO / MAPPO update loop consumes, the on-policy counterpart of mpe_replay_sample.  The trajectory is laid out as
+ * the ring is, a step where the ring has a slot:
+ *   obs_in  [T][sum D_i * B]   agent i's block at floats off[i] * B .. off[i + 1] * B of a step, [B][D_i] row-major
+ *   act     [T][A][B][5]       utter [T][A][B][dim_c] (NULL when dim_c = 0)
+ *   logp, adv, ret, val  [T][A][B]      (logp may be NULL: then nothing is gathered for it)
+ * THE MINIBATCH RULE.  N = T * B.  Position q in [0, N) names step t = q / B and world b = q % B: the index
+ * idx = t * B + b of a (step, world) pair, the same for every agent, as the ring's draws are.  For a given (seed, epoch), perm is
+ * a bijection of [0, N): a 4-round Feistel network with cycle walking.
+ *   w = max(1, ceil(bits(N - 1) / 2)) with bits(0) = 0; mask = 2^w - 1.
+ *   The round keys k_0 .. k_3 are the four words (x, y, z, w) of Philox4x32-10 with key (seed lo, seed hi) on the counter
+ *     (epoch lo, epoch hi, 0, MPE_STREAM_MINIBATCH).
+ *   One pass over x: L = x >> w, R = x & mask; for r = 0 .. 3: (L, R) <- (R, L ^ (fmix32((uint32)R ^ k_r) & mask)); then
+ *     x = L << w | R.  fmix32 is the 32-bit MurmurHash3 finaliser:
+ *     h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16.
+ *   perm(q) applies passes to x = q (at least one) until x < N.
+ *   Termination: a pass is a bijection of [0, 2^(2 w)) and q < N, so the cycle of q under it returns to q, a value below N: the
+ *   walk reaches a value below N after finitely many passes and needs no iteration cap.  (Injective: perm(q) is the next value
+ *   below N on q's cycle.)
+ *   Row r of the minibatch that starts at position `first` is the pair perm(first + r).  first + M <= N is required, so the
+ *   minibatches first = 0, M, 2 M, .. of one epoch partition the trajectory.
+ *   The epoch used is epoch + (epoch_add ? *epoch_add : 0): epoch_add is an optional DEVICE uint64, read by the launch, so a
+ *   captured graph moves to a new shuffle at every replay when the caller bumps it.
+ * THE ADVANTAGE STATISTICS RULE.  Per agent i the elements are x_e = adv[t][i][b], e = t * B + b in ascending order, N = T * B of
+ * them.  Sums are in float64, in ONE fixed order: chunks hold 4096 elements; inside chunk c, lane j of 256 adds (double) x and
+ * (double) x * (double) x of elements c * 4096 + j + 256 k, k = 0 .. 15 in that order (elements >= N are skipped); the 256 lane
+ * sums are folded by s_j += s_(j + stride) for stride = 128, 64, .., 1; the chunk partials are added sequentially in ascending c,
+ * giving S and Q.  mean = S / N; var = max(0, (Q - S * mean) / (N - 1)), and 0 for N = 1 (the unbiased form); every double
+ * operation rounded on its own (the build uses -ffp-contract=off).
+ *   stats[i] = { (float) mean, 1.0f / ((float) sqrt(var) + eps) },  eps a finite float >= 0.
+ * A normalised advantage is (adv - mean) * rstd: two float32 operations, each rounded on its own.
+ * mpe_adv_stats: adv [T][A][B]; work: mpe_adv_stats_work(T, A, B) doubles of device memory, 8-byte aligned, every one of them
+ * written before it is read (no need to clear it); stats [A][2].  Two launches, no atomics, no host synchronisation.  Refused by
+ * name before any launch, in this order: T < 1; A outside 1..MPE_ACTOR_MAX_AGENTS; B < 0; adv, work or stats NULL; adv or stats not
+ * 4-byte or work not 8-byte aligned; A * B >= 2^31, T >= 2^31 or T * A * B > 2^40; a non-finite or negative eps.  B == 0 returns 0
+ * without a launch.  mpe_adv_stats_work (host only) applies the T, A, B and size checks and returns the count, or a negative code.
+ * mpe_onpolicy_batch: ONE launch.  Outputs, M rows each: idx int64 [M]; obs: agent i's [M][D_i] block at floats off[i] * M; act
+ * [A][M][5]; utter [A][M][dim_c]; logp, adv, ret, val [A][M]; joint_obs (optional) [M][sum D_i], every agent's observation side
+ * by side in agent order.  Every row output is a bit copy of its source; adv is (adv - stats[i][0]) * stats[i][1] when stats
+ * (device, [A][2]) is given and a bit copy when it is NULL.  Refused by name before any launch, in this order: traj NULL; T < 1; A
+ * outside 1..MPE_ACTOR_MAX_AGENTS; B < 0; an observation width outside 1..MPE_REPLAY_MAX_WIDTH; dim_c outside
+ * 0..MPE_REPLAY_MAX_WIDTH; M < 0; first < 0 or first + M > T * B; traj->obs_in, act, adv, ret or val NULL; idx, obs, act, adv, ret
+ * or val NULL; dim_c > 0 and traj->utter or utter NULL; logp given on one side only; a float pointer not 4-byte aligned, idx or
+ * epoch_add not 8-byte aligned; A * B >= 2^31, T >= 2^31 or T * A * B > 2^40.  M == 0 or B == 0 returns 0 without a launch.
+ * mpe_onpolicy_perm (host only): perm(q) for N = T * B by the very function the kernel calls, or a negative code (N outside
+ * 1..2^40, q outside [0, N)).                                                                                                 */
+#define MPE_STREAM_MINIBATCH 0x4D494E49u        /* "MINI": the round keys of the minibatch permutation                      */
+typedef struct MpeOnPolicyTraj {
+  int64_t T;                                      /* steps, >= 1                                                            */
+  int32_t A;                                      /* agents, 1..MPE_ACTOR_MAX_AGENTS                                        */
+  int32_t dim_c;                                  /* utterance width, 0: none                                               */
+  int64_t B;                                      /* worlds                                                                 */
+  int32_t obs_width[16];                          /* D_i, 1..MPE_REPLAY_MAX_WIDTH                                           */
+  const float *obs_in, *act, *utter, *logp, *adv, *ret, *val;
+} MpeOnPolicyTraj;
+size_t mpe_sizeof_onpolicy_traj(void);
+int64_t mpe_onpolicy_perm(int64_t N, uint64_t seed, uint64_t epoch, int64_t q);
+int64_t mpe_adv_stats_work(int64_t T, int32_t A, int64_t B);
+int mpe_adv_stats(int64_t T, int32_t A, int64_t B, const float *adv, float eps, double *work, float *stats, void *stream);
+int mpe_onpolicy_batch(const MpeOnPolicyTraj *traj, int64_t M, int64_t first, uint64_t seed, uint64_t epoch,
+                       const uint64_t *epoch_add, const float *stats, int64_t *idx, float *obs, float *act, float *utter, float *logp,
+                       float *adv, float *ret, float *val, float *joint_obs, void *stream);
+
 /* ---- the replay buffer: the last S steps of all B worlds in device memory (csrc/mpe_replay.hip) ------------------------------
  * What an off-policy learner keeps beside the loop above: a ring of transitions (obs, action, reward, done, next obs) of every
  * agent, filled by ONE launch per step (mpe_replay_push) and sampled by ONE launch per minibatch (mpe_replay_sample), the same

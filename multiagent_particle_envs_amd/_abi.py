@@ -90,6 +90,15 @@ class MpeGae(C.Structure):             # include/mpe_hip.h: the GAE rule's scala
     _fields_ = [("gamma", C.c_float), ("lambda_", C.c_float), ("episode_len", C.c_int64), ("episode_phase", C.c_int64)]
 
 
+MPE_STREAM_MINIBATCH = 0x4D494E49
+
+
+class MpeOnPolicyTraj(C.Structure):    # include/mpe_hip.h: a recorded trajectory as mpe_onpolicy_batch reads it
+    _fields_ = [("T", C.c_int64), ("A", C.c_int32), ("dim_c", C.c_int32), ("B", C.c_int64), ("obs_width", C.c_int32 * 16),
+                ("obs_in", C.c_void_p), ("act", C.c_void_p), ("utter", C.c_void_p), ("logp", C.c_void_p), ("adv", C.c_void_p),
+                ("ret", C.c_void_p), ("val", C.c_void_p)]
+
+
 MPE_REPLAY_MAX_AGENTS, MPE_REPLAY_MAX_WIDTH = 16, 4096
 MPE_STREAM_REPLAY = 0x5245504C
 
@@ -220,6 +229,11 @@ EXPORTS = {
     "mpe_sizeof_gae": (C.c_size_t, []),
     "mpe_gae_segments": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "mpe_gae": (C.c_int, [C.POINTER(MpeGae), C.c_int64, C.c_int32, C.c_int64] + [C.c_void_p] * 7),
+    "mpe_sizeof_onpolicy_traj": (C.c_size_t, []),
+    "mpe_onpolicy_perm": (C.c_int64, [C.c_int64, C.c_uint64, C.c_uint64, C.c_int64]),
+    "mpe_adv_stats_work": (C.c_int64, [C.c_int64, C.c_int32, C.c_int64]),
+    "mpe_adv_stats": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mpe_onpolicy_batch": (C.c_int, [C.POINTER(MpeOnPolicyTraj), C.c_int64, C.c_int64, C.c_uint64, C.c_uint64] + [C.c_void_p] * 12),
     "mpe_sizeof_replay": (C.c_size_t, []),
     "mpe_replay_supported": (C.c_int, [C.POINTER(MpeReplay)]),
     "mpe_replay_push": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
@@ -272,6 +286,7 @@ def lib():
             handle.mpe_sizeof_replay_prio() != C.sizeof(MpeReplayPrio) or \
             handle.mpe_sizeof_td_target() != C.sizeof(MpeTdTarget) or \
             handle.mpe_sizeof_gae() != C.sizeof(MpeGae) or \
+            handle.mpe_sizeof_onpolicy_traj() != C.sizeof(MpeOnPolicyTraj) or \
             handle.mpe_sizeof_replay_nstep() != C.sizeof(MpeReplayNStep):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")
     _lib = handle

@@ -1396,6 +1396,101 @@ int mpe_gae(const MpeGae *g, int64_t T, int32_t A, int64_t B, const float *rew, 
   return hip_result(mpe::launch_gae(a, static_cast<hipStream_t>(stream)), what);
 }
 
+// ---- on-policy minibatches (mpe_onpolicy.hip) -----------------------------------------------------------------------------------
+size_t mpe_sizeof_onpolicy_traj(void) { return sizeof(MpeOnPolicyTraj); }
+// the checks the three entry points share, in the order every one of them states
+static int check_onp_shape(int64_t T, int32_t A, int64_t B, const char *what) {
+  if (T < 1) return fail(MPE_EINVAL, "%s: T = %lld steps (need at least 1)", what, (long long)T);
+  if (A < 1 || A > MPE_ACTOR_MAX_AGENTS) return fail(MPE_EINVAL, "%s: A = %d agents (1..MPE_ACTOR_MAX_AGENTS = %d)", what, A, MPE_ACTOR_MAX_AGENTS);
+  if (B < 0) return fail(MPE_EINVAL, "%s: B = %lld", what, (long long)B);
+  return 0;
+}
+// (what keeps every index inside 64 bits, a step and a world inside 32, and the grids inside 2^31 blocks)
+static int check_onp_size(int64_t T, int32_t A, int64_t B, const char *what) {
+  if (B > 0x7fffffffll / A || T > 0x7fffffffll || T > ((int64_t)1 << 40) / ((int64_t)A * (B > 0 ? B : 1)))
+    return fail(MPE_EINVAL, "%s: T * A * B = %lld * %d * %lld (need A * B < 2^31, T < 2^31 and T * A * B <= 2^40)", what, (long long)T, A,
+                (long long)B);
+  return 0;
+}
+int64_t mpe_onpolicy_perm(int64_t N, uint64_t seed, uint64_t epoch, int64_t q) {
+  const char *what = "mpe_onpolicy_perm";
+  if (N < 1 || N > ((int64_t)1 << 40)) return fail(MPE_EINVAL, "%s: N = %lld (1..2^40)", what, (long long)N);
+  if (q < 0 || q >= N) return fail(MPE_EINVAL, "%s: q = %lld (need 0 <= q < N = %lld)", what, (long long)q, (long long)N);
+  return (int64_t)mpe::onp_perm(mpe::onp_make_perm((uint64_t)N, seed, epoch), (uint64_t)q);
+}
+int64_t mpe_adv_stats_work(int64_t T, int32_t A, int64_t B) {
+  const char *what = "mpe_adv_stats_work";
+  if (int rc = check_onp_shape(T, A, B, what)) return rc;
+  if (int rc = check_onp_size(T, A, B, what)) return rc;
+  return (int64_t)(2 * (uint64_t)A * mpe::adv_chunks((uint64_t)T * (uint64_t)B));
+}
+int mpe_adv_stats(int64_t T, int32_t A, int64_t B, const float *adv, float eps, double *work, float *stats, void *stream) {
+  const char *what = "mpe_adv_stats";
+  if (int rc = check_onp_shape(T, A, B, what)) return rc;
+  const struct { const void *p; const char *name; } in[] = {{adv, "adv"}, {work, "work"}, {stats, "stats"}};
+  for (const auto &f : in)
+    if (!f.p) return fail(MPE_EINVAL, "%s: %s is NULL", what, f.name);
+  if ((((uintptr_t)adv | (uintptr_t)stats) & 3) || ((uintptr_t)work & 7))
+    return fail(MPE_EINVAL, "%s: adv and stats must be 4-byte and work 8-byte aligned", what);
+  if (int rc = check_onp_size(T, A, B, what)) return rc;
+  if (!std::isfinite(eps) || eps < 0.f) return fail(MPE_EINVAL, "%s: eps = %g (need a finite value >= 0)", what, (double)eps);
+  mpe::AdvStatsArgs a;
+  a.adv = adv, a.work = work, a.stats = stats;
+  a.T = (uint64_t)T, a.B = (uint64_t)B, a.N = (uint64_t)T * (uint64_t)B;
+  a.A = A;
+  a.eps = eps;
+  if (B == 0) return 0;
+  return hip_result(mpe::launch_adv_stats(a, static_cast<hipStream_t>(stream)), what);
+}
+int mpe_onpolicy_batch(const MpeOnPolicyTraj *tr, int64_t M, int64_t first, uint64_t seed, uint64_t epoch, const uint64_t *epoch_add,
+                       const float *stats, int64_t *idx, float *obs, float *act, float *utter, float *logp, float *adv, float *ret,
+                       float *val, float *joint_obs, void *stream) {
+  const char *what = "mpe_onpolicy_batch";
+  if (!tr) return fail(MPE_EINVAL, "%s: traj is NULL", what);
+  if (int rc = check_onp_shape(tr->T, tr->A, tr->B, what)) return rc;
+  for (int i = 0; i < tr->A; ++i)
+    if (tr->obs_width[i] < 1 || tr->obs_width[i] > MPE_REPLAY_MAX_WIDTH)
+      return fail(MPE_EINVAL, "%s: obs_width[%d] = %d (1..MPE_REPLAY_MAX_WIDTH = %d)", what, i, tr->obs_width[i], MPE_REPLAY_MAX_WIDTH);
+  if (tr->dim_c < 0 || tr->dim_c > MPE_REPLAY_MAX_WIDTH)
+    return fail(MPE_EINVAL, "%s: dim_c = %d (0..MPE_REPLAY_MAX_WIDTH = %d)", what, tr->dim_c, MPE_REPLAY_MAX_WIDTH);
+  if (M < 0) return fail(MPE_EINVAL, "%s: M = %lld", what, (long long)M);
+  // (T * B saturates: whatever overflows 63 bits is refused by the size check below)
+  const int64_t N = tr->B > 0 && tr->T > INT64_MAX / tr->B ? INT64_MAX : tr->T * tr->B;
+  if (first < 0 || first > N || M > N - first)
+    return fail(MPE_EINVAL, "%s: first = %lld, M = %lld (need 0 <= first and first + M <= T * B = %lld)", what, (long long)first,
+                (long long)M, (long long)N);
+  const struct { const void *p; const char *name; } need[] = {
+      {tr->obs_in, "traj->obs_in"}, {tr->act, "traj->act"}, {tr->adv, "traj->adv"}, {tr->ret, "traj->ret"}, {tr->val, "traj->val"},
+      {idx, "idx"}, {obs, "obs"}, {act, "act"}, {adv, "adv"}, {ret, "ret"}, {val, "val"}};
+  for (const auto &f : need)
+    if (!f.p) return fail(MPE_EINVAL, "%s: %s is NULL", what, f.name);
+  if (tr->dim_c > 0 && !tr->utter) return fail(MPE_EINVAL, "%s: traj->utter is NULL and dim_c = %d", what, tr->dim_c);
+  if (tr->dim_c > 0 && !utter) return fail(MPE_EINVAL, "%s: utter is NULL and dim_c = %d", what, tr->dim_c);
+  if (!tr->logp != !logp)
+    return fail(MPE_EINVAL, "%s: %s is given and %s is NULL (both, or neither)", what, logp ? "logp" : "traj->logp", logp ? "traj->logp" : "logp");
+  const uintptr_t f4 = (uintptr_t)tr->obs_in | (uintptr_t)tr->act | (uintptr_t)tr->utter | (uintptr_t)tr->logp | (uintptr_t)tr->adv |
+                       (uintptr_t)tr->ret | (uintptr_t)tr->val | (uintptr_t)stats | (uintptr_t)obs | (uintptr_t)act | (uintptr_t)utter |
+                       (uintptr_t)logp | (uintptr_t)adv | (uintptr_t)ret | (uintptr_t)val | (uintptr_t)joint_obs;
+  if ((f4 & 3) || (((uintptr_t)idx | (uintptr_t)epoch_add) & 7))
+    return fail(MPE_EINVAL, "%s: every float tensor must be 4-byte, idx and epoch_add 8-byte aligned", what);
+  if (int rc = check_onp_size(tr->T, tr->A, tr->B, what)) return rc;
+  mpe::OnpArgs a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  a.obs_in = tr->obs_in, a.act = tr->act, a.utter = tr->dim_c > 0 ? tr->utter : nullptr, a.logp = tr->logp, a.adv = tr->adv;
+  a.ret = tr->ret, a.val = tr->val, a.stats = stats, a.epoch_add = epoch_add, a.idx = idx;
+  a.o_obs = obs, a.o_act = act, a.o_utter = utter, a.o_logp = logp, a.o_adv = adv, a.o_ret = ret, a.o_val = val, a.joint_obs = joint_obs;
+  a.T = (uint64_t)tr->T, a.B = (uint64_t)tr->B, a.M = (uint64_t)M, a.first = (uint64_t)first, a.seed = seed, a.epoch = epoch;
+  a.A = tr->A, a.dim_c = tr->dim_c;
+  for (int i = 0; i < tr->A; ++i) {
+    a.off[i + 1] = a.off[i] + tr->obs_width[i];
+    a.magic[i] = mpe::replay_magic((uint32_t)tr->obs_width[i]);
+  }
+  a.d_sum = a.off[tr->A];
+  a.magic_c = mpe::replay_magic((uint32_t)tr->dim_c);
+  if (M == 0 || tr->B == 0) return 0;
+  return hip_result(mpe::launch_onpolicy_batch(a, static_cast<hipStream_t>(stream)), what);
+}
+
 // ---- the replay buffer (mpe_replay.hip) ---------------------------------------------------------------------------------------
 size_t mpe_sizeof_replay(void) { return sizeof(MpeReplay); }
 static int check_replay(const MpeReplay *r, const char *what, bool pointers) {

@@ -2,6 +2,8 @@
 #pragma once
 #include "mpe_device.h"
 #include "mpe_gae.h"
+#include "mpe_gather.h"
+#include "mpe_onpolicy.h"
 
 namespace mpe {
 
@@ -130,6 +132,26 @@ int launch_critic(const CriticArgs &a, hipStream_t stream);
 
 // GAE(lambda) over a recorded trajectory (mpe_gae.hip; GaeArgs and the per-lane walk: mpe_gae.h), checked by the caller (mpe_gae)
 int launch_gae(const GaeArgs &a, hipStream_t stream);
+
+// on-policy minibatches (mpe_onpolicy.hip; OnpArgs, AdvStatsArgs and the index arithmetic: mpe_onpolicy.h), checked by the caller
+constexpr uint32_t kStreamMinibatch = 0x4d494e49u;  // "MINI"
+static_assert(kStreamMinibatch == MPE_STREAM_MINIBATCH, "include/mpe_hip.h names the minibatch stream");
+static_assert(kOnpMaxAgents == MPE_ACTOR_MAX_AGENTS && kOnpActionDim == MPE_ACTION_DIM, "mpe_onpolicy.h restates both");
+// THE MINIBATCH RULE's round keys: the four words of one Philox block (the kernel and mpe_onpolicy_perm call this one function)
+__host__ __device__ inline OnpPerm onp_make_perm(uint64_t N, uint64_t seed, uint64_t epoch) {
+  OnpPerm p;
+  onp_perm_shape(p, N);
+  U4 c;
+  c.x = (uint32_t)epoch;
+  c.y = (uint32_t)(epoch >> 32);
+  c.z = 0u;
+  c.w = kStreamMinibatch;
+  const U4 o = philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  p.k[0] = o.x, p.k[1] = o.y, p.k[2] = o.z, p.k[3] = o.w;
+  return p;
+}
+int launch_adv_stats(const AdvStatsArgs &a, hipStream_t stream);            // two launches: the chunk sums, then the ordered final pass
+int launch_onpolicy_batch(const OnpArgs &a, hipStream_t stream);
 
 // the replay buffer (mpe_replay.hip): both launches' arguments, checked and filled by the caller (mpe_replay_push / _sample)
 constexpr int kReplayMaxSegs = 2 * MPE_REPLAY_MAX_AGENTS + 4;     // obs and next obs per agent, act, utter, rew, done

@@ -70,35 +70,7 @@ __global__ __launch_bounds__(kReplayPushThreads) void k_replay_push(const Replay
   }
 }
 
-// Rows of W floats gathered for the n samples of a tile: lanes run over the tile's n * W OUTPUT floats (stores fully coalesced,
-// loads coalesced within a gathered row), four independent elements per lane in flight; element e is row e / W = umulhi(e, magic).
-// d2: the same values into rows of a joint tensor (row stride w2), or nullptr.
-__device__ __forceinline__ void gather_rows(const float *__restrict__ src, uint64_t slot_stride, uint32_t W, uint32_t magic,
-                                            float *__restrict__ d1, float *__restrict__ d2, uint32_t w2, const uint32_t *s_slot,
-                                            const uint32_t *s_world, uint32_t n) {
-  const uint32_t total = n * W;
-  for (uint32_t e0 = threadIdx.x; e0 < total; e0 += 4 * 256) {
-    float v[4];
-    uint32_t r[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t e = e0 + k * 256;
-      if (e < total) {
-        r[k] = magic ? __umulhi(e, magic) : e;
-        const uint32_t col = e - r[k] * W;
-        v[k] = src[(uint64_t)s_slot[r[k]] * slot_stride + (uint64_t)s_world[r[k]] * W + col];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t e = e0 + k * 256;
-      if (e < total) {
-        d1[e] = v[k];
-        if (d2) d2[(uint64_t)r[k] * w2 + (e - r[k] * W)] = v[k];
-      }
-    }
-  }
-}
+// (gather_rows, the row gather of the jobs below: csrc/mpe_gather.h, shared with k_onpolicy_batch)
 
 // Only the n-step instantiations hold an NStepTile in LDS (1 792 bytes) and take ReplayNStepArgs; NoNStep stands in for both in
 // the one-step ones, which never name either.
@@ -200,16 +172,16 @@ __global__ __launch_bounds__(256) void k_replay_sample(const ReplaySampleArgs a,
     const uint32_t w2 = nx ? (uint32_t)a.d_sum : (uint32_t)a.joint_width;
     const uint32_t *slots = s_slot;
     if constexpr (NSTEP) slots = nx ? s_ns.last : s_slot;
-    gather_rows(src, (uint64_t)a.d_sum * B, W, a.magic[i], d1, jt ? jt + m0 * w2 + a.off[i] : nullptr, w2, slots, s_world, n);
+    gather_rows(t, src, (uint64_t)a.d_sum * B, W, a.magic[i], d1, jt ? jt + m0 * w2 + a.off[i] : nullptr, w2, slots, s_world, n);
   } else if (job < 3 * A) {
     const uint32_t i = job - 2 * A, W = MPE_ACTION_DIM;
     float *jt = a.joint && a.col_move[i] >= 0 ? a.joint + m0 * (uint32_t)a.joint_width + a.col_move[i] : nullptr;
-    gather_rows(a.act + (uint64_t)i * B * W, (uint64_t)A * B * W, W, 0x33333334u, a.o_act + ((uint64_t)i * M + m0) * W, jt,
+    gather_rows(t, a.act + (uint64_t)i * B * W, (uint64_t)A * B * W, W, 0x33333334u, a.o_act + ((uint64_t)i * M + m0) * W, jt,
                 (uint32_t)a.joint_width, s_slot, s_world, n);
   } else if (job < rew_job) {      // (only with dim_c > 0: otherwise rew_job == 3 * A)
     const uint32_t i = job - 3 * A, W = (uint32_t)a.dim_c;
     float *jt = a.joint && a.col_utter[i] >= 0 ? a.joint + m0 * (uint32_t)a.joint_width + a.col_utter[i] : nullptr;
-    gather_rows(a.utter + (uint64_t)i * B * W, (uint64_t)A * B * W, W, a.magic_c, a.o_utter + ((uint64_t)i * M + m0) * W, jt,
+    gather_rows(t, a.utter + (uint64_t)i * B * W, (uint64_t)A * B * W, W, a.magic_c, a.o_utter + ((uint64_t)i * M + m0) * W, jt,
                 (uint32_t)a.joint_width, s_slot, s_world, n);
   } else {
     for (uint32_t e = t; e < A * kReplayTile; e += 256) {      // lanes over a tile's samples of one agent

@@ -2,11 +2,15 @@
 centralised, on all of them) in ONE launch (mpe_critic_q with per-agent pointers and widths), `PolicyLoop.run(T, values=V)` records
 V along the closed loop -- of the observation every step was decided on, and of the output observation of every segment-ending
 step --, and `gae` turns the recorded trajectory into advantages and returns in ONE launch (mpe_gae: THE GAE RULE of
-include/mpe_hip.h).  Backward passes, advantage normalisation and the clipped loss stay in torch autograd.
+include/mpe_hip.h).  `Minibatches` then hands the update loop its shuffled minibatches: the advantage statistics once
+per trajectory (mpe_adv_stats) and ONE launch per minibatch that draws its rows from a keyed permutation of the (step, world) pairs
+and gathers every field of every agent, the advantages normalised (mpe_onpolicy_batch).  Backward passes, the
+clipped loss and the optimiser stay in torch autograd.
 
     V = Values(env, critic_modules)
     traj = loop.run(25, values=V)               # + traj.obs_in, traj.val [T,A,B], traj.boot [K,A,B]
     g = gae(traj, gamma=0.99, lam=0.95)         # g.adv, g.ret [T,A,B]
+    for batch in Minibatches(traj, g, 4096).epoch(e): ...      # batch.obs_n[i] [M,D_i], batch.act, .logp, .adv, .ret, .val [A,M]
 """
 import ctypes as C
 import math
@@ -232,3 +236,185 @@ def gae(traj, gamma, lam, out=None):
     if getattr(traj, "val", None) is None or getattr(traj, "boot", None) is None:
         raise _abi.MpeError("gae: traj holds no values: record it with PolicyLoop.run(T, values=Values(env, modules))")
     return gae_tensors(traj.rew, traj.done, traj.val, traj.boot, gamma, lam, traj.episode_len, traj.episode_phase, out)
+
+
+# ---- minibatches: advantage statistics and the shuffled one-launch gather (mpe_adv_stats / mpe_onpolicy_batch) ----
+def perm(N, seed, epoch, q):
+    """perm(q) of THE MINIBATCH RULE for a trajectory of N = T * B (step, world) pairs (mpe_onpolicy_perm, host only)."""
+    j = _abi.lib().mpe_onpolicy_perm(int(N), int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1), int(q))
+    if j < 0:
+        _abi.check(int(j), "mpe_onpolicy_perm")
+    return int(j)
+
+
+def _stats_work(T, A, B, dev, cache={}):
+    """the float64 workspace of mpe_adv_stats for one shape on one device (every entry is written before it is read)"""
+    n = _abi.lib().mpe_adv_stats_work(T, A, B)
+    if n < 0:
+        _abi.check(int(n), "mpe_adv_stats_work")
+    key = (T, A, B, dev)
+    w = cache.get(key)
+    if w is None:
+        if len(cache) >= 16:
+            cache.clear()
+        w = cache[key] = torch.empty((max(int(n), 1),), dtype=torch.float64, device=dev)
+    return w
+
+
+def adv_stats(g_or_adv, eps=1e-8, out=None):
+    """Per-agent advantage mean and 1 / (std + eps) by THE ADVANTAGE STATISTICS RULE: two launches, no host synchronisation.
+    g_or_adv: a GaeResult or an adv [T, A, B] float32 tensor on a GPU.  -> stats [A, 2] float32 (`out`, or a new tensor)."""
+    who = "adv_stats"
+    adv = g_or_adv.adv if isinstance(g_or_adv, GaeResult) else g_or_adv
+    if not torch.is_tensor(adv) or adv.dtype != torch.float32 or adv.dim() != 3 or not adv.is_contiguous():
+        raise _abi.MpeError("%s: adv is a contiguous float32 [T, A, B] tensor on a GPU" % who)
+    T, A, B = (int(n) for n in adv.shape)
+    dev = adv.device
+    if not math.isfinite(float(eps)) or float(eps) < 0:
+        raise _abi.MpeError("%s: eps = %r (a finite value >= 0)" % (who, eps))
+    if out is None:
+        out = torch.empty((A, 2), dtype=torch.float32, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (A, 2) or not out.is_contiguous() or out.device != dev:
+        raise _abi.MpeError("%s: out is a contiguous float32 [%d, 2] tensor on adv's device" % (who, A))
+    if not adv.is_cuda:
+        raise _abi.MpeError("%s: adv is on %s (the tensors live on a GPU: there is no CPU path)" % (who, dev))
+    work = _stats_work(T, A, B, dev)
+    _abi.check(_abi.lib().mpe_adv_stats(T, A, B, adv.data_ptr(), float(eps), work.data_ptr(), out.data_ptr(), _abi.raw_stream(dev)),
+               "mpe_adv_stats")
+    return out
+
+
+class OnPolicyBatch(object):
+    """One minibatch of M rows, every tensor this object's Minibatches owns (rewritten by the next batch() of the same M):
+    idx [M] int64 (t * B + b), obs_n: A views [M, D_i] of the flat tensor `obs`, act [A, M, 5], utter [A, M, dim_c] or None, logp
+    [A, M] or None, adv, ret, val [A, M], joint_obs [M, sum D_i] or None."""
+    __slots__ = ("M", "B", "idx", "obs", "obs_n", "act", "utter", "logp", "adv", "ret", "val", "joint_obs")
+
+    @property
+    def t(self):
+        return torch.div(self.idx, self.B, rounding_mode="floor")
+
+    @property
+    def b(self):
+        return self.idx % self.B
+
+
+class Minibatches(object):
+    """Shuffled minibatches of a recorded trajectory by THE MINIBATCH RULE: batch(epoch, k) is ONE launch that draws rows
+    k * M .. of the (seed, epoch) permutation of the T * B (step, world) pairs and gathers every field of every agent for them.
+    traj: what PolicyLoop.run(T, values=V) recorded (obs_in_flat, act, utter, logp, val); g: gae's GaeResult.  normalise: adv is
+    written (adv - mean) * rstd, the statistics (adv_stats(g, eps)) computed once here -- restats() after g.adv was rewritten.
+    joint: also joint_obs [M, sum D_i], the input of Values(centralised=True).  epoch_counter: a device uint64 tensor of one
+    element added to every batch's epoch by the launch itself (a captured graph reshuffles when the caller bumps it).
+    No host synchronisation: {gae, adv_stats, batch} captures into a HIP graph."""
+
+    def __init__(self, traj, g, M, seed=0, normalise=True, joint=False, eps=1e-8, epoch_counter=None):
+        who = "Minibatches"
+        if not isinstance(g, GaeResult):
+            raise _abi.MpeError("%s: g is a GaeResult (what gae returned)" % who)
+        flat = getattr(traj, "obs_in_flat", None)
+        if flat is None or getattr(traj, "val", None) is None:
+            raise _abi.MpeError("%s: traj holds no decision observations: record it with PolicyLoop.run(T, values=Values(env, modules))" % who)
+        _tensor_check(g.adv, "g.adv", None, (torch.float32,), None, who)
+        if g.adv.dim() != 3:
+            raise _abi.MpeError("%s: g.adv is a contiguous float32 [T, A, B] tensor on a GPU" % who)
+        T, A, B = (int(n) for n in g.adv.shape)
+        dev = g.adv.device
+
+        def chk(x, name, shape):
+            if not torch.is_tensor(x) or x.dtype != torch.float32 or tuple(x.shape) != tuple(shape) or not x.is_contiguous() or x.device != dev:
+                raise _abi.MpeError("%s: %s is a contiguous float32 %s tensor on g.adv's device" % (who, name, list(shape)))
+        chk(g.ret, "g.ret", (T, A, B))
+        chk(traj.val, "traj.val", (T, A, B))
+        chk(traj.act, "traj.act", (T, A, B, _abi.MPE_ACTION_DIM))
+        widths = getattr(traj, "obs_widths", None)
+        if widths is None:
+            widths = [int(o.shape[1]) for o in traj.obs_in[0]]
+        widths = [int(d) for d in widths]
+        if len(widths) != A:
+            raise _abi.MpeError("%s: %d observation widths for %d agents" % (who, len(widths), A))
+        chk(flat, "traj.obs_in_flat", (T, sum(widths) * B))
+        utter, logp = getattr(traj, "utter", None), getattr(traj, "logp", None)
+        dim_c = 0
+        if utter is not None:
+            if not torch.is_tensor(utter) or utter.dim() != 4:
+                raise _abi.MpeError("%s: traj.utter is a contiguous float32 [T, A, B, dim_c] tensor on g.adv's device" % who)
+            dim_c = int(utter.shape[3])
+            chk(utter, "traj.utter", (T, A, B, dim_c))
+        if logp is not None:
+            chk(logp, "traj.logp", (T, A, B))
+        if int(M) < 1:
+            raise _abi.MpeError("%s: M = %r rows (need at least 1)" % (who, M))
+        if epoch_counter is not None and (not torch.is_tensor(epoch_counter) or epoch_counter.dtype not in (torch.uint64, torch.int64) or
+                                          epoch_counter.numel() != 1 or epoch_counter.device != dev):
+            raise _abi.MpeError("%s: epoch_counter is a uint64 (or int64) tensor of one element on g.adv's device" % who)
+        if not g.adv.is_cuda:
+            raise _abi.MpeError("%s: g.adv is on %s (the tensors live on a GPU: there is no CPU path)" % (who, dev))
+        self.traj, self.g, self.T, self.A, self.B, self.N, self.M = traj, g, T, A, B, T * B, int(M)
+        self.widths, self.dim_c, self.device = widths, dim_c, dev
+        self.seed, self.joint, self.eps, self.epoch_counter = int(seed) & (2 ** 64 - 1), bool(joint), float(eps), epoch_counter
+        self._keep = (flat, traj.act, utter, logp, traj.val)
+        tr = self._traj = _abi.MpeOnPolicyTraj()
+        tr.T, tr.A, tr.B, tr.dim_c = T, A, B, dim_c
+        for i, d in enumerate(widths):
+            tr.obs_width[i] = d
+        tr.obs_in, tr.act, tr.utter = flat.data_ptr(), traj.act.data_ptr(), utter.data_ptr() if dim_c else None
+        tr.logp, tr.adv, tr.ret, tr.val = logp.data_ptr() if logp is not None else None, g.adv.data_ptr(), g.ret.data_ptr(), traj.val.data_ptr()
+        self.stats = torch.empty((A, 2), dtype=torch.float32, device=dev) if normalise else None
+        self._out = {}
+        if normalise:
+            self.restats()
+
+    def restats(self):
+        """The statistics of g.adv as it stands now (two launches, into this object's `stats`)."""
+        if self.stats is None:
+            raise _abi.MpeError("Minibatches.restats: built with normalise=False")
+        return adv_stats(self.g, self.eps, out=self.stats)
+
+    def __len__(self):
+        return (self.N + self.M - 1) // self.M
+
+    def _outputs(self, M):
+        o = self._out.get(M)
+        if o is None:
+            if len(self._out) >= 16:
+                self._out.clear()
+            A, dev, f = self.A, self.device, torch.float32
+            o = OnPolicyBatch()
+            o.M, o.B = M, self.B
+            o.idx = torch.zeros((M,), dtype=torch.int64, device=dev)
+            o.obs = torch.zeros((sum(self.widths) * M,), dtype=f, device=dev)
+            off, o.obs_n = 0, []
+            for d in self.widths:
+                o.obs_n.append(o.obs[off * M:(off + d) * M].view(M, d))
+                off += d
+            o.act = torch.zeros((A, M, _abi.MPE_ACTION_DIM), dtype=f, device=dev)
+            o.utter = torch.zeros((A, M, self.dim_c), dtype=f, device=dev) if self.dim_c else None
+            o.logp = torch.zeros((A, M), dtype=f, device=dev) if self._keep[3] is not None else None
+            o.adv, o.ret, o.val = (torch.zeros((A, M), dtype=f, device=dev) for _ in range(3))
+            o.joint_obs = torch.zeros((M, sum(self.widths)), dtype=f, device=dev) if self.joint else None
+            self._out[M] = o
+        return o
+
+    def batch(self, epoch, k, M=None):
+        """Minibatch k of `epoch`: rows k * self.M .. of the permutation (M rows; the default: self.M, or what is left of the
+        trajectory behind k * self.M).  One launch.  -> OnPolicyBatch."""
+        first = int(k) * self.M
+        if int(k) < 0 or first >= self.N:
+            raise _abi.MpeError("Minibatches.batch: k = %r (an epoch has %d minibatches of %d rows)" % (k, len(self), self.M))
+        M = min(self.M, self.N - first) if M is None else int(M)
+        o = self._outputs(M)
+        ptr = lambda x: x.data_ptr() if x is not None else None      # noqa: E731
+        _abi.check(_abi.lib().mpe_onpolicy_batch(
+            C.byref(self._traj), M, first, self.seed, int(epoch) & (2 ** 64 - 1), ptr(self.epoch_counter), ptr(self.stats), o.idx.data_ptr(),
+            o.obs.data_ptr(), o.act.data_ptr(), ptr(o.utter), ptr(o.logp), o.adv.data_ptr(), o.ret.data_ptr(), o.val.data_ptr(),
+            ptr(o.joint_obs), _abi.raw_stream(self.device)), "mpe_onpolicy_batch")
+        return o
+
+    def epoch(self, e, drop_last=False):
+        """Iterates the ceil(N / M) minibatches of epoch e (the last one short unless drop_last); together they hold every (step,
+        world) pair once."""
+        for k in range(len(self)):
+            if drop_last and (k + 1) * self.M > self.N:
+                return
+            yield self.batch(e, k)
