@@ -1,6 +1,6 @@
 """An IPPO learner on simple_spread, wired from the device-side pieces.
 
-    python examples/ppo_spread.py [--worlds 1024] [--updates 50] [--epochs 4] [--minibatch M]
+    python examples/ppo_spread.py [--worlds 1024] [--updates 50] [--epochs 4] [--minibatch M [--fused-loss]]
 
 The closed loop (PolicyLoop) plays one 25-step episode in every world and records, beside the rows played and their log
 probabilities, the observation every step was decided on and each agent's own critic along it (run(25, values=V): one more launch
@@ -9,8 +9,10 @@ the episodes are cut by the time limit, so the last step bootstraps from V of it
 the clipped surrogate, the value loss and the optimiser are plain torch autograd over traj.obs_in, traj.act and traj.logp.  With
 --minibatch M every epoch is a shuffled pass over minibatches of M (step, world) pairs instead (Minibatches: the advantage
 statistics once per rollout, then ONE launch per minibatch that draws its rows from a keyed permutation and gathers every agent's
-observation, move, log probability, normalised advantage and return).  One JSON line per update.  A readable wiring, not a
-benchmark.
+observation, move, log probability, normalised advantage and return).  With --fused-loss the clipped surrogate, the value loss and
+their gradients with respect to the logits and the values are the device's loss head instead (PpoLoss: two launches per minibatch
+for all agents; the networks' forward and backward passes stay in torch autograd).  One JSON line per update.  A readable wiring,
+not a benchmark.
 """
 import argparse
 import json
@@ -22,7 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from multiagent_particle_envs_amd import Actors, Minibatches, PolicyLoop, Values, gae, make_env  # noqa: E402
+from multiagent_particle_envs_amd import Actors, Minibatches, PolicyLoop, PpoLoss, Values, gae, make_env  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--worlds", type=int, default=1024)
@@ -32,7 +34,10 @@ ap.add_argument("--gamma", type=float, default=0.95)
 ap.add_argument("--lam", type=float, default=0.95)
 ap.add_argument("--clip", type=float, default=0.2)
 ap.add_argument("--minibatch", type=int, default=0, help="rows per shuffled minibatch; 0: one full-batch step per epoch")
+ap.add_argument("--fused-loss", action="store_true", help="the loss head on the device (PpoLoss); needs --minibatch")
 args = ap.parse_args()
+if args.fused_loss and not args.minibatch:
+    ap.error("--fused-loss needs --minibatch M (the loss head reads a minibatch's own tensors)")
 EPISODE = 25
 
 
@@ -50,6 +55,7 @@ behaviour = Actors(env, pi, mode="sample", logp=True)     # re-reads its modules
 V = Values(env, vf)
 loop = PolicyLoop(env, behaviour, episode_len=EPISODE)
 opt = torch.optim.Adam([p for m in pi + vf for p in m.parameters()], lr=3e-4)
+fused = PpoLoss(env, clip=args.clip, vf_coef=0.5) if args.fused_loss else None
 
 
 def losses(i, obs, act, old_logp, adv, ret):
@@ -66,6 +72,13 @@ for update in range(args.updates):
     for epoch in range(args.epochs):
         if mbs is not None:
             for batch in mbs.epoch(epoch):                # one launch each: rows of a keyed shuffle, adv already normalised
+                if fused is not None:                     # every agent's loss and dL/dlogits, dL/dvalues: two launches
+                    loss = fused([pi[i](batch.obs_n[i]) for i in range(A)], [vf[i](batch.obs_n[i]) for i in range(A)], batch)
+                    opt.zero_grad()
+                    loss.backward()
+                    opt.step()
+                    policy_loss, value_loss = -loss.stats[:, 0].sum(), loss.stats[:, 1].sum()
+                    continue
                 policy_loss = value_loss = 0.0
                 for i in range(A):
                     pl, vl = losses(i, batch.obs_n[i], batch.act[i], batch.logp[i], batch.adv[i], batch.ret[i])

@@ -524,6 +524,62 @@ int mpe_onpolicy_batch(const MpeOnPolicyTraj *traj, int64_t M, int64_t first, ui
                        const uint64_t *epoch_add, const float *stats, int64_t *idx, float *obs, float *act, float *utter, float *logp,
                        float *adv, float *ret, float *val, float *joint_obs, void *stream);
 
+/* ---- the PPO loss head: the clipped surrogate, its statistics and its gradients in TWO launches (csrc/mpe_ppo_loss.hip) ----------
+ * What stands between mpe_onpolicy_batch and the optimiser of a PPO / IPPO / MAPPO update, for every agent at once: the loss of a
+ * minibatch and dL/dlogits, dL/dvalues, from which torch autograd (or a later backward kernel) goes on into the networks.
+ * THE PPO LOSS RULE.  Agents i < A <= MPE_ACTOR_MAX_AGENTS, rows m < M.  The heads are laid out as in
+ * mpe_actor_act: agent i has n_out_i = 5 * movable_i + dim_c * speaks_i logits, 1 <= n_out_i <= MPE_ACTOR_MAX_OUT, the move head
+ * the first 5 and the utterance head the last dim_c (a speaker with dim_c = 0 has no utterance head).
+ *   logits_ptrs[i]  agent i's contiguous [M][n_out_i] float32 block: a HOST array of A device pointers, as obs_ptrs is
+ *   value_ptrs[i]   agent i's [M] float32 block; the whole array may be NULL: a policy-only loss, no value term, dvalues untouched
+ *   act [A][M][5], utter [A][M][dim_c], logp_old, adv, ret, val_old [A][M]: mpe_onpolicy_batch's own outputs
+ * The chosen index c of a head is the lowest index of the row's maximum in act / utter (np.argmax; the rows played are one-hot).
+ * Every float32 operation is rounded on its own (the build uses -ffp-contract=off), in the order written; inside a head exp and
+ * log are pol_head's __expf and __logf (a row's logp is what mpe_actor_act recorded for the same logits), the ratio's exp is the
+ * accurate expf.  Per head of n logits z_0 .. z_(n-1):
+ *   zm = max z;  e_j = exp(z_j - zm);  s = ((e_0 + e_1) + ..) + e_(n-1);  p_j = e_j / s;  ls = log s;  l_j = (z_j - zm) - ls
+ *   lp = l_c;  H = -(((p_0 * l_0) + p_1 * l_1) + .. + p_(n-1) * l_(n-1))
+ * Per row: logp = lp of the move head, + lp of the utterance head where the agent has both; ent = the same sum of H;
+ *   lo = 1 - clip;  hi = 1 + clip;  lr = logp - logp_old;  ratio = exp(lr);  s1 = ratio * adv;
+ *   s2 = min(max(ratio, lo), hi) * adv;  surr = min(s1, s2);  kl = (ratio - 1) - lr
+ *   g = ((lo <= ratio && ratio <= hi) || s1 < s2) ? adv : 0      -- a select: what torch.min and clamp hand back, ties and the
+ *                                                                   inclusive clamp bounds included
+ * With values: d = v - ret; a = d * d.  value_clip >= 0 (negative: off; NaN is refused): dv0 = v - val_old;
+ *   vc = val_old + min(max(dv0, -value_clip), value_clip);  b = (vc - ret) * (vc - ret);  inside = |dv0| <= value_clip;
+ *   vl = inside ? a : max(a, b);  on = inside || a >= b.  Off: vl = a, on = true.  dvl = on ? 2 * d : 0.
+ * L_i = -mean surr + vf_coef * mean vl - ent_coef * mean ent; the loss is the sum of the L_i.  The same launch writes, with
+ * Mf = (float) M, cg = (g * ratio) / Mf and ce = ent_coef / Mf, per head
+ *   dL/dz_j = (-(cg * ([j == c] - p_j))) - ce * (-(p_j * (l_j + H)))        dL/dv = (vf_coef * dvl) / Mf
+ * Sums.  Per agent surr, vl, ent, kl, [g == 0 && adv != 0] (the clipped rows) and ratio are summed in float64 in ONE fixed order:
+ * a chunk is the 256 rows of a block, one per lane (a lane at or beyond M holds +0.0); the 256 lane values are folded as THE
+ * ADVANTAGE STATISTICS RULE folds its lane sums; a second, one-block launch adds the chunk partials in ascending chunk order and
+ * writes stats [A][8] = the six means S / M (float64, rounded when stored), L_i, 0, with
+ *   L_i = ((-mean surr) + (double) vf_coef * mean vl) - (double) ent_coef * mean ent in float64,
+ * and loss = (float) of the L_i added in ascending i in float64.  No atomics, no host synchronisation.
+ * Outputs: dlogits_ptrs[i] [M][n_out_i] (a HOST array of device pointers); dvalues [A][M] (written only with value_ptrs); rows
+ * (optional) [A][M][4] = logp, surr, vl, ent: the very floats the sums consumed; work: mpe_ppo_loss_work(A, M) doubles of device
+ * memory, 8-byte aligned, every one written before it is read; stats [A][8]; loss [1].  Nothing at or beyond row M and no column at
+ * or beyond n_out_i is written.  A block of rows whose base is 16-byte aligned moves in 16-byte pieces, any other in 4-byte ones.
+ * Refused by name before any launch, in this order: cfg, logits_ptrs, logp_old, adv, dlogits_ptrs, work, stats or loss NULL; A
+ * outside 1..MPE_ACTOR_MAX_AGENTS; dim_c outside 0..MPE_ACTOR_MAX_OUT; an agent with no head, or with more than MPE_ACTOR_MAX_OUT
+ * logits; M < 0; a non-finite or negative clip; a non-finite vf_coef or ent_coef, a NaN value_clip; value_ptrs given and val_old,
+ * ret or dvalues NULL; act NULL with a movable agent, utter NULL with a speaker; a NULL logits_ptrs[i], dlogits_ptrs[i] or
+ * value_ptrs[i]; a float pointer not 4-byte or work not 8-byte aligned; A * M >= 2^31.  M == 0 returns 0 without a launch.
+ * mpe_ppo_loss_work (host only) applies the A, M and size checks and returns the count, or a negative code.                     */
+typedef struct MpePpoLoss {
+  int32_t n_agents;                               /* A, 1..MPE_ACTOR_MAX_AGENTS                                             */
+  int32_t dim_c;                                  /* utterance width, 0: none                                               */
+  uint8_t movable[16], speaks[16];                /* which heads agent i has                                                */
+  float clip;                                     /* finite, >= 0                                                           */
+  float value_clip;                               /* >= 0: the clipped value loss; negative: off                            */
+  float vf_coef, ent_coef;                        /* finite                                                                 */
+} MpePpoLoss;
+size_t mpe_sizeof_ppo_loss(void);
+int64_t mpe_ppo_loss_work(int32_t A, int64_t M);
+int mpe_ppo_loss(const MpePpoLoss *cfg, const float *const *logits_ptrs, const float *const *value_ptrs, int64_t M, const float *act,
+                 const float *utter, const float *logp_old, const float *adv, const float *ret, const float *val_old,
+                 float *const *dlogits_ptrs, float *dvalues, float *rows, double *work, float *stats, float *loss, void *stream);
+
 /* ---- the replay buffer: the last S steps of all B worlds in device memory (csrc/mpe_replay.hip) ------------------------------
  * What an off-policy learner keeps beside the loop above: a ring of transitions (obs, action, reward, done, next obs) of every
  * agent, filled by ONE launch per step (mpe_replay_push) and sampled by ONE launch per minibatch (mpe_replay_sample), the same

@@ -103,6 +103,11 @@ MPE_REPLAY_MAX_AGENTS, MPE_REPLAY_MAX_WIDTH = 16, 4096
 MPE_STREAM_REPLAY = 0x5245504C
 
 
+class MpePpoLoss(C.Structure):         # include/mpe_hip.h: the heads and scalars of THE PPO LOSS RULE (mpe_ppo_loss)
+    _fields_ = [("n_agents", C.c_int32), ("dim_c", C.c_int32), ("movable", C.c_uint8 * 16), ("speaks", C.c_uint8 * 16),
+                ("clip", C.c_float), ("value_clip", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float)]
+
+
 class MpeReplay(C.Structure):          # include/mpe_hip.h: the replay ring of mpe_replay_push / mpe_replay_sample
     _fields_ = [("n_agents", C.c_int32), ("dim_c", C.c_int32), ("B", C.c_int64), ("S", C.c_int64),
                 ("obs_width", C.c_int32 * MPE_REPLAY_MAX_AGENTS), ("movable", C.c_uint8 * MPE_REPLAY_MAX_AGENTS),
@@ -234,6 +239,10 @@ EXPORTS = {
     "mpe_adv_stats_work": (C.c_int64, [C.c_int64, C.c_int32, C.c_int64]),
     "mpe_adv_stats": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mpe_onpolicy_batch": (C.c_int, [C.POINTER(MpeOnPolicyTraj), C.c_int64, C.c_int64, C.c_uint64, C.c_uint64] + [C.c_void_p] * 12),
+    "mpe_sizeof_ppo_loss": (C.c_size_t, []),
+    "mpe_ppo_loss_work": (C.c_int64, [C.c_int32, C.c_int64]),
+    "mpe_ppo_loss": (C.c_int, [C.POINTER(MpePpoLoss), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int64] + [C.c_void_p] * 6 +
+                     [C.POINTER(C.c_void_p)] + [C.c_void_p] * 6),
     "mpe_sizeof_replay": (C.c_size_t, []),
     "mpe_replay_supported": (C.c_int, [C.POINTER(MpeReplay)]),
     "mpe_replay_push": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
@@ -287,6 +296,7 @@ def lib():
             handle.mpe_sizeof_td_target() != C.sizeof(MpeTdTarget) or \
             handle.mpe_sizeof_gae() != C.sizeof(MpeGae) or \
             handle.mpe_sizeof_onpolicy_traj() != C.sizeof(MpeOnPolicyTraj) or \
+            handle.mpe_sizeof_ppo_loss() != C.sizeof(MpePpoLoss) or \
             handle.mpe_sizeof_replay_nstep() != C.sizeof(MpeReplayNStep):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")
     _lib = handle

@@ -1491,6 +1491,87 @@ int mpe_onpolicy_batch(const MpeOnPolicyTraj *tr, int64_t M, int64_t first, uint
   return hip_result(mpe::launch_onpolicy_batch(a, static_cast<hipStream_t>(stream)), what);
 }
 
+// ---- the PPO loss head (mpe_ppo_loss.hip) ---------------------------------------------------------------------------------------
+size_t mpe_sizeof_ppo_loss(void) { return sizeof(MpePpoLoss); }
+// the checks mpe_ppo_loss and mpe_ppo_loss_work share, in mpe_ppo_loss's order around its own
+static int check_ppo_agents(int32_t A, const char *what) {
+  if (A < 1 || A > MPE_ACTOR_MAX_AGENTS) return fail(MPE_EINVAL, "%s: A = %d agents (1..MPE_ACTOR_MAX_AGENTS = %d)", what, A, MPE_ACTOR_MAX_AGENTS);
+  return 0;
+}
+static int check_ppo_rows(int64_t M, const char *what) {
+  if (M < 0) return fail(MPE_EINVAL, "%s: M = %lld", what, (long long)M);
+  return 0;
+}
+// (what keeps an [A][M] element and the grid inside 2^31)
+static int check_ppo_size(int32_t A, int64_t M, const char *what) {
+  if (M > 0x7fffffffll / A) return fail(MPE_EINVAL, "%s: A * M = %d * %lld (need A * M < 2^31)", what, A, (long long)M);
+  return 0;
+}
+int64_t mpe_ppo_loss_work(int32_t A, int64_t M) {
+  const char *what = "mpe_ppo_loss_work";
+  if (int rc = check_ppo_agents(A, what)) return rc;
+  if (int rc = check_ppo_rows(M, what)) return rc;
+  if (int rc = check_ppo_size(A, M, what)) return rc;
+  return (int64_t)((uint64_t)mpe::kPpoSums * (uint64_t)A * mpe::ppo_chunks((uint64_t)M));
+}
+int mpe_ppo_loss(const MpePpoLoss *cfg, const float *const *logits_ptrs, const float *const *value_ptrs, int64_t M, const float *act,
+                 const float *utter, const float *logp_old, const float *adv, const float *ret, const float *val_old,
+                 float *const *dlogits_ptrs, float *dvalues, float *rows, double *work, float *stats, float *loss, void *stream) {
+  const char *what = "mpe_ppo_loss";
+  const struct { const void *p; const char *name; } need[] = {{cfg, "cfg"},         {logits_ptrs, "logits_ptrs"},   {logp_old, "logp_old"},
+                                                              {adv, "adv"},         {dlogits_ptrs, "dlogits_ptrs"}, {work, "work"},
+                                                              {stats, "stats"},     {loss, "loss"}};
+  for (const auto &f : need)
+    if (!f.p) return fail(MPE_EINVAL, "%s: %s is NULL", what, f.name);
+  const int32_t A = cfg->n_agents;
+  if (int rc = check_ppo_agents(A, what)) return rc;
+  if (cfg->dim_c < 0 || cfg->dim_c > MPE_ACTOR_MAX_OUT) return fail(MPE_EINVAL, "%s: dim_c = %d (0..%d)", what, cfg->dim_c, MPE_ACTOR_MAX_OUT);
+  bool any_move = false, any_speak = false;
+  for (int i = 0; i < A; ++i) {
+    const bool mv = cfg->movable[i] != 0, sp = cfg->speaks[i] != 0 && cfg->dim_c > 0;
+    const int n_out = MPE_ACTION_DIM * mv + cfg->dim_c * sp;
+    if (n_out < 1) return fail(MPE_EINVAL, "%s: agent %d has no head (neither movable nor speaking with dim_c > 0)", what, i);
+    if (n_out > MPE_ACTOR_MAX_OUT)
+      return fail(MPE_EUNSUPPORTED, "%s: agent %d: %d logits (5 * movable + dim_c * speaks) > MPE_ACTOR_MAX_OUT = %d", what, i, n_out,
+                  MPE_ACTOR_MAX_OUT);
+    any_move |= mv, any_speak |= sp;
+  }
+  if (int rc = check_ppo_rows(M, what)) return rc;
+  if (!std::isfinite(cfg->clip) || cfg->clip < 0.f) return fail(MPE_EINVAL, "%s: clip = %g (need a finite value >= 0)", what, (double)cfg->clip);
+  if (!std::isfinite(cfg->vf_coef)) return fail(MPE_EINVAL, "%s: vf_coef = %g is not finite", what, (double)cfg->vf_coef);
+  if (!std::isfinite(cfg->ent_coef)) return fail(MPE_EINVAL, "%s: ent_coef = %g is not finite", what, (double)cfg->ent_coef);
+  if (std::isnan(cfg->value_clip)) return fail(MPE_EINVAL, "%s: value_clip is NaN (negative: off)", what);
+  if (value_ptrs) {
+    const struct { const void *p; const char *name; } with[] = {{val_old, "val_old"}, {ret, "ret"}, {dvalues, "dvalues"}};
+    for (const auto &f : with)
+      if (!f.p) return fail(MPE_EINVAL, "%s: value_ptrs is given and %s is NULL", what, f.name);
+  }
+  if (any_move && !act) return fail(MPE_EINVAL, "%s: act is NULL and an agent is movable", what);
+  if (any_speak && !utter) return fail(MPE_EINVAL, "%s: utter is NULL and an agent speaks", what);
+  uintptr_t f4 = (uintptr_t)act | (uintptr_t)utter | (uintptr_t)logp_old | (uintptr_t)adv | (uintptr_t)rows | (uintptr_t)stats | (uintptr_t)loss;
+  if (value_ptrs) f4 |= (uintptr_t)ret | (uintptr_t)val_old | (uintptr_t)dvalues;
+  for (int i = 0; i < A; ++i) {
+    if (!logits_ptrs[i]) return fail(MPE_EINVAL, "%s: logits_ptrs[%d] is NULL", what, i);
+    if (!dlogits_ptrs[i]) return fail(MPE_EINVAL, "%s: dlogits_ptrs[%d] is NULL", what, i);
+    if (value_ptrs && !value_ptrs[i]) return fail(MPE_EINVAL, "%s: value_ptrs[%d] is NULL", what, i);
+    f4 |= (uintptr_t)logits_ptrs[i] | (uintptr_t)dlogits_ptrs[i] | (value_ptrs ? (uintptr_t)value_ptrs[i] : 0);
+  }
+  if ((f4 & 3) || ((uintptr_t)work & 7)) return fail(MPE_EINVAL, "%s: every float tensor must be 4-byte and work 8-byte aligned", what);
+  if (int rc = check_ppo_size(A, M, what)) return rc;
+  mpe::PpoArgs a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  for (int i = 0; i < A; ++i) {
+    a.logits[i] = logits_ptrs[i], a.dlogits[i] = dlogits_ptrs[i], a.values[i] = value_ptrs ? value_ptrs[i] : nullptr;
+    a.movable[i] = cfg->movable[i] != 0, a.speaks[i] = cfg->speaks[i] != 0 && cfg->dim_c > 0;
+  }
+  a.act = act, a.utter = utter, a.logp_old = logp_old, a.adv = adv, a.ret = ret, a.val_old = val_old;
+  a.dvalues = dvalues, a.rows = rows, a.work = work, a.stats = stats, a.loss = loss;
+  a.M = (uint64_t)M, a.A = A, a.dim_c = cfg->dim_c, a.has_values = value_ptrs != nullptr;
+  a.clip = cfg->clip, a.value_clip = cfg->value_clip, a.vf_coef = cfg->vf_coef, a.ent_coef = cfg->ent_coef;
+  if (M == 0) return 0;
+  return hip_result(mpe::launch_ppo_loss(a, static_cast<hipStream_t>(stream)), what);
+}
+
 // ---- the replay buffer (mpe_replay.hip) ---------------------------------------------------------------------------------------
 size_t mpe_sizeof_replay(void) { return sizeof(MpeReplay); }
 static int check_replay(const MpeReplay *r, const char *what, bool pointers) {

@@ -4,6 +4,7 @@
 #include "mpe_gae.h"
 #include "mpe_gather.h"
 #include "mpe_onpolicy.h"
+#include "mpe_ppo_loss.h"
 
 namespace mpe {
 
@@ -152,6 +153,10 @@ __host__ __device__ inline OnpPerm onp_make_perm(uint64_t N, uint64_t seed, uint
 }
 int launch_adv_stats(const AdvStatsArgs &a, hipStream_t stream);            // two launches: the chunk sums, then the ordered final pass
 int launch_onpolicy_batch(const OnpArgs &a, hipStream_t stream);
+
+// the PPO loss head (mpe_ppo_loss.hip; PpoArgs, the index arithmetic and the row's arithmetic: mpe_ppo_loss.h), checked by the caller
+static_assert(kPpoMaxAgents == MPE_ACTOR_MAX_AGENTS && kPpoMaxOut == MPE_ACTOR_MAX_OUT && kPpoMove == MPE_ACTION_DIM, "mpe_ppo_loss.h restates them");
+int launch_ppo_loss(const PpoArgs &a, hipStream_t stream);                  // two launches: the rows and chunk sums, then the ordered final pass
 
 // the replay buffer (mpe_replay.hip): both launches' arguments, checked and filled by the caller (mpe_replay_push / _sample)
 constexpr int kReplayMaxSegs = 2 * MPE_REPLAY_MAX_AGENTS + 4;     // obs and next obs per agent, act, utter, rew, done

@@ -4,13 +4,16 @@ V along the closed loop -- of the observation every step was decided on, and of 
 step --, and `gae` turns the recorded trajectory into advantages and returns in ONE launch (mpe_gae: THE GAE RULE of
 include/mpe_hip.h).  `Minibatches` then hands the update loop its shuffled minibatches: the advantage statistics once
 per trajectory (mpe_adv_stats) and ONE launch per minibatch that draws its rows from a keyed permutation of the (step, world) pairs
-and gathers every field of every agent, the advantages normalised (mpe_onpolicy_batch).  Backward passes, the
-clipped loss and the optimiser stay in torch autograd.
+and gathers every field of every agent, the advantages normalised (mpe_onpolicy_batch).  `PpoLoss` is the loss
+head on such a minibatch: the clipped surrogate, the value loss, the entropy and their gradients with respect to the logits and the
+values in two launches for all agents (mpe_ppo_loss).  The networks' forward and backward passes and the optimiser
+stay in torch autograd.
 
     V = Values(env, critic_modules)
     traj = loop.run(25, values=V)               # + traj.obs_in, traj.val [T,A,B], traj.boot [K,A,B]
     g = gae(traj, gamma=0.99, lam=0.95)         # g.adv, g.ret [T,A,B]
     for batch in Minibatches(traj, g, 4096).epoch(e): ...      # batch.obs_n[i] [M,D_i], batch.act, .logp, .adv, .ret, .val [A,M]
+        loss = PpoLoss(env)(logits_n, values_n, batch)         # loss.backward(): dL/dlogits, dL/dvalues from the same two launches
 """
 import ctypes as C
 import math
@@ -418,3 +421,209 @@ class Minibatches(object):
             if drop_last and (k + 1) * self.M > self.N:
                 return
             yield self.batch(e, k)
+
+
+# ---- the PPO loss head: the clipped surrogate and its gradients in two launches (mpe_ppo_loss) ----------------------
+class PpoLossResult(object):
+    """What ppo_loss_tensors wrote: loss [1]; stats [A, 8] (per agent the means of the surrogate, the value loss, the entropy, the
+    approximate KL (ratio - 1) - log ratio, the clipped rows and the ratio, then L_i, then 0); dlogits_n: A views [M, n_out_i] and
+    dvalues [A, M] (None for a policy-only loss) of ONE flat float32 buffer `grads`, already scaled by 1 / M and the coefficients;
+    rows [A, M, 4] (logp, surr, vl, ent) or None."""
+    __slots__ = ("M", "n_out", "loss", "stats", "grads", "dlogits_n", "dvalues", "rows", "work")
+
+    STATS = ("surrogate", "value_loss", "entropy", "approx_kl", "clip_fraction", "ratio", "loss", "reserved")
+
+
+def _ppo_result(n_out, M, values, rows, dev):
+    """the buffers of one (heads, M) on one device: every agent's dlogits block starts at a multiple of 4 floats of `grads`"""
+    r = PpoLossResult()
+    A, f = len(n_out), torch.float32
+    off, at = [], 0
+    for n in n_out:
+        off.append(at)
+        at += (M * n + 3) // 4 * 4
+    r.M, r.n_out = M, list(n_out)
+    r.grads = torch.zeros((at + (A * M if values else 0),), dtype=f, device=dev)
+    r.dlogits_n = [r.grads[o:o + M * n].view(M, n) for o, n in zip(off, n_out)]
+    r.dvalues = r.grads[at:at + A * M].view(A, M) if values else None
+    r.rows = torch.zeros((A, M, 4), dtype=f, device=dev) if rows else None
+    r.stats = torch.zeros((A, 8), dtype=f, device=dev)
+    r.loss = torch.zeros((1,), dtype=f, device=dev)
+    n = _abi.lib().mpe_ppo_loss_work(A, M)
+    if n < 0:
+        _abi.check(int(n), "mpe_ppo_loss_work")
+    r.work = torch.empty((max(int(n), 1),), dtype=torch.float64, device=dev)
+    return r
+
+
+def ppo_loss_tensors(logits_n, values_n, act, utter, logp_old, adv, ret, val_old, movable, speaks, dim_c, clip=0.2, value_clip=None,
+                     vf_coef=0.5, ent_coef=0.0, rows=False, out=None):
+    """THE PPO LOSS RULE in two launches for every agent, no host synchronisation (captures into a HIP graph): the clipped
+    surrogate, the (clipped) value loss and the entropy of a minibatch, and their gradients.  logits_n[i]: agent i's [M, n_out_i]
+    float32 logits, n_out_i = 5 * movable[i] + dim_c * speaks[i]; values_n[i]: [M] or [M, 1], or values_n=None (policy only: ret and
+    val_old are not read); act [A, M, 5], utter [A, M, dim_c] (None without speakers), logp_old, adv, ret, val_old [A, M]: an
+    OnPolicyBatch's own tensors.  value_clip=None: the plain squared error.  rows=True: also the per-row logp, surr, vl, ent.
+    out: a PpoLossResult to rewrite.  -> PpoLossResult."""
+    who = "ppo_loss_tensors"
+    if not isinstance(logits_n, (list, tuple)) or not 1 <= len(logits_n) <= _abi.MPE_ACTOR_MAX_AGENTS:
+        raise _abi.MpeError("%s: logits_n is a list of 1..MPE_ACTOR_MAX_AGENTS = %d tensors, one per agent" % (who, _abi.MPE_ACTOR_MAX_AGENTS))
+    A = len(logits_n)
+    movable, speaks, dim_c = [bool(m) for m in movable], [bool(s) for s in speaks], int(dim_c)
+    if len(movable) != A or len(speaks) != A:
+        raise _abi.MpeError("%s: %d movable and %d speaks flags for %d agents" % (who, len(movable), len(speaks), A))
+    if not 0 <= dim_c <= _abi.MPE_ACTOR_MAX_OUT:
+        raise _abi.MpeError("%s: dim_c = %d (0..MPE_ACTOR_MAX_OUT = %d)" % (who, dim_c, _abi.MPE_ACTOR_MAX_OUT))
+    speaks = [s and dim_c > 0 for s in speaks]
+    n_out = [_abi.MPE_ACTION_DIM * m + dim_c * s for m, s in zip(movable, speaks)]
+    for i, n in enumerate(n_out):
+        if not 1 <= n <= _abi.MPE_ACTOR_MAX_OUT:
+            raise _abi.MpeError("%s: agent %d has %d logits (5 * movable + dim_c * speaks), need 1..MPE_ACTOR_MAX_OUT = %d"
+                                % (who, i, n, _abi.MPE_ACTOR_MAX_OUT))
+    z0 = logits_n[0]
+    if not torch.is_tensor(z0) or z0.dim() != 2:
+        raise _abi.MpeError("%s: logits_n[0] is a contiguous float32 [M, %d] tensor on a GPU" % (who, n_out[0]))
+    M, dev = int(z0.shape[0]), z0.device
+
+    def chk(x, name, shapes):
+        if not torch.is_tensor(x) or x.dtype != torch.float32 or tuple(x.shape) not in shapes or not x.is_contiguous() or x.device != dev:
+            raise _abi.MpeError("%s: %s is a contiguous float32 %s tensor on logits_n[0]'s device"
+                                % (who, name, " or ".join(str(list(s)) for s in shapes)))
+    for i, z in enumerate(logits_n):
+        chk(z, "logits_n[%d]" % i, [(M, n_out[i])])
+    if values_n is not None:
+        if not isinstance(values_n, (list, tuple)) or len(values_n) != A:
+            raise _abi.MpeError("%s: values_n is a list of %d tensors, one per agent, or None" % (who, A))
+        for i, v in enumerate(values_n):
+            chk(v, "values_n[%d]" % i, [(M,), (M, 1)])
+    if any(movable):
+        chk(act, "act", [(A, M, _abi.MPE_ACTION_DIM)])
+    if any(speaks):
+        chk(utter, "utter", [(A, M, dim_c)])
+    chk(logp_old, "logp_old", [(A, M)])
+    chk(adv, "adv", [(A, M)])
+    if values_n is not None:
+        chk(ret, "ret", [(A, M)])
+        chk(val_old, "val_old", [(A, M)])
+    if not math.isfinite(float(clip)) or float(clip) < 0:
+        raise _abi.MpeError("%s: clip = %r (a finite value >= 0)" % (who, clip))
+    if not math.isfinite(float(vf_coef)) or not math.isfinite(float(ent_coef)):
+        raise _abi.MpeError("%s: vf_coef = %r, ent_coef = %r (both finite)" % (who, vf_coef, ent_coef))
+    if value_clip is not None and (not math.isfinite(float(value_clip)) or float(value_clip) < 0):
+        raise _abi.MpeError("%s: value_clip = %r (None, or a finite value >= 0)" % (who, value_clip))
+    if out is not None:
+        if not isinstance(out, PpoLossResult) or out.M != M or out.n_out != n_out or (out.dvalues is None) != (values_n is None) or \
+                out.grads.device != dev or (rows and out.rows is None):
+            raise _abi.MpeError("%s: out is a PpoLossResult of the same heads, M = %d, values and rows (what an earlier call returned)" % (who, M))
+    n = _abi.lib().mpe_ppo_loss_work(A, M)      # (host only: the size check)
+    if n < 0:
+        _abi.check(int(n), "mpe_ppo_loss_work")
+    if not z0.is_cuda:
+        raise _abi.MpeError("%s: logits_n[0] is on %s (the tensors live on a GPU: there is no CPU path)" % (who, dev))
+    if out is None:
+        out = _ppo_result(n_out, M, values_n is not None, rows, dev)
+    cfg = _abi.MpePpoLoss()
+    cfg.n_agents, cfg.dim_c = A, dim_c
+    for i in range(A):
+        cfg.movable[i], cfg.speaks[i] = int(movable[i]), int(speaks[i])
+    cfg.clip, cfg.value_clip, cfg.vf_coef, cfg.ent_coef = float(clip), -1.0 if value_clip is None else float(value_clip), float(vf_coef), float(ent_coef)
+    ptr = lambda x: x.data_ptr() if x is not None else None      # noqa: E731
+    zp = (C.c_void_p * A)(*[z.data_ptr() for z in logits_n])
+    vp = (C.c_void_p * A)(*[v.data_ptr() for v in values_n]) if values_n is not None else None
+    gp = (C.c_void_p * A)(*[g.data_ptr() for g in out.dlogits_n])
+    use_rows = out.rows if rows else None
+    _abi.check(_abi.lib().mpe_ppo_loss(C.byref(cfg), zp, vp, M, ptr(act) if any(movable) else None, ptr(utter) if any(speaks) else None,
+                                       logp_old.data_ptr(), adv.data_ptr(), ptr(ret) if vp is not None else None,
+                                       ptr(val_old) if vp is not None else None, gp, ptr(out.dvalues), ptr(use_rows), out.work.data_ptr(),
+                                       out.stats.data_ptr(), out.loss.data_ptr(), _abi.raw_stream(dev)), "mpe_ppo_loss")
+    return out
+
+
+class _PpoLossFn(torch.autograd.Function):
+    """forward: the two launches; backward: grad_output * the gradients the forward wrote (ONE multiply over the flat buffer)"""
+
+    @staticmethod
+    def forward(ctx, head, batch, n_values, *tensors):
+        A = head.A
+        logits_n = [t.detach() for t in tensors[:A]]
+        values_n = [t.detach() for t in tensors[A:]] if n_values else None
+        M = int(logits_n[0].shape[0]) if torch.is_tensor(logits_n[0]) and logits_n[0].dim() == 2 else -1
+        key = (M, n_values > 0, logits_n[0].device if torch.is_tensor(logits_n[0]) else None)
+        res = ppo_loss_tensors(logits_n, values_n, batch.act, batch.utter, batch.logp, batch.adv, batch.ret, batch.val, head.movable,
+                               head.speaks, head.dim_c, head.clip, head.value_clip, head.vf_coef, head.ent_coef, out=head._out.get(key))
+        if key not in head._out:
+            if len(head._out) >= 16:
+                head._out.clear()
+            head._out[key] = res
+        head._generation[key] = head._generation.get(key, 0) + 1
+        ctx.res, ctx.shapes, ctx.owner = res, [tuple(t.shape) for t in tensors], (head, key, head._generation[key])
+        head.last = res
+        return res.loss.view(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        res = ctx.res
+        head, key, generation = ctx.owner
+        if head._generation.get(key) != generation or head._out.get(key) is not res:
+            raise _abi.MpeError("PpoLoss: backward() of a loss whose buffers a later forward with the same M has rewritten (the "
+                                "buffers are cached per M: call backward() before the next forward)")
+        A = len(res.dlogits_n)
+        g = grad_output * res.grads      # out of place: the buffer is rewritten by the next forward of the same M
+        at, grads = 0, []
+        for n in res.n_out:
+            grads.append(g[at:at + res.M * n].view(res.M, n))
+            at += (res.M * n + 3) // 4 * 4
+        for i, shape in enumerate(ctx.shapes[A:]):
+            grads.append(g[at + i * res.M:at + (i + 1) * res.M].view(shape))
+        return (None, None, None) + tuple(grads)
+
+
+class PpoLoss(object):
+    """The PPO loss head behind torch autograd: loss = PpoLoss(env, clip, value_clip, vf_coef, ent_coef)(logits_n, values_n, batch).
+    The heads (movable, speaks, dim_c) are the env's, as Actors takes them.  logits_n[i]: module i's [M, n_out_i] output;
+    values_n[i]: [M] or [M, 1], or values_n=None; batch: an OnPolicyBatch (its act, utter, logp, adv, ret, val).  The forward is
+    mpe_ppo_loss's two launches for all agents, the backward ONE multiply of grad_output with the gradients the forward wrote; no
+    host read anywhere.  loss is the sum over the agents of -mean surr + vf_coef * mean vl - ent_coef * mean ent; loss.stats [A, 8]
+    (device) carries PpoLossResult.STATS.  The buffers are cached per M: the loss, its stats and the gradients of one call are
+    rewritten by the next call with the same M, so call backward() (and read the stats) before the next forward; a backward()
+    behind such a forward is refused.  Once differentiable: the gradients are the forward's own, not a graph."""
+
+    def __init__(self, env, clip=0.2, value_clip=None, vf_coef=0.5, ent_coef=0.0):
+        w = env.world
+        self.env, self.A = env, len(w.agents)
+        if self.A > _abi.MPE_ACTOR_MAX_AGENTS:
+            raise _abi.MpeError("PpoLoss: %d agents (at most MPE_ACTOR_MAX_AGENTS = %d)" % (self.A, _abi.MPE_ACTOR_MAX_AGENTS))
+        self.movable = [bool(a.movable) for a in w.agents]
+        self.speaks = [not a.silent for a in w.agents]
+        self.dim_c = int(w.dim_c) if any(self.speaks) else 0
+        self.n_out = [_abi.MPE_ACTION_DIM * m + self.dim_c * s for m, s in zip(self.movable, self.speaks)]
+        for i, n in enumerate(self.n_out):
+            if not 1 <= n <= _abi.MPE_ACTOR_MAX_OUT:
+                raise _abi.MpeError("PpoLoss: agent %d has %d logits (5 * movable + dim_c * speaks), need 1..MPE_ACTOR_MAX_OUT = %d"
+                                    % (i, n, _abi.MPE_ACTOR_MAX_OUT))
+        if not math.isfinite(float(clip)) or float(clip) < 0:
+            raise _abi.MpeError("PpoLoss: clip = %r (a finite value >= 0)" % (clip,))
+        if value_clip is not None and (not math.isfinite(float(value_clip)) or float(value_clip) < 0):
+            raise _abi.MpeError("PpoLoss: value_clip = %r (None, or a finite value >= 0)" % (value_clip,))
+        if not math.isfinite(float(vf_coef)) or not math.isfinite(float(ent_coef)):
+            raise _abi.MpeError("PpoLoss: vf_coef = %r, ent_coef = %r (both finite)" % (vf_coef, ent_coef))
+        self.clip, self.value_clip, self.vf_coef, self.ent_coef = float(clip), value_clip, float(vf_coef), float(ent_coef)
+        self._out, self._generation, self.last = {}, {}, None
+
+    def __call__(self, logits_n, values_n, batch):
+        who = "PpoLoss"
+        if not isinstance(logits_n, (list, tuple)) or len(logits_n) != self.A:
+            raise _abi.MpeError("%s: logits_n is a list of %d tensors, one per agent" % (who, self.A))
+        if values_n is not None and (not isinstance(values_n, (list, tuple)) or len(values_n) != self.A):
+            raise _abi.MpeError("%s: values_n is a list of %d tensors, one per agent, or None" % (who, self.A))
+        if not isinstance(batch, OnPolicyBatch):
+            raise _abi.MpeError("%s: batch is an OnPolicyBatch (what Minibatches.batch returned)" % who)
+        if batch.logp is None:
+            raise _abi.MpeError("%s: batch.logp is None: the trajectory was recorded without log probabilities (Actors(logp=True))" % who)
+        for name, ts in (("logits_n", logits_n), ("values_n", values_n or ())):
+            for i, t in enumerate(ts):
+                if not torch.is_tensor(t):
+                    raise _abi.MpeError("%s: %s[%d] is not a tensor" % (who, name, i))
+        loss = _PpoLossFn.apply(self, batch, len(values_n) if values_n is not None else 0, *(list(logits_n) + list(values_n or ())))
+        loss.stats = self.last.stats
+        return loss
