@@ -1,6 +1,6 @@
 """An IPPO learner on simple_spread, wired from the device-side pieces.
 
-    python examples/ppo_spread.py [--worlds 1024] [--updates 50] [--epochs 4] [--minibatch M [--fused-loss]]
+    python examples/ppo_spread.py [--worlds 1024] [--updates 50] [--epochs 4] [--minibatch M [--fused-loss [--fused-nets]]]
 
 The closed loop (PolicyLoop) plays one 25-step episode in every world and records, beside the rows played and their log
 probabilities, the observation every step was decided on and each agent's own critic along it (run(25, values=V): one more launch
@@ -11,7 +11,9 @@ the clipped surrogate, the value loss and the optimiser are plain torch autograd
 statistics once per rollout, then ONE launch per minibatch that draws its rows from a keyed permutation and gathers every agent's
 observation, move, log probability, normalised advantage and return).  With --fused-loss the clipped surrogate, the value loss and
 their gradients with respect to the logits and the values are the device's loss head instead (PpoLoss: two launches per minibatch
-for all agents; the networks' forward and backward passes stay in torch autograd).  One JSON line per update.  A readable wiring,
+for all agents; the networks' forward and backward passes stay in torch autograd), and with --fused-nets those passes leave torch
+too (Trainable: the actors' and the critics' forward are one launch each, their backward two launches each -- the hidden
+activations recomputed, every weight's and bias's gradient written; the optimiser stays torch's).  One JSON line per update.  A readable wiring,
 not a benchmark.
 """
 import argparse
@@ -24,7 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from multiagent_particle_envs_amd import Actors, Minibatches, PolicyLoop, PpoLoss, Values, gae, make_env  # noqa: E402
+from multiagent_particle_envs_amd import Actors, Minibatches, PolicyLoop, PpoLoss, Trainable, Values, gae, make_env  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--worlds", type=int, default=1024)
@@ -35,7 +37,10 @@ ap.add_argument("--lam", type=float, default=0.95)
 ap.add_argument("--clip", type=float, default=0.2)
 ap.add_argument("--minibatch", type=int, default=0, help="rows per shuffled minibatch; 0: one full-batch step per epoch")
 ap.add_argument("--fused-loss", action="store_true", help="the loss head on the device (PpoLoss); needs --minibatch")
+ap.add_argument("--fused-nets", action="store_true", help="the networks' forward and backward on the device (Trainable); needs --fused-loss")
 args = ap.parse_args()
+if args.fused_nets and not args.fused_loss:
+    ap.error("--fused-nets needs --fused-loss (the backward kernel starts from the loss head's dL/dlogits and dL/dvalues)")
 if args.fused_loss and not args.minibatch:
     ap.error("--fused-loss needs --minibatch M (the loss head reads a minibatch's own tensors)")
 EPISODE = 25
@@ -56,6 +61,8 @@ V = Values(env, vf)
 loop = PolicyLoop(env, behaviour, episode_len=EPISODE)
 opt = torch.optim.Adam([p for m in pi + vf for p in m.parameters()], lr=3e-4)
 fused = PpoLoss(env, clip=args.clip, vf_coef=0.5) if args.fused_loss else None
+if args.fused_nets:      # the same modules behind autograd Functions: logits [M, 5] and values [M] per agent, one launch per set
+    pi_rows, v_rows = Trainable(Actors(env, pi, mode="sample", logits=True)), Trainable(V)
 
 
 def losses(i, obs, act, old_logp, adv, ret):
@@ -73,7 +80,10 @@ for update in range(args.updates):
         if mbs is not None:
             for batch in mbs.epoch(epoch):                # one launch each: rows of a keyed shuffle, adv already normalised
                 if fused is not None:                     # every agent's loss and dL/dlogits, dL/dvalues: two launches
-                    loss = fused([pi[i](batch.obs_n[i]) for i in range(A)], [vf[i](batch.obs_n[i]) for i in range(A)], batch)
+                    if args.fused_nets:
+                        loss = fused(pi_rows(batch.obs_n), v_rows(batch.obs_n), batch)
+                    else:
+                        loss = fused([pi[i](batch.obs_n[i]) for i in range(A)], [vf[i](batch.obs_n[i]) for i in range(A)], batch)
                     opt.zero_grad()
                     loss.backward()
                     opt.step()

@@ -580,6 +580,46 @@ int mpe_ppo_loss(const MpePpoLoss *cfg, const float *const *logits_ptrs, const f
                  const float *utter, const float *logp_old, const float *adv, const float *ret, const float *val_old,
                  float *const *dlogits_ptrs, float *dvalues, float *rows, double *work, float *stats, float *loss, void *stream);
 
+/* ---- MLP weight gradients: forward recompute, back-propagation and dW in TWO launches (csrc/mpe_mlp_grad.hip) ---------------------
+ * What stands between mpe_ppo_loss (or any dL/doutput) and the optimiser: the gradients of every weight and bias of the set's
+ * modules, for all agents at once.  set: any MpeActorSet (every mode, MPE_POLICY_VALUE included; heads, dim_c's meaning and seed are
+ * not read beyond the set's own validity).  in_ptrs[i]: agent i's contiguous [M][D_i] input rows (a HOST array of A device
+ * pointers; the same pointer A times is allowed).  dout_ptrs[i]: agent i's contiguous [M][n_out_i] rows of dL/doutput, n_out_i =
+ * width[i][n_layers[i]] -- mpe_ppo_loss's dlogits block, or, for a one-output net, a row of its dvalues.  grad: float32, the layout
+ * and the offsets of set->weights: per layer dW as [in][out'] followed by db[out'].
+ * THE MLP GRADIENT RULE.  Agent i has layers 0..L-1, W_l packed as [in_l][out_l'], activation phi between them.
+ *   h_(-1) = in;  h_l = phi(W_l^T h_(l-1) + b_l) for l < L-1 is RECOMPUTED from in with mpe_actor_act's arithmetic: the accumulator
+ *   starts at the bias and takes the inputs in ascending order, two per v_mfma_f32_32x32x2_f32 step.  Tanh is the accurate tanhf
+ *   here, NOT the forward's 1 - 2 / (exp2(x * 2 log2 e) + 1): 1 - h * h of a saturated unit multiplies that formula's absolute error
+ *   a hundredfold.  Nothing is saved by a forward, and no hidden activation goes to memory.
+ *   delta_(L-1) = dout;  delta_(l-1) = (delta_l . W_l^T) * phi'(h_(l-1)), the sum over layer l's outputs ascending, accumulator from 0;
+ *   Tanh: phi' = 1 - h * h (product rounded, then the difference);  ReLU: a select, delta_(l-1) = h > 0 ? (delta_l . W_l^T) : 0, on
+ *   the activation's OUTPUT (a unit at exactly 0 gets 0: torch's rule)
+ *   dW_l[k][j] = sum over rows of h_(l-1)[row][k] * delta_l[row][j];   db_l[j] = sum over rows of delta_l[row][j]
+ * Fixed order.  The rows are cut into groups of 64 and the groups into chunks of span = max(1, ceil(ceil(M / 64) / 128))
+ * consecutive groups: a function of M alone.  Within a group an entry of dW is four float32 chains -- MFMA step t (rows 2 t and
+ * 2 t + 1 of the group) goes to chain t mod 4, each chain from 0 in ascending order -- folded as (c0 + c1) + (c2 + c3); the groups'
+ * values are added to the chunk's float32 sum in ascending order.  db adds the chunk's rows in float64, ascending, and leaves as a float32 pair (hi = the sum rounded, lo = the
+ * remainder rounded: a bias is a sum of signed terms that may cancel to far less than a chunk's share).  Each
+ * (agent, chunk) partial goes to `work`; the second launch adds, per entry, the partials (a bias: every hi, then every lo) in float64 -- agents sharing the module
+ * (equal offset[i]) in ascending order, each agent's chunks in ascending order -- and rounds once.  The result is a function of the
+ * inputs and M only, bit for bit on every run.  No atomics, no host synchronisation.
+ * Padding.  Every padding entry of a module's block of grad is exactly +0.0f: columns at or beyond out_l, rows at or beyond in_l of
+ * a later layer, the unused columns of a 16-wide last layer.  Floats of grad outside every module's block are not written.
+ * work: mpe_mlp_grad_work(set, M) floats of device memory, every one written before it is read.  mpe_mlp_grad_work is host only
+ * (set->weights is not read) and returns the count, or a negative code.
+ * Refused by name before any launch, in this order: set NULL; n_agents outside 1..MPE_ACTOR_MAX_AGENTS; a mode that is none of
+ * GREEDY / SAMPLE / SOFTMAX / VALUE; per agent: layers outside 1..3, an unknown activation, an input width outside
+ * 1..MPE_ACTOR_MAX_INPUT, a hidden width outside 1..MPE_POLICY_MAX_WIDTH, an output width outside 1..MPE_ACTOR_MAX_OUT, an offset
+ * that is negative, no multiple of 16 or too large for the blocks to stay below 2^31; two agents at one offset with different
+ * shapes (layers, widths, activation); two agents' blocks overlapping at different offsets; M < 0; M >= 2^31.  mpe_mlp_grad then:
+ * set->weights NULL or not 16-byte aligned; in_ptrs, dout_ptrs, grad or work NULL; a NULL in_ptrs[i] or dout_ptrs[i]; a pointer that
+ * is not 4-byte aligned.  M == 0 writes an all-zero grad (one launch) and succeeds.
+ * Out of scope: dL/din (MADDPG's actor loss through the critic needs it), optimiser steps, bf16.                                */
+int64_t mpe_mlp_grad_work(const MpeActorSet *set, int64_t M);
+int mpe_mlp_grad(const MpeActorSet *set, const float *const *in_ptrs, const float *const *dout_ptrs, int64_t M, float *grad,
+                 float *work, void *stream);
+
 /* ---- the replay buffer: the last S steps of all B worlds in device memory (csrc/mpe_replay.hip) ------------------------------
  * What an off-policy learner keeps beside the loop above: a ring of transitions (obs, action, reward, done, next obs) of every
  * agent, filled by ONE launch per step (mpe_replay_push) and sampled by ONE launch per minibatch (mpe_replay_sample), the same

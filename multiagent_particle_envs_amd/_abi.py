@@ -243,6 +243,9 @@ EXPORTS = {
     "mpe_ppo_loss_work": (C.c_int64, [C.c_int32, C.c_int64]),
     "mpe_ppo_loss": (C.c_int, [C.POINTER(MpePpoLoss), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int64] + [C.c_void_p] * 6 +
                      [C.POINTER(C.c_void_p)] + [C.c_void_p] * 6),
+    "mpe_mlp_grad_work": (C.c_int64, [C.POINTER(MpeActorSet), C.c_int64]),
+    "mpe_mlp_grad": (C.c_int, [C.POINTER(MpeActorSet), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int64, C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
     "mpe_sizeof_replay": (C.c_size_t, []),
     "mpe_replay_supported": (C.c_int, [C.POINTER(MpeReplay)]),
     "mpe_replay_push": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,

@@ -1572,6 +1572,92 @@ int mpe_ppo_loss(const MpePpoLoss *cfg, const float *const *logits_ptrs, const f
   return hip_result(mpe::launch_ppo_loss(a, static_cast<hipStream_t>(stream)), what);
 }
 
+// ---- the MLP weight gradients (mpe_mlp_grad.hip) --------------------------------------------------------------------------------
+// the checks mpe_mlp_grad and mpe_mlp_grad_work share, in the header's order; fills everything of the launch's arguments but the
+// pointers
+static int check_mlp_grad(const MpeActorSet *s, int64_t M, const char *what, mpe::MlpGradArgs &a) {
+  if (!s) return fail(MPE_EINVAL, "%s: set is NULL", what);
+  if (s->n_agents < 1 || s->n_agents > MPE_ACTOR_MAX_AGENTS)
+    return fail(MPE_EINVAL, "%s: n_agents = %d (1..MPE_ACTOR_MAX_AGENTS = %d)", what, s->n_agents, MPE_ACTOR_MAX_AGENTS);
+  if (s->mode != MPE_POLICY_GREEDY && s->mode != MPE_POLICY_SAMPLE && s->mode != MPE_POLICY_SOFTMAX && s->mode != MPE_POLICY_VALUE)
+    return fail(MPE_EINVAL, "%s: mode %d (MPE_POLICY_GREEDY / SAMPLE / SOFTMAX / VALUE)", what, s->mode);
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  const int A = s->n_agents;
+  for (int i = 0; i < A; ++i) {
+    const int nl = s->n_layers[i];
+    if (nl < 1 || nl > MPE_POLICY_MAX_LAYERS)
+      return fail(MPE_EINVAL, "%s: agent %d has %d Linear layers (1..%d)", what, i, nl, MPE_POLICY_MAX_LAYERS);
+    if (s->activation[i] != MPE_POLICY_RELU && s->activation[i] != MPE_POLICY_TANH)
+      return fail(MPE_EINVAL, "%s: agent %d: activation %d (MPE_POLICY_RELU / TANH)", what, i, s->activation[i]);
+    if (s->width[i][0] < 1 || s->width[i][0] > MPE_ACTOR_MAX_INPUT)
+      return fail(MPE_EINVAL, "%s: agent %d: input width %d (1..MPE_ACTOR_MAX_INPUT = %d)", what, i, s->width[i][0], MPE_ACTOR_MAX_INPUT);
+    for (int l = 1; l < nl; ++l)
+      if (s->width[i][l] < 1 || s->width[i][l] > MPE_POLICY_MAX_WIDTH)
+        return fail(MPE_EINVAL, "%s: agent %d: hidden width %d (1..MPE_POLICY_MAX_WIDTH = %d)", what, i, s->width[i][l], MPE_POLICY_MAX_WIDTH);
+    if (s->width[i][nl] < 1 || s->width[i][nl] > MPE_ACTOR_MAX_OUT)
+      return fail(MPE_EINVAL, "%s: agent %d: the last layer gives %d outputs (1..MPE_ACTOR_MAX_OUT = %d)", what, i, s->width[i][nl],
+                  MPE_ACTOR_MAX_OUT);
+    a.size[i] = mpe::mg_size(nl, s->width[i][0]);
+    if (s->offset[i] < 0 || s->offset[i] % 16 || s->offset[i] > 0x7fffffff - a.size[i])
+      return fail(MPE_EINVAL, "%s: agent %d: offset %lld (a non-negative multiple of 16 floats, the block's end below 2^31)", what, i,
+                  (long long)s->offset[i]);
+    a.off[i] = (int32_t)s->offset[i];
+    a.nl[i] = (uint8_t)nl;
+    a.act[i] = (uint8_t)s->activation[i];
+    for (int l = 0; l <= nl; ++l) a.width[i][l] = (int16_t)s->width[i][l];
+  }
+  for (int i = 0; i < A; ++i) {
+    a.owner[i] = 1;
+    for (int b = 0; b < i; ++b) {
+      if (a.off[b] == a.off[i]) {
+        if (a.nl[b] != a.nl[i] || a.act[b] != a.act[i] || std::memcmp(a.width[b], a.width[i], sizeof(a.width[i])))
+          return fail(MPE_EINVAL, "%s: agents %d and %d share offset %d with different shapes (layers, widths or activation)", what, b, i,
+                      a.off[i]);
+        a.owner[i] = 0;
+      } else if (a.off[b] < a.off[i] + a.size[i] && a.off[i] < a.off[b] + a.size[b]) {
+        return fail(MPE_EINVAL, "%s: the blocks of agents %d and %d overlap (offsets %d and %d: a module is shared whole, at equal offsets, or not at all)", what,
+                    b, i, a.off[b], a.off[i]);
+      }
+    }
+  }
+  if (M < 0) return fail(MPE_EINVAL, "%s: M = %lld", what, (long long)M);
+  if (M > 0x7fffffffll) return fail(MPE_EINVAL, "%s: M = %lld (need M < 2^31)", what, (long long)M);
+  a.M = (uint64_t)M;
+  a.A = A;
+  const int64_t chunks = (int64_t)mpe::mg_chunks(a.M);
+  int64_t at = 0;
+  for (int i = 0; i < A; ++i) {
+    a.woff[i] = at;
+    at += chunks * mpe::mg_psize(a.size[i]);
+  }
+  return 0;
+}
+int64_t mpe_mlp_grad_work(const MpeActorSet *s, int64_t M) {
+  mpe::MlpGradArgs a;
+  if (int rc = check_mlp_grad(s, M, "mpe_mlp_grad_work", a)) return rc;
+  return a.woff[a.A - 1] + (int64_t)mpe::mg_chunks(a.M) * mpe::mg_psize(a.size[a.A - 1]);
+}
+int mpe_mlp_grad(const MpeActorSet *s, const float *const *in_ptrs, const float *const *dout_ptrs, int64_t M, float *grad, float *work,
+                 void *stream) {
+  const char *what = "mpe_mlp_grad";
+  mpe::MlpGradArgs a;
+  if (int rc = check_mlp_grad(s, M, what, a)) return rc;
+  if (!s->weights || ((uintptr_t)s->weights & 15)) return fail(MPE_EINVAL, "%s: set->weights is NULL or not 16-byte aligned", what);
+  const struct { const void *p; const char *name; } need[] = {{in_ptrs, "in_ptrs"}, {dout_ptrs, "dout_ptrs"}, {grad, "grad"}, {work, "work"}};
+  for (const auto &f : need)
+    if (!f.p) return fail(MPE_EINVAL, "%s: %s is NULL", what, f.name);
+  uintptr_t f4 = (uintptr_t)grad | (uintptr_t)work;
+  for (int i = 0; i < a.A; ++i) {
+    if (!in_ptrs[i]) return fail(MPE_EINVAL, "%s: in_ptrs[%d] is NULL", what, i);
+    if (!dout_ptrs[i]) return fail(MPE_EINVAL, "%s: dout_ptrs[%d] is NULL", what, i);
+    f4 |= (uintptr_t)in_ptrs[i] | (uintptr_t)dout_ptrs[i];
+    a.in[i] = in_ptrs[i], a.dout[i] = dout_ptrs[i];
+  }
+  if (f4 & 3) return fail(MPE_EINVAL, "%s: every pointer must be 4-byte aligned", what);
+  a.w = s->weights, a.grad = grad, a.work = work;
+  return hip_result(mpe::launch_mlp_grad(a, static_cast<hipStream_t>(stream)), what);
+}
+
 // ---- the replay buffer (mpe_replay.hip) ---------------------------------------------------------------------------------------
 size_t mpe_sizeof_replay(void) { return sizeof(MpeReplay); }
 static int check_replay(const MpeReplay *r, const char *what, bool pointers) {

@@ -5,6 +5,7 @@
 #include "mpe_gather.h"
 #include "mpe_onpolicy.h"
 #include "mpe_ppo_loss.h"
+#include "mpe_mlp_grad.h"
 
 namespace mpe {
 
@@ -157,6 +158,11 @@ int launch_onpolicy_batch(const OnpArgs &a, hipStream_t stream);
 // the PPO loss head (mpe_ppo_loss.hip; PpoArgs, the index arithmetic and the row's arithmetic: mpe_ppo_loss.h), checked by the caller
 static_assert(kPpoMaxAgents == MPE_ACTOR_MAX_AGENTS && kPpoMaxOut == MPE_ACTOR_MAX_OUT && kPpoMove == MPE_ACTION_DIM, "mpe_ppo_loss.h restates them");
 int launch_ppo_loss(const PpoArgs &a, hipStream_t stream);                  // two launches: the rows and chunk sums, then the ordered final pass
+
+// the MLP weight gradients (mpe_mlp_grad.hip; MlpGradArgs and every index: mpe_mlp_grad.h), checked by the caller
+static_assert(kMgMaxAgents == MPE_ACTOR_MAX_AGENTS && kMgHW == MPE_POLICY_MAX_WIDTH && kMgLW == MPE_ACTOR_MAX_OUT &&
+              kMgMaxIn == MPE_ACTOR_MAX_INPUT && MPE_POLICY_MAX_LAYERS == 3, "mpe_mlp_grad.h restates them");
+int launch_mlp_grad(const MlpGradArgs &a, hipStream_t stream);              // two launches: the chunks' partials, then the ordered final pass
 
 // the replay buffer (mpe_replay.hip): both launches' arguments, checked and filled by the caller (mpe_replay_push / _sample)
 constexpr int kReplayMaxSegs = 2 * MPE_REPLAY_MAX_AGENTS + 4;     // obs and next obs per agent, act, utter, rew, done
