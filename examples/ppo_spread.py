@@ -1,6 +1,6 @@
 """An IPPO learner on simple_spread, wired from the device-side pieces.
 
-    python examples/ppo_spread.py [--worlds 1024] [--updates 50] [--epochs 4] [--minibatch M [--fused-loss [--fused-nets]]]
+    python examples/ppo_spread.py [--worlds 1024] [--updates 50] [--epochs 4] [--minibatch M [--fused-loss [--fused-nets [--device-adam]]]]
 
 The closed loop (PolicyLoop) plays one 25-step episode in every world and records, beside the rows played and their log
 probabilities, the observation every step was decided on and each agent's own critic along it (run(25, values=V): one more launch
@@ -13,7 +13,9 @@ observation, move, log probability, normalised advantage and return).  With --fu
 their gradients with respect to the logits and the values are the device's loss head instead (PpoLoss: two launches per minibatch
 for all agents; the networks' forward and backward passes stay in torch autograd), and with --fused-nets those passes leave torch
 too (Trainable: the actors' and the critics' forward are one launch each, their backward two launches each -- the hidden
-activations recomputed, every weight's and bias's gradient written; the optimiser stays torch's).  One JSON line per update.  A readable wiring,
+activations recomputed, every weight's and bias's gradient written; the optimiser stays torch's).  With --device-adam the optimiser
+leaves torch as well (DeviceAdam: the packed weights are the master copy, updated in place by two launches per minibatch for both
+sets; every forward reads them, nothing is packed again).  One JSON line per update.  A readable wiring,
 not a benchmark.
 """
 import argparse
@@ -26,7 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from multiagent_particle_envs_amd import Actors, Minibatches, PolicyLoop, PpoLoss, Trainable, Values, gae, make_env  # noqa: E402
+from multiagent_particle_envs_amd import Actors, DeviceAdam, Minibatches, PolicyLoop, PpoLoss, Trainable, Values, gae, make_env  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--worlds", type=int, default=1024)
@@ -38,7 +40,10 @@ ap.add_argument("--clip", type=float, default=0.2)
 ap.add_argument("--minibatch", type=int, default=0, help="rows per shuffled minibatch; 0: one full-batch step per epoch")
 ap.add_argument("--fused-loss", action="store_true", help="the loss head on the device (PpoLoss); needs --minibatch")
 ap.add_argument("--fused-nets", action="store_true", help="the networks' forward and backward on the device (Trainable); needs --fused-loss")
+ap.add_argument("--device-adam", action="store_true", help="the optimiser step on the device (DeviceAdam); needs --fused-nets")
 args = ap.parse_args()
+if args.device_adam and not args.fused_nets:
+    ap.error("--device-adam needs --fused-nets (the step reads the packed gradients of the backward kernel)")
 if args.fused_nets and not args.fused_loss:
     ap.error("--fused-nets needs --fused-loss (the backward kernel starts from the loss head's dL/dlogits and dL/dvalues)")
 if args.fused_loss and not args.minibatch:
@@ -63,6 +68,9 @@ opt = torch.optim.Adam([p for m in pi + vf for p in m.parameters()], lr=3e-4)
 fused = PpoLoss(env, clip=args.clip, vf_coef=0.5) if args.fused_loss else None
 if args.fused_nets:      # the same modules behind autograd Functions: logits [M, 5] and values [M] per agent, one launch per set
     pi_rows, v_rows = Trainable(Actors(env, pi, mode="sample", logits=True)), Trainable(V)
+if args.device_adam:     # the packed weights become the master copy; the sampling set reads the same live buffer
+    dev_opt = DeviceAdam([pi_rows, v_rows], lr=3e-4)
+    dev_opt.share(pi_rows, behaviour)
 
 
 def losses(i, obs, act, old_logp, adv, ret):
@@ -84,6 +92,12 @@ for update in range(args.updates):
                         loss = fused(pi_rows(batch.obs_n), v_rows(batch.obs_n), batch)
                     else:
                         loss = fused([pi[i](batch.obs_n[i]) for i in range(A)], [vf[i](batch.obs_n[i]) for i in range(A)], batch)
+                    if args.device_adam:
+                        opt.zero_grad()               # host only (.grad = None): autograd's views of the packed gradient are set, not
+                        loss.backward()               # accumulated; nothing reads them -- the step takes the packed gradient itself
+                        dev_opt.step()
+                        policy_loss, value_loss = -loss.stats[:, 0].sum(), loss.stats[:, 1].sum()
+                        continue
                     opt.zero_grad()
                     loss.backward()
                     opt.step()

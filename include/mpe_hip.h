@@ -615,10 +615,79 @@ int mpe_ppo_loss(const MpePpoLoss *cfg, const float *const *logits_ptrs, const f
  * shapes (layers, widths, activation); two agents' blocks overlapping at different offsets; M < 0; M >= 2^31.  mpe_mlp_grad then:
  * set->weights NULL or not 16-byte aligned; in_ptrs, dout_ptrs, grad or work NULL; a NULL in_ptrs[i] or dout_ptrs[i]; a pointer that
  * is not 4-byte aligned.  M == 0 writes an all-zero grad (one launch) and succeeds.
- * Out of scope: dL/din (MADDPG's actor loss through the critic needs it), optimiser steps, bf16.                                */
+ * Out of scope: dL/din (MADDPG's actor loss through the critic needs it), bf16.  The optimiser step that consumes grad in this
+ * layout, in place on set->weights, is mpe_adam_step below.                                                                     */
 int64_t mpe_mlp_grad_work(const MpeActorSet *set, int64_t M);
 int mpe_mlp_grad(const MpeActorSet *set, const float *const *in_ptrs, const float *const *dout_ptrs, int64_t M, float *grad,
                  float *work, void *stream);
+
+/* ---- the optimiser step: Adam / AdamW with global-norm clipping on the packed buffers, in place, in TWO launches (csrc/mpe_adam.hip) --
+ * What stands between mpe_mlp_grad and the next forward: up to MPE_ADAM_MAX_SETS packed buffers -- each an MpeActorSet's `weights`,
+ * mpe_mlp_grad's `grad` in the same layout, and the moments m and v in that layout too -- are updated together; the forward kernels
+ * read the new weights at their next launch, nothing is repacked.  The step count and the bias-correction products live in DEVICE
+ * memory (state), so {batch, forward, loss, backward, step} is one capturable straight line.
+ * Per set: n floats, a multiple of 16, every pointer 16-byte aligned; N = the sum of the n, 16 <= N < 2^31; the four buffers of a
+ * set and the buffers of different sets do not overlap (one set's grad may not be another's either).
+ * THE ADAM RULE.
+ * Tiling.  span is the smallest integer >= 1 with sum_s ceil(n_s / (MPE_ADAM_TILE * span)) <= MPE_ADAM_MAX_PARTIALS: a function of
+ *   the sizes alone.  Set s is cut into tiles of MPE_ADAM_TILE * span floats; the tiles are numbered set by set, ascending: P in all.
+ * Norm (launch 1, one workgroup of 256 lanes per tile).  In tile p, lane l (0..255) starts a float64 accumulator at 0; for
+ *   j = 0..span-1 it takes the four floats at tile offset (256 j + l) * 4 in ascending order and adds (double) g * (double) g; floats
+ *   at or beyond n_s add nothing.  The 256 lane sums are folded by the fixed tree
+ *     for stride = 128, 64, .., 1:  x[l] += x[l + stride]  (l < stride)
+ *   and the result is work[p].
+ * State commit (launch 1).  Lane 0 of workgroup 0 also copies state[3..5] (pending) to state[0..2] (committed); nothing else in
+ *   launch 1 reads the state.
+ * Scalars (launch 2, the same grid; EVERY workgroup).  work[0..P) is loaded into 256 lanes, 0.0 beyond P, and folded by the same tree
+ *   into S; norm = sqrt(S) in float64.  If norm is not finite the step is SKIPPED: no float of any weights, m or v changes, pending :=
+ *   committed, state[6] = norm, state[7] = 0, state[8] += 1.  Otherwise
+ *     c = max_grad_norm > 0 ? min(1, max_grad_norm / (norm + 1e-6)) : 1                 (torch's clip_grad_norm_)
+ *     (t, p1, p2) = committed;  t' = t + 1;  p1' = p1 * beta1;  p2' = p2 * beta2        (running float64 products, no pow)
+ *   and every scalar is computed in float64 and rounded to float32 once: cf = (float) c, a1 = (float) (1 - beta1), a2 = (float) (1 -
+ *   beta2), b2 = (float) beta2, step = (float) (lr / (1 - p1')), s2 = (float) sqrt(1 - p2'), e = (float) eps, dec = (float) (1 - lr *
+ *   weight_decay); where lr_ptr is given, lr is (double) *lr_ptr.  Lane 0 of workgroup 0 writes pending := (t', p1', p2'), state[6] =
+ *   norm, state[7] = c.  The readers of the committed triple never race with the write of the pending one: that is why the state is
+ *   a pair.  state[9..15] stay 0; a fresh state is (0, 1, 1, 0, 1, 1, 0, ..).
+ * Per element (launch 2).  Every operation is float32, rounded on its own, no fused multiply-add; sqrt and / correctly rounded:
+ *     g = grad * cf
+ *     w = weight_decay != 0 ? w * dec : w
+ *     m = m + (g - m) * a1
+ *     v = v * b2 + (g * g) * a2
+ *     w = w - step * (m / (sqrt(v) / s2 + e))
+ *   (the operation order of torch's single-tensor Adam and AdamW).  All accesses to w, m, v and grad are 16 bytes wide.
+ * Padding.  A padding entry has w = 0, g = +0.0f, m = v = 0 and stays exactly +0.0f in w, m and v: eps > 0 is required for it.
+ * Bit equality.  Only +, -, x and correctly rounded / and sqrt, no denormal flush: the results are a function of the inputs alone,
+ * bit for bit on every run and bit-equal to a NumPy restatement (tests/_adam_ref.py).  No atomics, no host synchronisation.
+ * state: MPE_ADAM_STATE_DOUBLES doubles of device memory the caller keeps between steps; work: mpe_adam_work(cfg) doubles (= P),
+ * every one written before it is read.  mpe_adam_work is host only (no pointer but cfg is read beyond the checks) and returns the
+ * count, or a negative code.
+ * Refused by name before any launch, in this order: cfg NULL; n_sets outside 1..MPE_ADAM_MAX_SETS; per set, in set order: weights,
+ * grad, m or v NULL; one of them not 16-byte aligned; n < 16 or no multiple of 16; two buffers (of one set or of two) that overlap;
+ * N >= 2^31; lr (when lr_ptr is NULL), beta1, beta2, eps, weight_decay or max_grad_norm not finite; a beta outside [0, 1); eps <= 0;
+ * lr, weight_decay or max_grad_norm < 0; lr_ptr not 4-byte aligned.  mpe_adam_step then: state or work NULL; state or work not
+ * 8-byte aligned.                                                                                                              */
+#define MPE_ADAM_MAX_SETS 8
+#define MPE_ADAM_TILE 1024            /* floats: 256 lanes x one 16-byte access */
+#define MPE_ADAM_MAX_PARTIALS 256
+#define MPE_ADAM_STATE_DOUBLES 16
+typedef struct MpeAdamSet {
+  float *weights;                                 /* updated in place                                                       */
+  const float *grad;
+  float *m, *v;                                   /* the moments, updated in place                                          */
+  int64_t n;                                      /* floats, a multiple of 16                                               */
+} MpeAdamSet;
+typedef struct MpeAdam {
+  double lr, beta1, beta2, eps;
+  double weight_decay;                            /* decoupled (AdamW); 0: Adam                                             */
+  double max_grad_norm;                           /* 0: no clipping                                                         */
+  const float *lr_ptr;                            /* optional DEVICE float read by the launch instead of lr (schedules under a
+                                                     captured graph)                                                        */
+  int32_t n_sets, reserved_;
+  MpeAdamSet set[MPE_ADAM_MAX_SETS];
+} MpeAdam;
+size_t mpe_sizeof_adam(void);
+int64_t mpe_adam_work(const MpeAdam *cfg);
+int mpe_adam_step(const MpeAdam *cfg, double *state, double *work, void *stream);
 
 /* ---- the replay buffer: the last S steps of all B worlds in device memory (csrc/mpe_replay.hip) ------------------------------
  * What an off-policy learner keeps beside the loop above: a ring of transitions (obs, action, reward, done, next obs) of every

@@ -99,6 +99,19 @@ class MpeOnPolicyTraj(C.Structure):    # include/mpe_hip.h: a recorded trajector
                 ("ret", C.c_void_p), ("val", C.c_void_p)]
 
 
+MPE_ADAM_MAX_SETS, MPE_ADAM_TILE, MPE_ADAM_MAX_PARTIALS, MPE_ADAM_STATE_DOUBLES = 8, 1024, 256, 16
+
+
+class MpeAdamSet(C.Structure):         # include/mpe_hip.h: one packed buffer of mpe_adam_step and its gradient and moments
+    _fields_ = [("weights", C.c_void_p), ("grad", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
+
+
+class MpeAdam(C.Structure):            # include/mpe_hip.h: the scalars and the sets of THE ADAM RULE (mpe_adam_step)
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("max_grad_norm", C.c_double), ("lr_ptr", C.c_void_p), ("n_sets", C.c_int32), ("reserved_", C.c_int32),
+                ("set", MpeAdamSet * MPE_ADAM_MAX_SETS)]
+
+
 MPE_REPLAY_MAX_AGENTS, MPE_REPLAY_MAX_WIDTH = 16, 4096
 MPE_STREAM_REPLAY = 0x5245504C
 
@@ -246,6 +259,9 @@ EXPORTS = {
     "mpe_mlp_grad_work": (C.c_int64, [C.POINTER(MpeActorSet), C.c_int64]),
     "mpe_mlp_grad": (C.c_int, [C.POINTER(MpeActorSet), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int64, C.c_void_p, C.c_void_p,
                                C.c_void_p]),
+    "mpe_sizeof_adam": (C.c_size_t, []),
+    "mpe_adam_work": (C.c_int64, [C.POINTER(MpeAdam)]),
+    "mpe_adam_step": (C.c_int, [C.POINTER(MpeAdam), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mpe_sizeof_replay": (C.c_size_t, []),
     "mpe_replay_supported": (C.c_int, [C.POINTER(MpeReplay)]),
     "mpe_replay_push": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
@@ -300,6 +316,7 @@ def lib():
             handle.mpe_sizeof_gae() != C.sizeof(MpeGae) or \
             handle.mpe_sizeof_onpolicy_traj() != C.sizeof(MpeOnPolicyTraj) or \
             handle.mpe_sizeof_ppo_loss() != C.sizeof(MpePpoLoss) or \
+            handle.mpe_sizeof_adam() != C.sizeof(MpeAdam) or \
             handle.mpe_sizeof_replay_nstep() != C.sizeof(MpeReplayNStep):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")
     _lib = handle

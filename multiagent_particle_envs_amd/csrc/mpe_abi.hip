@@ -1658,6 +1658,79 @@ int mpe_mlp_grad(const MpeActorSet *s, const float *const *in_ptrs, const float 
   return hip_result(mpe::launch_mlp_grad(a, static_cast<hipStream_t>(stream)), what);
 }
 
+// ---- the optimiser step (mpe_adam.hip) ------------------------------------------------------------------------------------------
+size_t mpe_sizeof_adam(void) { return sizeof(MpeAdam); }
+// the checks mpe_adam_step and mpe_adam_work share, in the header's order; fills everything of the launch's arguments but state and work
+static int check_adam(const MpeAdam *c, const char *what, mpe::AdamArgs &a) {
+  if (!c) return fail(MPE_EINVAL, "%s: cfg is NULL", what);
+  if (c->n_sets < 1 || c->n_sets > MPE_ADAM_MAX_SETS)
+    return fail(MPE_EINVAL, "%s: n_sets = %d (1..MPE_ADAM_MAX_SETS = %d)", what, c->n_sets, MPE_ADAM_MAX_SETS);
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  const int S = c->n_sets;
+  static const char *const names[4] = {"weights", "grad", "m", "v"};
+  for (int s = 0; s < S; ++s) {
+    const MpeAdamSet &q = c->set[s];
+    const void *ptr[4] = {q.weights, q.grad, q.m, q.v};
+    for (int k = 0; k < 4; ++k)
+      if (!ptr[k]) return fail(MPE_EINVAL, "%s: set[%d].%s is NULL", what, s, names[k]);
+    for (int k = 0; k < 4; ++k)
+      if ((uintptr_t)ptr[k] & 15) return fail(MPE_EINVAL, "%s: set[%d].%s is not 16-byte aligned", what, s, names[k]);
+    if (q.n < 16 || q.n % 16) return fail(MPE_EINVAL, "%s: set[%d].n = %lld floats (a multiple of 16, at least 16)", what, s, (long long)q.n);
+  }
+  for (int s = 0; s < S; ++s)
+    for (int k = 0; k < 4; ++k)
+      for (int s2 = 0; s2 <= s; ++s2)
+        for (int k2 = 0; k2 < (s2 == s ? k : 4); ++k2) {
+          const void *pa[4] = {c->set[s2].weights, c->set[s2].grad, c->set[s2].m, c->set[s2].v};
+          const void *pb[4] = {c->set[s].weights, c->set[s].grad, c->set[s].m, c->set[s].v};
+          const unsigned __int128 a0 = (uintptr_t)pa[k2], a1 = a0 + (unsigned __int128)c->set[s2].n * 4;
+          const unsigned __int128 b0 = (uintptr_t)pb[k], b1 = b0 + (unsigned __int128)c->set[s].n * 4;
+          if (a0 < b1 && b0 < a1)
+            return fail(MPE_EINVAL, "%s: set[%d].%s and set[%d].%s overlap", what, s2, names[k2], s, names[k]);
+        }
+  int64_t N = 0;
+  for (int s = 0; s < S; ++s) {
+    if (c->set[s].n > 0x7fffffffll - N) return fail(MPE_EINVAL, "%s: the sets hold 2^31 floats or more (need N < 2^31)", what);
+    N += c->set[s].n;
+  }
+  const struct { double x; const char *name; } sc[] = {{c->lr, "lr"}, {c->beta1, "beta1"}, {c->beta2, "beta2"}, {c->eps, "eps"},
+                                                       {c->weight_decay, "weight_decay"}, {c->max_grad_norm, "max_grad_norm"}};
+  for (const auto &f : sc)
+    if (!std::isfinite(f.x) && !(f.name == sc[0].name && c->lr_ptr)) return fail(MPE_EINVAL, "%s: %s = %g is not finite", what, f.name, f.x);
+  if (c->beta1 < 0.0 || c->beta1 >= 1.0) return fail(MPE_EINVAL, "%s: beta1 = %g (need 0 <= beta1 < 1)", what, c->beta1);
+  if (c->beta2 < 0.0 || c->beta2 >= 1.0) return fail(MPE_EINVAL, "%s: beta2 = %g (need 0 <= beta2 < 1)", what, c->beta2);
+  if (c->eps <= 0.0) return fail(MPE_EINVAL, "%s: eps = %g (need eps > 0: a padding entry divides by it)", what, c->eps);
+  if (!c->lr_ptr && c->lr < 0.0) return fail(MPE_EINVAL, "%s: lr = %g (need >= 0)", what, c->lr);
+  if (c->weight_decay < 0.0) return fail(MPE_EINVAL, "%s: weight_decay = %g (need >= 0)", what, c->weight_decay);
+  if (c->max_grad_norm < 0.0) return fail(MPE_EINVAL, "%s: max_grad_norm = %g (need >= 0; 0: no clipping)", what, c->max_grad_norm);
+  if ((uintptr_t)c->lr_ptr & 3) return fail(MPE_EINVAL, "%s: lr_ptr is not 4-byte aligned", what);
+  for (int s = 0; s < S; ++s) {
+    a.w[s] = c->set[s].weights, a.g[s] = c->set[s].grad, a.m[s] = c->set[s].m, a.v[s] = c->set[s].v;
+    a.n[s] = (uint32_t)c->set[s].n;
+  }
+  a.n_sets = (uint32_t)S;
+  mpe::adam_tiling(a);
+  a.lr = c->lr_ptr ? 0.0 : c->lr, a.beta1 = c->beta1, a.beta2 = c->beta2, a.eps = c->eps;
+  a.weight_decay = c->weight_decay, a.max_grad_norm = c->max_grad_norm;
+  a.lr_ptr = c->lr_ptr;
+  return 0;
+}
+int64_t mpe_adam_work(const MpeAdam *cfg) {
+  mpe::AdamArgs a;
+  if (int rc = check_adam(cfg, "mpe_adam_work", a)) return rc;
+  return (int64_t)mpe::adam_tiles(a);
+}
+int mpe_adam_step(const MpeAdam *cfg, double *state, double *work, void *stream) {
+  const char *what = "mpe_adam_step";
+  mpe::AdamArgs a;
+  if (int rc = check_adam(cfg, what, a)) return rc;
+  if (!state) return fail(MPE_EINVAL, "%s: state is NULL", what);
+  if (!work) return fail(MPE_EINVAL, "%s: work is NULL", what);
+  if (((uintptr_t)state | (uintptr_t)work) & 7) return fail(MPE_EINVAL, "%s: state and work must be 8-byte aligned", what);
+  a.state = state, a.work = work;
+  return hip_result(mpe::launch_adam(a, static_cast<hipStream_t>(stream)), what);
+}
+
 // ---- the replay buffer (mpe_replay.hip) ---------------------------------------------------------------------------------------
 size_t mpe_sizeof_replay(void) { return sizeof(MpeReplay); }
 static int check_replay(const MpeReplay *r, const char *what, bool pointers) {

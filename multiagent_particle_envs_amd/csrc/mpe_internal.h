@@ -6,6 +6,7 @@
 #include "mpe_onpolicy.h"
 #include "mpe_ppo_loss.h"
 #include "mpe_mlp_grad.h"
+#include "mpe_adam.h"
 
 namespace mpe {
 
@@ -163,6 +164,11 @@ int launch_ppo_loss(const PpoArgs &a, hipStream_t stream);                  // t
 static_assert(kMgMaxAgents == MPE_ACTOR_MAX_AGENTS && kMgHW == MPE_POLICY_MAX_WIDTH && kMgLW == MPE_ACTOR_MAX_OUT &&
               kMgMaxIn == MPE_ACTOR_MAX_INPUT && MPE_POLICY_MAX_LAYERS == 3, "mpe_mlp_grad.h restates them");
 int launch_mlp_grad(const MlpGradArgs &a, hipStream_t stream);              // two launches: the chunks' partials, then the ordered final pass
+
+// the optimiser step (mpe_adam.hip; AdamArgs, the tiling and the arithmetic: mpe_adam.h), checked by the caller
+static_assert(kAdamMaxSets == MPE_ADAM_MAX_SETS && kAdamTile == MPE_ADAM_TILE && kAdamMaxPartials == MPE_ADAM_MAX_PARTIALS &&
+              kAdamStateDoubles == MPE_ADAM_STATE_DOUBLES, "mpe_adam.h restates them");
+int launch_adam(const AdamArgs &a, hipStream_t stream);                     // two launches: the norm's partials and the commit, then the update
 
 // the replay buffer (mpe_replay.hip): both launches' arguments, checked and filled by the caller (mpe_replay_push / _sample)
 constexpr int kReplayMaxSegs = 2 * MPE_REPLAY_MAX_AGENTS + 4;     // obs and next obs per agent, act, utter, rew, done

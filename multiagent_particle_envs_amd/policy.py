@@ -433,7 +433,8 @@ class PolicyLoop(object):
         step -- with nothing recorded.  -> an object whose replay() runs them and advances this loop's step count by T; the
         draw keys and episode numbers are those of the captured steps (a replay repeats them: capture a multiple of episode_len
         steps from an episode start for a periodic rollout, as RandomRollout.capture).  The weights are frozen for the capture
-        (freeze() again and re-capture after an update).  Two warm-up steps really run in front of the capture; the state and the
+        (freeze() again and re-capture after a torch update of the modules); with a DeviceAdam (optim.py) the actors already read
+        the optimiser's live buffer, the captured launches read it too, and the graph needs NO re-capture after an update.  Two warm-up steps really run in front of the capture; the state and the
         step count are put back.  replay: every captured step pushes its transition to that ReplayBuffer; the
         push reads and advances the buffer's device-side step count, so each replay() fills the next T slots (the warm-up steps'
         pushes are taken back through the buffer's _mark / _rewind hooks: the count is restored -- and a prioritized buffer's

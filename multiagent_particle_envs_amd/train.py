@@ -154,6 +154,7 @@ class _TrainFn(torch.autograd.Function):
         dev = owner.net.world.device
         dout = [torch.zeros(s, dtype=torch.float32, device=dev) if g is None else g.contiguous() for g, s in zip(grad_outputs, ctx.shapes)]
         res = mlp_grad_tensors(owner.net, ctx.in_n, dout, packed=ctx.packed)
+        owner.last_grad = res      # (what DeviceAdam.step() reads in place of the parameters' .grad)
         flat = res.packed.clone()      # out of place: the cached buffer is rewritten by the next backward of the same M
         views, _ = _module_views(owner.net, flat)
         grads = []
@@ -179,6 +180,7 @@ class Trainable(object):
             raise _abi.MpeError("Trainable: the Actors were built without logits=True (the forward hands autograd the launch's logits)")
         self.net = net
         self._generation = {}
+        self.last_grad = None      # the MlpGradResult of the last backward(); DeviceAdam.step() consumes it
         self._lins, self._params, seen = [], [], set()
         for (lins, _), m in zip(net._check(), net.modules):
             if id(m) in seen:
