@@ -15,79 +15,31 @@ import math
 import torch
 
 from . import _abi
-from .policy import Actors, env_joint_layout, pack_actor16
+from .netset import Cache, NetSet
+from .policy import Actors, env_joint_layout
 from .replay import NStepReplayBatch, ReplayBatch
-from .rollout import _actor_layers
 
 
-class Critics(object):
+class Critics(NetSet):
     """Per-agent MLP critics over the centralised joint row: `modules` is one nn.Sequential per agent, or one module every agent
     shares (the layer rules of Actors: Linear layers with ReLU / Tanh between them, at most 3, hidden widths <= 64, float32).  The
     first Linear takes joint_width inputs (ReplayBatch.joint's row: at most MPE_ACTOR_MAX_INPUT = 256 floats), the last gives 1
     output.  The weights are packed again at every call unless freeze() was called, so in-place (soft) updates are seen."""
+    who, noun = "Critics", "critics"
 
     def __init__(self, env, modules):
-        import torch.nn as nn
-        w = env.world
-        self.env, self.world = env, w
-        self.A = len(w.agents)
-        if self.A > _abi.MPE_ACTOR_MAX_AGENTS:
-            raise _abi.MpeError("Critics: %d agents (at most MPE_ACTOR_MAX_AGENTS = %d per set)" % (self.A, _abi.MPE_ACTOR_MAX_AGENTS))
-        self.off, self.joint_width, self.col_move, self.col_utter = env_joint_layout(env, "Critics")
+        NetSet.__init__(self, env, modules)
+        self._out = Cache()
+
+    def _widths(self):
+        self.off, self.joint_width, self.col_move, self.col_utter = env_joint_layout(self.env, "Critics")
         if self.joint_width > _abi.MPE_ACTOR_MAX_INPUT:
             raise _abi.MpeError("Critics: the joint row has %d floats, a critic's input is at most MPE_ACTOR_MAX_INPUT = %d wide"
                                 % (self.joint_width, _abi.MPE_ACTOR_MAX_INPUT))
-        self.shared = isinstance(modules, nn.Module)
-        self.modules = [modules] * self.A if self.shared else list(modules)
-        if len(self.modules) != self.A:
-            raise _abi.MpeError("Critics: %d critics for %d agents" % (len(self.modules), self.A))
-        self._frozen = None
-        self._out = {}
-        self._check()
+        self.in_widths, self.n_out = [self.joint_width] * self.A, [1] * self.A
 
-    def _check(self):
-        layers = []
-        for i, m in enumerate(self.modules):
-            try:
-                lins, act = _actor_layers(m, 1, "Critics")
-            except _abi.MpeError as e:
-                raise _abi.MpeError("%s [agent %d's critic: one output]" % (e, i))
-            if lins[0].in_features != self.joint_width:
-                raise _abi.MpeError("Critics: agent %d's critic takes %d inputs, the joint row has %d" % (i, lins[0].in_features, self.joint_width))
-            layers.append((lins, act))
-        return layers
-
-    def pack(self, device=None):
-        """-> (weights tensor, MpeActorSet in mode MPE_POLICY_VALUE): one packed copy per distinct module object."""
-        layers = self._check()
-        aset = _abi.MpeActorSet()
-        blobs, where, off = [], {}, 0
-        for i, m in enumerate(self.modules):
-            if id(m) not in where:
-                blob = pack_actor16(m, 1)
-                where[id(m)] = off
-                blobs.append(blob if device is None else blob.to(device))
-                off += blob.numel()
-            lins, act = layers[i]
-            aset.n_layers[i] = len(lins)
-            aset.width[i][0] = lins[0].in_features
-            for k, lin in enumerate(lins):
-                aset.width[i][k + 1] = lin.out_features
-            aset.activation[i] = _abi.MPE_POLICY_TANH if act == "tanh" else _abi.MPE_POLICY_RELU
-            aset.offset[i] = where[id(m)]
-        wts = torch.cat(blobs).contiguous()
-        aset.n_agents, aset.dim_c, aset.mode, aset.seed = self.A, 0, _abi.MPE_POLICY_VALUE, 0
-        aset.weights = wts.data_ptr() if wts.is_cuda else None
-        return wts, aset
-
-    def freeze(self):
-        """Pack the weights once; q() stops re-reading the modules (call again after an update; unfreeze() goes back)."""
-        self._frozen = self.pack(self.world.device)
-        return self
-
-    def unfreeze(self):
-        self._frozen = None
-        return self
+    def _input_refusal(self, i, n, D):
+        return "Critics: agent %d's critic takes %d inputs, the joint row has %d" % (i, n, D)
 
     def _rows_check(self, rows, who):
         if not torch.is_tensor(rows) or rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != self.joint_width or \
@@ -95,17 +47,10 @@ class Critics(object):
             raise _abi.MpeError("%s: rows is a contiguous float32 [M, %d] tensor on the env's device" % (who, self.joint_width))
         return int(rows.shape[0])
 
-    def _launch(self, rows, M, td=None):
+    def _launch(self, rows, M, td=None, _packed=None):
         """The one launch: q [A, M] (and y [A, M] when td, an MpeTdTarget, is given) -> (q, y); tensors cached per M."""
-        out = self._out.get(M)
-        if out is None:
-            dev = self.world.device
-            if len(self._out) >= 16:
-                self._out.clear()
-            out = self._out[M] = (torch.zeros((self.A, M), dtype=torch.float32, device=dev),
-                                  torch.zeros((self.A, M), dtype=torch.float32, device=dev))
-        q, y = out
-        wts, aset = self._frozen if self._frozen is not None else self.pack(self.world.device)
+        q, y = self._out.get(M, lambda: tuple(torch.zeros((self.A, M), dtype=torch.float32, device=self.world.device) for _ in range(2)))
+        wts, aset = _packed if _packed is not None else self.packed()
         ptrs = (C.c_void_p * self.A)(*([rows.data_ptr()] * self.A))
         _abi.check(_abi.lib().mpe_critic_q(C.byref(aset), ptrs, M, q.data_ptr(), C.byref(td) if td is not None else None,
                                            y.data_ptr() if td is not None else None, _abi.raw_stream(self.world.device)), "mpe_critic_q")
@@ -116,6 +61,12 @@ class Critics(object):
         """One launch: every agent's critic on the joint rows [M, joint_width] -> q [A, M] (this object's tensor per M)."""
         M = self._rows_check(rows, "Critics.q")
         return self._launch(rows, M)[0]
+
+    def train_forward(self, rows, packed):
+        """The forward Trainable runs, on the packed pair it hands to the backward: q -> (M, q[i] [M] per agent, the input rows)."""
+        M = self._rows_check(rows, "Critics.q")
+        q = self._launch(rows, M, _packed=packed)[0]
+        return M, [q[i].clone() for i in range(self.A)], [rows] * self.A
 
     def reference(self, rows):
         """The fp64 torch forward pass, on whatever device the modules and rows are -> [A, M] float64."""

@@ -21,110 +21,68 @@ import math
 import torch
 
 from . import _abi
-from .learner import Critics
-from .rollout import _actor_layers
+from .netset import Cache, Generations, NetSet, check_tensor
+from .policy import _obs_blocks
 
 
-class Values(object):
+class Values(NetSet):
     """Per-agent MLP state-value critics: `modules` is one nn.Sequential per agent, or one module every agent shares (Critics'
     layer rules: Linear layers with ReLU / Tanh between them, at most 3, hidden widths <= 64, float32, ONE output).  Decentralised
     (the default) critic i's first Linear takes agent i's observation width D_i and reads agent i's own [M, D_i] block, zero-copy;
     centralised=True: every critic takes all observations side by side, sum D_i <= MPE_ACTOR_MAX_INPUT inputs, from one [M, sum D_i]
     tensor of this object's (one torch.cat per call).  The weights are packed again at every call unless freeze() was called."""
+    who, noun = "Values", "critics"
 
     def __init__(self, env, modules, centralised=False):
-        import torch.nn as nn
-        w = env.world
-        self.env, self.world = env, w
-        self.A = len(w.agents)
-        if self.A > _abi.MPE_ACTOR_MAX_AGENTS:
-            raise _abi.MpeError("Values: %d agents (at most MPE_ACTOR_MAX_AGENTS = %d per set)" % (self.A, _abi.MPE_ACTOR_MAX_AGENTS))
-        off = getattr(env, "_obs_off", None)
-        if off is None:
-            raise _abi.MpeError("Values: this env has no device-side observation layout (env.fused is False)")
-        self.obs_widths = [int(off[i + 1] - off[i]) for i in range(self.A)]
         self.centralised = bool(centralised)
+        NetSet.__init__(self, env, modules)
+        self._out, self._cat, self._ptrs = Cache(), Cache(), Cache(64)
+
+    def _widths(self):
         total = sum(self.obs_widths)
         if self.centralised and total > _abi.MPE_ACTOR_MAX_INPUT:
             raise _abi.MpeError("Values(centralised=True): the observations together have %d floats, a critic's input is at most "
                                 "MPE_ACTOR_MAX_INPUT = %d wide" % (total, _abi.MPE_ACTOR_MAX_INPUT))
-        self.in_widths = [total] * self.A if self.centralised else list(self.obs_widths)
-        self.shared = isinstance(modules, nn.Module)
-        self.modules = [modules] * self.A if self.shared else list(modules)
-        if len(self.modules) != self.A:
-            raise _abi.MpeError("Values: %d critics for %d agents" % (len(self.modules), self.A))
-        self._frozen = None
-        self._out, self._cat, self._ptrs = {}, {}, {}
-        self._check()
+        self.in_widths, self.n_out = [total] * self.A if self.centralised else list(self.obs_widths), [1] * self.A
 
-    def _check(self):
-        layers = []
-        for i, m in enumerate(self.modules):
-            try:
-                lins, act = _actor_layers(m, 1, "Values")
-            except _abi.MpeError as e:
-                raise _abi.MpeError("%s [agent %d's critic: one output]" % (e, i))
-            if lins[0].in_features != self.in_widths[i]:
-                raise _abi.MpeError("Values: agent %d's critic takes %d inputs, %s %d" % (
-                    i, lins[0].in_features, "the observations together have" if self.centralised else "its observation has",
-                    self.in_widths[i]))
-            if self.in_widths[i] > _abi.MPE_ACTOR_MAX_INPUT:
-                raise _abi.MpeError("Values: agent %d's input width %d > MPE_ACTOR_MAX_INPUT = %d" % (i, self.in_widths[i], _abi.MPE_ACTOR_MAX_INPUT))
-            layers.append((lins, act))
-        return layers
-
-    # a set of one-output critics is packed, frozen and thawed as Critics' is (mode MPE_POLICY_VALUE, one copy per module object)
-    pack, freeze, unfreeze = Critics.pack, Critics.freeze, Critics.unfreeze
+    def _input_refusal(self, i, n, D):
+        return "Values: agent %d's critic takes %d inputs, %s %d" % (
+            i, n, "the observations together have" if self.centralised else "its observation has", D)
 
     def _inputs(self, obs_n):
         """-> (M, the HOST array of A device pointers, what keeps them alive); checked once per distinct set of blocks"""
-        if len(obs_n) != self.A:
-            raise _abi.MpeError("Values.v: %d observation blocks for %d agents" % (len(obs_n), self.A))
-        if not torch.is_tensor(obs_n[0]) or obs_n[0].dim() != 2:
-            raise _abi.MpeError("Values.v: obs_n[0] is a contiguous float32 [M, %d] tensor on the env's device" % self.obs_widths[0])
-        M, dev = int(obs_n[0].shape[0]), self.world.device
-        key = (M,) + tuple(o.data_ptr() if torch.is_tensor(o) else None for o in obs_n)
-        hit = self._ptrs.get(key)
-        if hit is None:
-            for i, o in enumerate(obs_n):
-                if not torch.is_tensor(o) or o.dtype != torch.float32 or not o.is_contiguous() or o.device != dev or \
-                        tuple(o.shape) != (M, self.obs_widths[i]):
-                    raise _abi.MpeError("Values.v: obs_n[%d] is a contiguous float32 [%d, %d] tensor on the env's device"
-                                        % (i, M, self.obs_widths[i]))
-            if len(self._ptrs) >= 64:
-                self._ptrs.clear()
-            if self.centralised:
-                cat = self._cat.get(M)
-                if cat is None:
-                    if len(self._cat) >= 16:
-                        self._cat.clear()
-                    cat = self._cat[M] = torch.zeros((M, self.in_widths[0]), dtype=torch.float32, device=dev)
-                hit = ((C.c_void_p * self.A)(*([cat.data_ptr()] * self.A)), cat)
-            else:
-                hit = ((C.c_void_p * self.A)(*key[1:]), None)
-            self._ptrs[key] = hit
-        if hit[1] is not None:
-            torch.cat(list(obs_n), dim=1, out=hit[1])
-        return M, hit[0]
+        def make(ptrs):
+            if not self.centralised:
+                return (C.c_void_p * self.A)(*ptrs), None
+            M = int(obs_n[0].shape[0])
+            cat = self._cat.get(M, lambda: torch.zeros((M, self.in_widths[0]), dtype=torch.float32, device=self.world.device))
+            return (C.c_void_p * self.A)(*([cat.data_ptr()] * self.A)), cat
+        M, (ptrs, cat) = _obs_blocks(self, obs_n, "Values.v", make)
+        if cat is not None:
+            torch.cat(list(obs_n), dim=1, out=cat)
+        return M, ptrs
 
-    def v(self, obs_n, out=None):
+    def v(self, obs_n, out=None, _packed=None):
         """One launch: critic i on obs_n[i] (a list of [M, D_i] device tensors: env.step's own output qualifies; centralised: every
-        critic on all of them) -> v [A, M] float32 (this object's tensor per M, or `out`)."""
+        critic on all of them) -> v [A, M] float32 (this object's tensor per M, or `out`).  (_packed: the pair to read in place of
+        packed().)"""
         M, ptrs = self._inputs(obs_n)
         dev = self.world.device
         if out is None:
-            out = self._out.get(M)
-            if out is None:
-                if len(self._out) >= 16:
-                    self._out.clear()
-                out = self._out[M] = torch.zeros((self.A, M), dtype=torch.float32, device=dev)
-        elif not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (self.A, M) or not out.is_contiguous() or \
-                out.device != dev:
-            raise _abi.MpeError("Values.v: out is a contiguous float32 [%d, %d] tensor on the env's device" % (self.A, M))
-        wts, aset = self._frozen if self._frozen is not None else self.pack(dev)
+            out = self._out.get(M, lambda: torch.zeros((self.A, M), dtype=torch.float32, device=dev))
+        else:
+            check_tensor("Values.v", out, "out", [(self.A, M)], "the env's device", dev)
+        wts, aset = _packed if _packed is not None else self.packed()
         _abi.check(_abi.lib().mpe_critic_q(C.byref(aset), ptrs, M, out.data_ptr(), None, None, _abi.raw_stream(dev)), "mpe_critic_q")
         del wts      # (stream-ordered: the caching allocator reuses the block only behind the launch)
         return out
+
+    def train_forward(self, obs_n, packed):
+        """The forward Trainable runs, on the packed pair it hands to the backward: v -> (M, v[i] [M] per agent, the input rows: the
+        side-by-side tensor for every agent where centralised)."""
+        v = self.v(obs_n, _packed=packed)
+        M = int(v.shape[1])
+        return M, [v[i].clone() for i in range(self.A)], [self._cat[M]] * self.A if self.centralised else list(obs_n)
 
     def reference(self, obs_n):
         """The fp64 torch forward pass, on whatever device the modules and obs_n are -> [A, M] float64."""
@@ -193,20 +151,12 @@ class GaeResult(object):
         self.adv, self.ret = adv, ret
 
 
-def _tensor_check(x, name, shape, dtypes, dev, who):
-    if not torch.is_tensor(x) or x.dtype not in dtypes or (shape is not None and tuple(x.shape) != tuple(shape)) or \
-            not x.is_contiguous() or (dev is not None and x.device != dev):
-        raise _abi.MpeError("%s: %s is a contiguous %s %s tensor on %s" % (
-            who, name, " / ".join(str(d).replace("torch.", "") for d in dtypes),
-            list(shape) if shape is not None else "[T, A, B]", "rew's device" if dev is not None else "a GPU"))
-
-
 def gae_tensors(rew, done, val, boot, gamma, lam, episode_len=0, episode_phase=0, out=None):
     """GAE(lambda) by THE GAE RULE in one launch, no host synchronisation (captures into a HIP graph).  rew, val [T, A, B] float32;
     done [T, A, B] bool or uint8; boot [K, A, B] float32 with K = segments(T, episode_len, episode_phase): V of the output
     observation of every segment-ending step.  out: a GaeResult to rewrite.  -> GaeResult(adv, ret)."""
     who = "gae_tensors"
-    _tensor_check(rew, "rew", None, (torch.float32,), None, who)
+    check_tensor(who, rew, "rew", None, "a GPU", text="[T, A, B]")
     if rew.dim() != 3:
         raise _abi.MpeError("%s: rew is a contiguous float32 [T, A, B] tensor on a GPU" % who)
     T, A, B = (int(n) for n in rew.shape)
@@ -214,16 +164,16 @@ def gae_tensors(rew, done, val, boot, gamma, lam, episode_len=0, episode_phase=0
     if not math.isfinite(float(gamma)) or not math.isfinite(float(lam)):
         raise _abi.MpeError("%s: gamma = %r, lam = %r (both finite)" % (who, gamma, lam))
     K = segments(T, episode_len, episode_phase)
-    _tensor_check(done, "done", (T, A, B), (torch.bool, torch.uint8), dev, who)
-    _tensor_check(val, "val", (T, A, B), (torch.float32,), dev, who)
-    _tensor_check(boot, "boot", (K, A, B), (torch.float32,), dev, who)
+    check_tensor(who, done, "done", [(T, A, B)], "rew's device", dev, (torch.bool, torch.uint8))
+    check_tensor(who, val, "val", [(T, A, B)], "rew's device", dev)
+    check_tensor(who, boot, "boot", [(K, A, B)], "rew's device", dev)
     if out is None:
         out = GaeResult(torch.empty_like(rew), torch.empty_like(rew))
     else:
         if not isinstance(out, GaeResult):
             raise _abi.MpeError("%s: out is a GaeResult (what an earlier call returned)" % who)
-        _tensor_check(out.adv, "out.adv", (T, A, B), (torch.float32,), dev, who)
-        _tensor_check(out.ret, "out.ret", (T, A, B), (torch.float32,), dev, who)
+        check_tensor(who, out.adv, "out.adv", [(T, A, B)], "rew's device", dev)
+        check_tensor(who, out.ret, "out.ret", [(T, A, B)], "rew's device", dev)
     if not rew.is_cuda:
         raise _abi.MpeError("%s: rew is on %s (the tensors live on a GPU: there is no CPU path)" % (who, dev))
     g = _abi.MpeGae()
@@ -250,18 +200,12 @@ def perm(N, seed, epoch, q):
     return int(j)
 
 
-def _stats_work(T, A, B, dev, cache={}):
+def _stats_work(T, A, B, dev, cache=Cache()):
     """the float64 workspace of mpe_adv_stats for one shape on one device (every entry is written before it is read)"""
     n = _abi.lib().mpe_adv_stats_work(T, A, B)
     if n < 0:
         _abi.check(int(n), "mpe_adv_stats_work")
-    key = (T, A, B, dev)
-    w = cache.get(key)
-    if w is None:
-        if len(cache) >= 16:
-            cache.clear()
-        w = cache[key] = torch.empty((max(int(n), 1),), dtype=torch.float64, device=dev)
-    return w
+    return cache.get((T, A, B, dev), lambda: torch.empty((max(int(n), 1),), dtype=torch.float64, device=dev))
 
 
 def adv_stats(g_or_adv, eps=1e-8, out=None):
@@ -277,8 +221,8 @@ def adv_stats(g_or_adv, eps=1e-8, out=None):
         raise _abi.MpeError("%s: eps = %r (a finite value >= 0)" % (who, eps))
     if out is None:
         out = torch.empty((A, 2), dtype=torch.float32, device=dev)
-    elif not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (A, 2) or not out.is_contiguous() or out.device != dev:
-        raise _abi.MpeError("%s: out is a contiguous float32 [%d, 2] tensor on adv's device" % (who, A))
+    else:
+        check_tensor(who, out, "out", [(A, 2)], "adv's device", dev)
     if not adv.is_cuda:
         raise _abi.MpeError("%s: adv is on %s (the tensors live on a GPU: there is no CPU path)" % (who, dev))
     work = _stats_work(T, A, B, dev)
@@ -318,15 +262,14 @@ class Minibatches(object):
         flat = getattr(traj, "obs_in_flat", None)
         if flat is None or getattr(traj, "val", None) is None:
             raise _abi.MpeError("%s: traj holds no decision observations: record it with PolicyLoop.run(T, values=Values(env, modules))" % who)
-        _tensor_check(g.adv, "g.adv", None, (torch.float32,), None, who)
+        check_tensor(who, g.adv, "g.adv", None, "a GPU", text="[T, A, B]")
         if g.adv.dim() != 3:
             raise _abi.MpeError("%s: g.adv is a contiguous float32 [T, A, B] tensor on a GPU" % who)
         T, A, B = (int(n) for n in g.adv.shape)
         dev = g.adv.device
 
         def chk(x, name, shape):
-            if not torch.is_tensor(x) or x.dtype != torch.float32 or tuple(x.shape) != tuple(shape) or not x.is_contiguous() or x.device != dev:
-                raise _abi.MpeError("%s: %s is a contiguous float32 %s tensor on g.adv's device" % (who, name, list(shape)))
+            check_tensor(who, x, name, [tuple(shape)], "g.adv's device", dev)
         chk(g.ret, "g.ret", (T, A, B))
         chk(traj.val, "traj.val", (T, A, B))
         chk(traj.act, "traj.act", (T, A, B, _abi.MPE_ACTION_DIM))
@@ -364,7 +307,7 @@ class Minibatches(object):
         tr.obs_in, tr.act, tr.utter = flat.data_ptr(), traj.act.data_ptr(), utter.data_ptr() if dim_c else None
         tr.logp, tr.adv, tr.ret, tr.val = logp.data_ptr() if logp is not None else None, g.adv.data_ptr(), g.ret.data_ptr(), traj.val.data_ptr()
         self.stats = torch.empty((A, 2), dtype=torch.float32, device=dev) if normalise else None
-        self._out = {}
+        self._out = Cache()
         if normalise:
             self.restats()
 
@@ -378,10 +321,7 @@ class Minibatches(object):
         return (self.N + self.M - 1) // self.M
 
     def _outputs(self, M):
-        o = self._out.get(M)
-        if o is None:
-            if len(self._out) >= 16:
-                self._out.clear()
+        def make():
             A, dev, f = self.A, self.device, torch.float32
             o = OnPolicyBatch()
             o.M, o.B = M, self.B
@@ -396,8 +336,8 @@ class Minibatches(object):
             o.logp = torch.zeros((A, M), dtype=f, device=dev) if self._keep[3] is not None else None
             o.adv, o.ret, o.val = (torch.zeros((A, M), dtype=f, device=dev) for _ in range(3))
             o.joint_obs = torch.zeros((M, sum(self.widths)), dtype=f, device=dev) if self.joint else None
-            self._out[M] = o
-        return o
+            return o
+        return self._out.get(M, make)
 
     def batch(self, epoch, k, M=None):
         """Minibatch k of `epoch`: rows k * self.M .. of the permutation (M rows; the default: self.M, or what is left of the
@@ -485,9 +425,7 @@ def ppo_loss_tensors(logits_n, values_n, act, utter, logp_old, adv, ret, val_old
     M, dev = int(z0.shape[0]), z0.device
 
     def chk(x, name, shapes):
-        if not torch.is_tensor(x) or x.dtype != torch.float32 or tuple(x.shape) not in shapes or not x.is_contiguous() or x.device != dev:
-            raise _abi.MpeError("%s: %s is a contiguous float32 %s tensor on logits_n[0]'s device"
-                                % (who, name, " or ".join(str(list(s)) for s in shapes)))
+        check_tensor(who, x, name, shapes, "logits_n[0]'s device", dev)
     for i, z in enumerate(logits_n):
         chk(z, "logits_n[%d]" % i, [(M, n_out[i])])
     if values_n is not None:
@@ -550,12 +488,8 @@ class _PpoLossFn(torch.autograd.Function):
         key = (M, n_values > 0, logits_n[0].device if torch.is_tensor(logits_n[0]) else None)
         res = ppo_loss_tensors(logits_n, values_n, batch.act, batch.utter, batch.logp, batch.adv, batch.ret, batch.val, head.movable,
                                head.speaks, head.dim_c, head.clip, head.value_clip, head.vf_coef, head.ent_coef, out=head._out.get(key))
-        if key not in head._out:
-            if len(head._out) >= 16:
-                head._out.clear()
-            head._out[key] = res
-        head._generation[key] = head._generation.get(key, 0) + 1
-        ctx.res, ctx.shapes, ctx.owner = res, [tuple(t.shape) for t in tensors], (head, key, head._generation[key])
+        head._out.get(key, lambda: res)
+        ctx.res, ctx.shapes, ctx.owner = res, [tuple(t.shape) for t in tensors], (head, key, head._generation.next(key))
         head.last = res
         return res.loss.view(())
 
@@ -564,7 +498,7 @@ class _PpoLossFn(torch.autograd.Function):
     def backward(ctx, grad_output):
         res = ctx.res
         head, key, generation = ctx.owner
-        if head._generation.get(key) != generation or head._out.get(key) is not res:
+        if head._generation.stale(key, generation) or head._out.get(key) is not res:
             raise _abi.MpeError("PpoLoss: backward() of a loss whose buffers a later forward with the same M has rewritten (the "
                                 "buffers are cached per M: call backward() before the next forward)")
         A = len(res.dlogits_n)
@@ -608,7 +542,7 @@ class PpoLoss(object):
         if not math.isfinite(float(vf_coef)) or not math.isfinite(float(ent_coef)):
             raise _abi.MpeError("PpoLoss: vf_coef = %r, ent_coef = %r (both finite)" % (vf_coef, ent_coef))
         self.clip, self.value_clip, self.vf_coef, self.ent_coef = float(clip), value_clip, float(vf_coef), float(ent_coef)
-        self._out, self._generation, self.last = {}, {}, None
+        self._out, self._generation, self.last = Cache(), Generations(), None
 
     def __call__(self, logits_n, values_n, batch):
         who = "PpoLoss"

@@ -1,8 +1,8 @@
 """The optimiser step on the device: `DeviceAdam` keeps the packed weights of up to eight `Actors` / `Values` / `Critics` as the
 MASTER copy in device memory, with Adam's moments in the same layout and the step count beside them, and `step()` updates all of
 them in place in TWO launches (mpe_adam_step: THE ADAM RULE of include/mpe_hip.h) from the packed gradients
-mpe_mlp_grad wrote.  The nets' `_frozen` points at the live buffers: every forward launch reads the new weights, nothing repacks,
-and a captured PolicyLoop graph keeps working across updates.
+mpe_mlp_grad wrote.  The live buffers are attached to the nets (NetSet.attach): every forward launch reads the new weights, nothing
+repacks, and a captured PolicyLoop graph keeps working across updates.
 
     pi, V = Trainable(Actors(env, actor_modules, logits=True)), Trainable(Values(env, critic_modules))
     opt = DeviceAdam([pi, V], lr=3e-4, max_grad_norm=0.5)
@@ -18,9 +18,10 @@ import torch
 
 from . import _abi
 from .learner import Critics
+from .netset import unpack_layers
 from .onpolicy import Values
 from .policy import Actors
-from .train import MlpGradResult, Trainable, _module_views
+from .train import MlpGradResult, Trainable
 
 _STATE = _abi.MPE_ADAM_STATE_DOUBLES
 
@@ -29,7 +30,7 @@ class DeviceAdam(object):
     """Adam / AdamW (weight_decay > 0: decoupled) with global-norm clipping (max_grad_norm > 0: torch's clip_grad_norm_ over ALL
     nets together) on the packed buffers, in place.  nets: 1..MPE_ADAM_MAX_SETS of Actors / Values / Critics (a Trainable stands for
     its .net).  Each net is packed ONCE here into a persistent buffer, gets m and v as zeros in the same layout, and reads that
-    buffer from now on (net._frozen): the modules' own parameters are NOT updated until write_back().  lr_tensor: a one-element
+    buffer from now on (net.attach): the modules' own parameters are NOT updated until write_back().  lr_tensor: a one-element
     float32 device tensor the launch reads instead of lr (a schedule under a captured graph).  Refused, with the argument named: a
     module object that appears in two of the nets (two master copies), a net on another device, a net that is already frozen.
     Do NOT call freeze() / unfreeze() on a net the optimiser holds: either replaces the live buffer by a snapshot of the stale
@@ -49,7 +50,7 @@ class DeviceAdam(object):
                                     % (who, k, type(net).__name__))
             if any(net is other for other in self.nets[:k]):
                 raise _abi.MpeError("%s: nets[%d] is nets[%d] again" % (who, k, [net is o for o in self.nets].index(True)))
-            if net._frozen is not None:
+            if net.attached() is not None:
                 raise _abi.MpeError("%s: nets[%d] is already frozen (unfreeze() it, or release() the DeviceAdam that holds it: the "
                                     "optimiser packs the modules once itself)" % (who, k))
             for i, m in enumerate(net.modules):
@@ -94,7 +95,7 @@ class DeviceAdam(object):
         self.work = torch.zeros((_abi.MPE_ADAM_MAX_PARTIALS,), dtype=torch.float64, device=dev)      # (mpe_adam_work(cfg) <= 256 doubles)
         self._shared = []
         for net, wts, aset in zip(self.nets, self.weights, self._asets):
-            net._frozen = (wts, aset)
+            net.attach((wts, aset))
 
     def _index(self, net, who):
         net = net.net if isinstance(net, Trainable) else net
@@ -113,7 +114,7 @@ class DeviceAdam(object):
         other = other.net if isinstance(other, Trainable) else other
         if not isinstance(other, (Actors, Values, Critics)):
             raise _abi.MpeError("%s: other is an Actors, a Values or a Critics (got %s)" % (who, type(other).__name__))
-        if other._frozen is not None:
+        if other.attached() is not None:
             raise _abi.MpeError("%s: other is already frozen" % who)
         if len(other.modules) != len(mine.modules) or any(a is not b for a, b in zip(other.modules, mine.modules)):
             raise _abi.MpeError("%s: other is built over other modules than net (the same module objects, in the same order)" % who)
@@ -124,7 +125,7 @@ class DeviceAdam(object):
             raise _abi.MpeError("%s: other's packed layout differs from net's (offsets %s against %s)"
                                 % (who, list(aset.offset)[:other.A], list(self._asets[k].offset)[:mine.A]))
         aset.weights = self.weights[k].data_ptr()
-        other._frozen = (self.weights[k], aset)
+        other.attach((self.weights[k], aset))
         self._shared.append(other)
         return other
 
@@ -134,11 +135,13 @@ class DeviceAdam(object):
         computed, which is set back to None here."""
         who = "DeviceAdam.step"
         for k, net in enumerate(self.nets):
-            if net._frozen is None or net._frozen[0] is not self.weights[k]:
+            pair = net.attached()
+            if pair is None or pair[0] is not self.weights[k]:
                 raise _abi.MpeError("%s: nets[%d] no longer reads the optimiser's live buffer (freeze() / unfreeze() was called on it: "
                                     "the step would update weights nobody reads -- release() the optimiser first)" % (who, k))
         for other in self._shared:
-            if other._frozen is None or not any(other._frozen[0] is w for w in self.weights):
+            pair = other.attached()
+            if pair is None or not any(pair[0] is w for w in self.weights):
                 raise _abi.MpeError("%s: a set joined by share() no longer reads the optimiser's live buffer (freeze() / unfreeze() was "
                                     "called on it)" % who)
         if grads is None:
@@ -165,26 +168,17 @@ class DeviceAdam(object):
     def write_back(self):
         """Copy the live weights into the modules' parameters (plain torch, off the hot path: for evaluation or saving through
         torch)."""
-        with torch.no_grad():
-            for net, wts in zip(self.nets, self.weights):
-                views, _ = _module_views(net, wts)
-                seen, k = set(), 0
-                for (lins, _), m in zip(net._check(), net.modules):
-                    if id(m) in seen:
-                        continue
-                    seen.add(id(m))
-                    for (w, b), lin in zip(views[k], lins):
-                        lin.weight.copy_(w)
-                        if lin.bias is not None:
-                            lin.bias.copy_(b)
-                    k += 1
+        for net, wts in zip(self.nets, self.weights):
+            at = 0
+            for _, lins in net.distinct():
+                at += unpack_layers(lins, wts, at=at)
         return self
 
     def release(self):
-        """write_back(), then every net (and every shared one) packs from its modules again (_frozen = None)."""
+        """write_back(), then every net (and every shared one) packs from its modules again (nothing stays attached)."""
         self.write_back()
         for net in self.nets + self._shared:
-            net._frozen = None
+            net.attach(None)
         self._shared = []
         return self
 

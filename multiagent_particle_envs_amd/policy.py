@@ -11,28 +11,14 @@ import ctypes as C
 import torch
 
 from . import _abi
-from .rollout import _POLICY_MODES, _actor_layers, _copy_struct, _step_many_env_check
-
-_W, _LW = _abi.MPE_POLICY_MAX_WIDTH, _abi.MPE_ACTOR_MAX_OUT
+from .netset import _LW, Cache, NetSet, _actor_layers, check_tensor, pack_layers
+from .rollout import _POLICY_MODES, _copy_struct, _step_many_env_check
 
 
 def pack_actor16(module, n_out):
-    """One actor in the packed layout of include/mpe_hip.h (MpeActorSet): for each Linear layer l, W_l as [in_l][out_l'] (W_l[k][j] =
-    weight[j][k]) then bias[out_l'], with in_0 = the input width, in_l = 64 for l > 0, out_l' = 64 for a hidden layer and 16 for the
-    last, zero padding.  -> a float32 tensor on the module's device whose length is a multiple of 16."""
-    lins, _ = _actor_layers(module, n_out, "Actors")
-    dev = lins[0].weight.device
-    parts = []
-    for k, lin in enumerate(lins):
-        n_in = lin.in_features if k == 0 else _W
-        wide = _LW if k + 1 == len(lins) else _W
-        w = torch.zeros((n_in, wide), dtype=torch.float32, device=dev)
-        w[:lin.in_features, :lin.out_features] = lin.weight.detach().t()
-        b = torch.zeros(wide, dtype=torch.float32, device=dev)
-        if lin.bias is not None:
-            b[:lin.out_features] = lin.bias.detach()
-        parts += [w.reshape(-1), b]
-    return torch.cat(parts)
+    """One actor in the packed layout of include/mpe_hip.h (MpeActorSet; netset.layout with a 16-wide last layer) -> a float32
+    tensor on the module's device whose length is a multiple of 16."""
+    return pack_layers(_actor_layers(module, n_out, "Actors")[0], _LW)
 
 
 def joint_layout(obs_widths, movable, speaks, dim_c):
@@ -63,12 +49,31 @@ def env_joint_layout(env, who):
                         int(w.dim_c) if any(speaks) else 0)
 
 
+def _obs_blocks(net, obs_n, who, make, M=None):
+    """-> (M, what make(A device pointers) built) for obs_n, a list of A contiguous float32 [M, D_i] blocks on the env's device (M:
+    obs_n[0]'s rows, where the caller does not fix it); the blocks are checked, and make() is called, once per distinct set of
+    blocks (net._ptrs)."""
+    if len(obs_n) != net.A:
+        raise _abi.MpeError("%s: %d observation blocks for %d agents" % (who, len(obs_n), net.A))
+    if M is None:
+        if not torch.is_tensor(obs_n[0]) or obs_n[0].dim() != 2:
+            raise _abi.MpeError("%s: obs_n[0] is a contiguous float32 [M, %d] tensor on the env's device" % (who, net.obs_widths[0]))
+        M = int(obs_n[0].shape[0])
+    key = (M,) + tuple(o.data_ptr() if torch.is_tensor(o) else None for o in obs_n)
+
+    def checked():
+        for i, o in enumerate(obs_n):
+            check_tensor(who, o, "obs_n[%d]" % i, [(M, net.obs_widths[i])], "the env's device", net.world.device)
+        return make(key[1:])
+    return M, net._ptrs.get(key, checked)
+
+
 class _Rows(object):
     """The outputs of Actors.act_rows for one M."""
     __slots__ = ("moves", "utter", "logp", "ids", "logits", "joint", "action")
 
 
-class Actors(object):
+class Actors(NetSet):
     """Per-agent MLP actors for any env: `modules` is one nn.Sequential per agent, or one module every agent shares (Linear layers
     with ReLU / Tanh between them, at most 3 Linear layers, hidden widths <= 64, float32).  Agent i's first Linear takes its
     observation width D_i; its last gives 5 * movable + dim_c * speaks logits: a movable agent's first 5 are its move head, a
@@ -77,128 +82,65 @@ class Actors(object):
     int32 (move head, utterance head; -1 where an agent has no such head) and pi.logits [A,B,16] (raw last-layer outputs).
     The weights are packed again at every act() unless freeze() was called, so in-place optimiser updates are seen; agents
     handed the SAME module object share one packed copy."""
+    who, noun = "Actors", "actors"
 
     def __init__(self, env, modules, mode="sample", seed=0, logp=False, ids=False, logits=False):
-        import torch.nn as nn
         if mode not in _POLICY_MODES:
             raise _abi.MpeError("Actors: mode is one of %s (got %r)" % (sorted(_POLICY_MODES), mode))
-        w = env.world
-        self.env, self.world, self.mode = env, w, mode
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self.A, self.B = len(w.agents), w.batch_size
-        if self.A > _abi.MPE_ACTOR_MAX_AGENTS:
-            raise _abi.MpeError("Actors: %d agents (at most MPE_ACTOR_MAX_AGENTS = %d per set)" % (self.A, _abi.MPE_ACTOR_MAX_AGENTS))
-        off = getattr(env, "_obs_off", None)
-        if off is None:
-            raise _abi.MpeError("Actors: this env has no device-side observation layout (env.fused is False)")
-        self.obs_widths = [int(off[i + 1] - off[i]) for i in range(self.A)]
-        self.movable = [bool(a.movable) for a in w.agents]
-        self.speaks = [not a.silent for a in w.agents]
-        self.dim_c = int(w.dim_c) if any(self.speaks) else 0
-        self.n_out = [_abi.MPE_ACTION_DIM * m + self.dim_c * s for m, s in zip(self.movable, self.speaks)]
-        self.shared = isinstance(modules, nn.Module)
-        self.modules = [modules] * self.A if self.shared else list(modules)
-        if len(self.modules) != self.A:
-            raise _abi.MpeError("Actors: %d actors for %d agents" % (len(self.modules), self.A))
+        self.mode, self.seed = mode, int(seed) & (2 ** 64 - 1)
+        NetSet.__init__(self, env, modules)
+        self.B = self.world.batch_size
         self._want = (bool(logp), bool(ids), bool(logits))
         self.moves = self.utter = self.logp = self.ids = self.logits = None
         self.off, self.joint_width, self.col_move, self.col_utter = joint_layout(self.obs_widths, self.movable, self.speaks, self.dim_c)
         self.rows = self.joint_rows = None
-        self._rows = {}
-        self._frozen = None
-        self._ptrs = {}
-        self._check()
+        self._rows, self._ptrs = Cache(), Cache(64)
 
-    def _check(self):
-        """Every module against its agent; -> [(Linear layers, activation)] per agent."""
-        layers = []
-        for i, m in enumerate(self.modules):
-            if self.n_out[i] < 1:
-                raise _abi.MpeError("Actors: agent %d neither moves nor speaks: it has no head" % i)
-            if self.n_out[i] > _LW:
-                raise _abi.MpeError("Actors: agent %d needs %d logits (5 * movable + dim_c * speaks), at most MPE_ACTOR_MAX_OUT = %d"
-                                    % (i, self.n_out[i], _LW))
-            try:
-                lins, act = _actor_layers(m, self.n_out[i], "Actors")
-            except _abi.MpeError as e:
-                raise _abi.MpeError("%s [agent %d: movable = %s, speaks = %s, dim_c = %d]"
-                                    % (e, i, self.movable[i], self.speaks[i], self.dim_c))
-            D = self.obs_widths[i]
-            if lins[0].in_features != D:
-                raise _abi.MpeError("Actors: agent %d's actor takes %d inputs, its observation has %d" % (i, lins[0].in_features, D))
-            if D > _abi.MPE_ACTOR_MAX_INPUT:
-                raise _abi.MpeError("Actors: agent %d's input width %d > MPE_ACTOR_MAX_INPUT = %d" % (i, D, _abi.MPE_ACTOR_MAX_INPUT))
-            layers.append((lins, act))
-        return layers
+    def _widths(self):
+        w = self.world
+        self.movable = [bool(a.movable) for a in w.agents]
+        self.speaks = [not a.silent for a in w.agents]
+        self.dim_c = int(w.dim_c) if any(self.speaks) else 0
+        self.n_out = [_abi.MPE_ACTION_DIM * m + self.dim_c * s for m, s in zip(self.movable, self.speaks)]
+        self.in_widths = self.obs_widths
 
-    def pack(self, device=None):
-        """-> (weights tensor, MpeActorSet): the set's packed actors, one copy per distinct module object."""
-        layers = self._check()
-        aset = _abi.MpeActorSet()
-        blobs, where, off = [], {}, 0
-        for i, m in enumerate(self.modules):
-            if id(m) not in where:
-                blob = pack_actor16(m, self.n_out[i])
-                where[id(m)] = off
-                blobs.append(blob if device is None else blob.to(device))
-                off += blob.numel()
-            lins, act = layers[i]
-            aset.n_layers[i] = len(lins)
-            aset.width[i][0] = lins[0].in_features
-            for k, lin in enumerate(lins):
-                aset.width[i][k + 1] = lin.out_features
-            aset.activation[i] = _abi.MPE_POLICY_TANH if act == "tanh" else _abi.MPE_POLICY_RELU
-            aset.offset[i] = where[id(m)]
-            aset.movable[i] = int(self.movable[i])
-            aset.speaks[i] = int(self.speaks[i])
-        wts = torch.cat(blobs).contiguous()
-        aset.n_agents, aset.dim_c = self.A, self.dim_c
-        aset.mode, aset.seed = _POLICY_MODES[self.mode], self.seed
-        aset.weights = wts.data_ptr() if wts.is_cuda else None
-        return wts, aset
+    def _agent(self, i):
+        if self.n_out[i] < 1:
+            raise _abi.MpeError("Actors: agent %d neither moves nor speaks: it has no head" % i)
+        if self.n_out[i] > _LW:
+            raise _abi.MpeError("Actors: agent %d needs %d logits (5 * movable + dim_c * speaks), at most MPE_ACTOR_MAX_OUT = %d"
+                                % (i, self.n_out[i], _LW))
+        return "agent %d: movable = %s, speaks = %s, dim_c = %d" % (i, self.movable[i], self.speaks[i], self.dim_c)
 
-    def freeze(self):
-        """Pack the weights once; act() stops re-reading the modules (call again after an update; unfreeze() goes back)."""
-        self._frozen = self.pack(self.world.device)
-        return self
+    def _input_refusal(self, i, n, D):
+        return "Actors: agent %d's actor takes %d inputs, its observation has %d" % (i, n, D)
 
-    def unfreeze(self):
-        self._frozen = None
-        return self
+    def _tail(self, aset):
+        for i in range(self.A):
+            aset.movable[i], aset.speaks[i] = int(self.movable[i]), int(self.speaks[i])
+        aset.dim_c, aset.mode, aset.seed = self.dim_c, _POLICY_MODES[self.mode], self.seed
+
+    def _new_rows(self, M):
+        """the output tensors of one launch over M rows"""
+        A, dev = self.A, self.world.device
+        r = _Rows()
+        r.moves = torch.zeros((A, M, _abi.MPE_ACTION_DIM), dtype=torch.float32, device=dev)
+        r.utter = torch.zeros((A, M, self.dim_c), dtype=torch.float32, device=dev) if self.dim_c else None
+        r.action = (r.moves, r.utter) if self.dim_c else r.moves
+        logp, ids, logits = self._want
+        r.logp = torch.zeros((A, M), dtype=torch.float32, device=dev) if logp else None
+        r.ids = torch.zeros((2, A, M), dtype=torch.int32, device=dev) if ids else None
+        r.logits = torch.zeros((A, M, _LW), dtype=torch.float32, device=dev) if logits else None
+        r.joint = None
+        return r
 
     def _buffers(self):
-        if self.moves is not None:
-            return
-        A, B, dev = self.A, self.B, self.world.device
-        self.moves = torch.zeros((A, B, _abi.MPE_ACTION_DIM), dtype=torch.float32, device=dev)
-        if self.dim_c:
-            self.utter = torch.zeros((A, B, self.dim_c), dtype=torch.float32, device=dev)
-            self._action = (self.moves, self.utter)
-        else:
-            self._action = self.moves
-        logp, ids, logits = self._want
-        if logp:
-            self.logp = torch.zeros((A, B), dtype=torch.float32, device=dev)
-        if ids:
-            self.ids = torch.zeros((2, A, B), dtype=torch.int32, device=dev)
-        if logits:
-            self.logits = torch.zeros((A, B, _LW), dtype=torch.float32, device=dev)
+        if self.moves is None:
+            r = self._new_rows(self.B)
+            self.moves, self.utter, self.logp, self.ids, self.logits, self._action = r.moves, r.utter, r.logp, r.ids, r.logits, r.action
 
-    def _obs_ptrs(self, obs_n):
-        if len(obs_n) != self.A:
-            raise _abi.MpeError("Actors.act: %d observation blocks for %d agents" % (len(obs_n), self.A))
-        key = tuple(o.data_ptr() for o in obs_n)
-        arr = self._ptrs.get(key)
-        if arr is None:
-            for i, o in enumerate(obs_n):
-                if not torch.is_tensor(o) or o.dtype != torch.float32 or not o.is_contiguous() or o.device != self.world.device or \
-                        tuple(o.shape) != (self.B, self.obs_widths[i]):
-                    raise _abi.MpeError("Actors.act: obs_n[%d] is a contiguous float32 [%d, %d] tensor on the env's device"
-                                        % (i, self.B, self.obs_widths[i]))
-            if len(self._ptrs) >= 64:
-                self._ptrs.clear()
-            arr = self._ptrs[key] = (C.c_void_p * self.A)(*key)
-        return arr
+    def _ptr_array(self, ptrs):
+        return (C.c_void_p * self.A)(*ptrs)
 
     def act(self, obs_n, t=0, moves=None, logp=None):
         """One launch: every agent's rows for the observations obs_n (a list of [B, D_i] device tensors: env.step's / env.reset's
@@ -206,11 +148,11 @@ class Actors(object):
         [A,B,dim_c]) where agents speak: what env.step takes, zero-copy.  The tensors are this object's own and are rewritten by
         the next act(); moves / logp: write those two into the caller's tensors instead (a trajectory's rows)."""
         self._buffers()
-        wts, aset = self._frozen if self._frozen is not None else self.pack(self.world.device)
+        wts, aset = self.packed()
         mv = self.moves if moves is None else moves
         lp = self.logp if logp is None else logp
         _abi.check(_abi.lib().mpe_actor_act(
-            C.byref(aset), self._obs_ptrs(obs_n), self.B, int(t), int(self.world.world_offset), mv.data_ptr(),
+            C.byref(aset), _obs_blocks(self, obs_n, "Actors.act", self._ptr_array, self.B)[1], self.B, int(t), int(self.world.world_offset), mv.data_ptr(),
             self.utter.data_ptr() if self.utter is not None else None, self.ids.data_ptr() if self.ids is not None else None,
             lp.data_ptr() if lp is not None else None, self.logits.data_ptr() if self.logits is not None else None,
             _abi.raw_stream(self.world.device)), "mpe_actor_act")
@@ -221,49 +163,21 @@ class Actors(object):
 
     def _rows_out(self, M, joint):
         """act_rows' own output tensors, one set per M (the [B]-sized buffers of act() are not touched)."""
-        r = self._rows.get(M)
-        if r is None:
-            A, dev = self.A, self.world.device
-            r = _Rows()
-            r.moves = torch.zeros((A, M, _abi.MPE_ACTION_DIM), dtype=torch.float32, device=dev)
-            r.utter = torch.zeros((A, M, self.dim_c), dtype=torch.float32, device=dev) if self.dim_c else None
-            r.action = (r.moves, r.utter) if self.dim_c else r.moves
-            logp, ids, logits = self._want
-            r.logp = torch.zeros((A, M), dtype=torch.float32, device=dev) if logp else None
-            r.ids = torch.zeros((2, A, M), dtype=torch.int32, device=dev) if ids else None
-            r.logits = torch.zeros((A, M, _LW), dtype=torch.float32, device=dev) if logits else None
-            r.joint = None
-            if len(self._rows) >= 16:
-                self._rows.clear()
-            self._rows[M] = r
+        r = self._rows.get(M, lambda: self._new_rows(M))
         if joint and r.joint is None:
             r.joint = torch.zeros((M, self.joint_width), dtype=torch.float32, device=self.world.device)
         return r
 
-    def act_rows(self, obs_n, t=0, row_offset=0, joint=None):
+    def act_rows(self, obs_n, t=0, row_offset=0, joint=None, _packed=None):
         """act() over M rows of any origin (M = obs_n[0].shape[0]: a sampled minibatch's next_obs_n) in one launch
         (mpe_actor_act_rows): row m's SAMPLE draws are those of world row_offset + m at step t.  joint=True: the same launch also
         writes the centralised critic's input rows [M, joint_width] -- every observation, then the action rows just decided, in
         ReplayBatch.joint's columns (self.off, col_move, col_utter) -- into a tensor of this object's; joint=a contiguous float32
         [M, >= joint_width] device tensor: into that one.  -> what act() returns, [A,M,...]; self.joint_rows is the joint tensor
         (None without joint) and self.rows holds every output of the call (moves, utter, logp, ids, logits, joint).  The tensors
-        are cached per M and rewritten by the next act_rows of that M."""
-        if len(obs_n) != self.A:
-            raise _abi.MpeError("Actors.act_rows: %d observation blocks for %d agents" % (len(obs_n), self.A))
-        if not torch.is_tensor(obs_n[0]) or obs_n[0].dim() != 2:
-            raise _abi.MpeError("Actors.act_rows: obs_n[0] is a contiguous float32 [M, %d] tensor on the env's device" % self.obs_widths[0])
-        M, dev = int(obs_n[0].shape[0]), self.world.device
-        key = (M,) + tuple(o.data_ptr() if torch.is_tensor(o) else None for o in obs_n)
-        arr = self._ptrs.get(key)
-        if arr is None:
-            for i, o in enumerate(obs_n):
-                if not torch.is_tensor(o) or o.dtype != torch.float32 or not o.is_contiguous() or o.device != dev or \
-                        tuple(o.shape) != (M, self.obs_widths[i]):
-                    raise _abi.MpeError("Actors.act_rows: obs_n[%d] is a contiguous float32 [%d, %d] tensor on the env's device"
-                                        % (i, M, self.obs_widths[i]))
-            if len(self._ptrs) >= 64:
-                self._ptrs.clear()
-            arr = self._ptrs[key] = (C.c_void_p * self.A)(*key[1:])
+        are cached per M and rewritten by the next act_rows of that M.  (_packed: the pair to read in place of packed().)"""
+        M, arr = _obs_blocks(self, obs_n, "Actors.act_rows", self._ptr_array)
+        dev = self.world.device
         own = joint is True
         if joint is not None and joint is not False and not own:
             if not torch.is_tensor(joint) or joint.dtype != torch.float32 or joint.dim() != 2 or joint.shape[0] != M or \
@@ -272,7 +186,7 @@ class Actors(object):
                                     % (M, self.joint_width))
         r = self._rows_out(M, own)
         jt = r.joint if own else joint if torch.is_tensor(joint) else None
-        wts, aset = self._frozen if self._frozen is not None else self.pack(dev)
+        wts, aset = _packed if _packed is not None else self.packed()
         _abi.check(_abi.lib().mpe_actor_act_rows(
             C.byref(aset), arr, M, int(t), int(row_offset), r.moves.data_ptr(), r.utter.data_ptr() if r.utter is not None else None,
             r.ids.data_ptr() if r.ids is not None else None, r.logp.data_ptr() if r.logp is not None else None,
@@ -281,6 +195,13 @@ class Actors(object):
         del wts
         self.rows, self.joint_rows = r, jt
         return r.action
+
+    def train_forward(self, obs_n, packed):
+        """The forward Trainable runs, on the packed pair it hands to the backward: act_rows -> (M, per agent the live columns
+        [M, n_out_i] of the launch's logits, the input rows)."""
+        self.act_rows(obs_n, _packed=packed)
+        z = self.rows.logits
+        return int(obs_n[0].shape[0]), [z[i, :, :n].clone(memory_format=torch.contiguous_format) for i, n in enumerate(self.n_out)], list(obs_n)
 
     def reference(self, obs_n):
         """The fp64 torch forward pass, on whatever device the modules and obs_n are: per agent (move logits [B,5] or None,
@@ -444,7 +365,7 @@ class PolicyLoop(object):
         if replay is not None:
             self._replay_check(replay)
             replay._alloc()
-        if pi._frozen is None:
+        if pi.attached() is None:
             pi.freeze()
         g = torch.cuda.CUDAGraph()
         s = torch.cuda.Stream(device=w.device)

@@ -17,6 +17,7 @@ import os
 import torch
 
 from . import _abi
+from .netset import _actor_layers, fill_set, pack_layers
 
 
 class RandomRollout(object):
@@ -789,62 +790,10 @@ def _rollout_actions(env, moves, episode_len, seed, comm, cache, key):
 _POLICY_MODES = {"greedy": _abi.MPE_POLICY_GREEDY, "sample": _abi.MPE_POLICY_SAMPLE, "softmax": _abi.MPE_POLICY_SOFTMAX}
 
 
-def _actor_layers(module, n_out=_abi.MPE_ACTION_DIM, who="MlpPolicy"):
-    """nn.Sequential (or a lone nn.Linear) -> ([Linear, ...], activation name); refuses anything the kernel does not evaluate.
-    n_out: the width the last Linear layer must have; who: the class the refusals name (policy.Actors checks its modules here)."""
-    import torch.nn as nn
-    mods = [module] if isinstance(module, nn.Linear) else list(module.children()) if isinstance(module, nn.Sequential) else None
-    if mods is None:
-        raise _abi.MpeError(who + ": an actor is an nn.Sequential of Linear layers with ReLU / Tanh between them (got %s)"
-                            % type(module).__name__)
-    lins, acts = [], []
-    for k, m in enumerate(mods):
-        want_linear = k % 2 == 0
-        if want_linear and isinstance(m, nn.Linear):
-            lins.append(m)
-        elif not want_linear and isinstance(m, (nn.ReLU, nn.Tanh)):
-            acts.append(type(m).__name__.lower())
-        else:
-            raise _abi.MpeError(who + ": unsupported layer %d (%s): an actor alternates Linear and ReLU / Tanh and ends with a Linear"
-                                % (k, type(m).__name__))
-    if not lins or len(mods) % 2 == 0:
-        raise _abi.MpeError(who + ": an actor ends with a Linear layer")
-    if len(lins) > _abi.MPE_POLICY_MAX_LAYERS:
-        raise _abi.MpeError(who + ": %d Linear layers (at most %d)" % (len(lins), _abi.MPE_POLICY_MAX_LAYERS))
-    if len(set(acts)) > 1:
-        raise _abi.MpeError(who + ": one activation per actor (got %s)" % sorted(set(acts)))
-    for k, lin in enumerate(lins):
-        if lin.weight.dtype != torch.float32 or (lin.bias is not None and lin.bias.dtype != torch.float32):
-            raise _abi.MpeError(who + ": Linear layer %d is not float32" % k)
-        if k > 0 and lin.in_features != lins[k - 1].out_features:
-            raise _abi.MpeError(who + ": Linear layer %d takes %d inputs, layer %d gives %d"
-                                % (k, lin.in_features, k - 1, lins[k - 1].out_features))
-        if k + 1 < len(lins) and lin.out_features > _abi.MPE_POLICY_MAX_WIDTH:
-            raise _abi.MpeError(who + ": hidden width %d > %d" % (lin.out_features, _abi.MPE_POLICY_MAX_WIDTH))
-    if lins[-1].out_features != n_out:
-        raise _abi.MpeError(who + ": the last Linear layer gives %d outputs (need %d)" % (lins[-1].out_features, n_out))
-    return lins, (acts[0] if acts else "relu")
-
-
 def pack_actor(module):
-    """One actor in the packed layout of include/mpe_hip.h (MpePolicy): for each Linear layer l, W_l as [in_l][out_l'] (W_l[k][j] =
-    weight[j][k]) then bias[out_l'], with in_0 = the input width, in_l = 64 for l > 0, out_l' = 64 for a hidden layer and 8 for the
-    last, zero padding.  -> a float32 tensor on the module's device whose length is a multiple of 16."""
-    lins, _ = _actor_layers(module)
-    dev = lins[0].weight.device
-    parts = []
-    for k, lin in enumerate(lins):
-        n_in = lin.in_features if k == 0 else _abi.MPE_POLICY_MAX_WIDTH
-        n_out = 8 if k + 1 == len(lins) else _abi.MPE_POLICY_MAX_WIDTH
-        w = torch.zeros((n_in, n_out), dtype=torch.float32, device=dev)
-        w[:lin.in_features, :lin.out_features] = lin.weight.detach().t()
-        b = torch.zeros(n_out, dtype=torch.float32, device=dev)
-        if lin.bias is not None:
-            b[:lin.out_features] = lin.bias.detach()
-        parts += [w.reshape(-1), b]
-    flat = torch.cat(parts)
-    pad = (-flat.numel()) % 16
-    return torch.cat([flat, flat.new_zeros(pad)]) if pad else flat
+    """One actor in the packed layout of include/mpe_hip.h (MpePolicy; netset.layout with an 8-wide last layer) -> a float32 tensor
+    on the module's device whose length is a multiple of 16."""
+    return pack_layers(_actor_layers(module)[0], 8)
 
 
 class MlpPolicy(object):
@@ -877,22 +826,8 @@ class MlpPolicy(object):
         self._layers = [_actor_layers(m) for m in self.modules]      # (a module may have been edited since)
         self._check(obs_widths)
         pol = _abi.MpePolicy()
-        blobs, where, off = [], {}, 0
-        for i in range(len(obs_widths)):
-            m = self.actor(i)
-            if id(m) not in where:
-                blob = pack_actor(m).to(device)
-                where[id(m)] = off
-                blobs.append(blob)
-                off += blob.numel()
-            lins, act = _actor_layers(m)
-            pol.n_layers[i] = len(lins)
-            pol.width[i][0] = lins[0].in_features
-            for k, lin in enumerate(lins):
-                pol.width[i][k + 1] = lin.out_features
-            pol.activation[i] = _abi.MPE_POLICY_TANH if act == "tanh" else _abi.MPE_POLICY_RELU
-            pol.offset[i] = where[id(m)]
-        w = torch.cat(blobs).contiguous()
+        modules = [self.actor(i) for i in range(len(obs_widths))]
+        w = fill_set(pol, modules, [self._layers[0 if self.shared else i] for i in range(len(modules))], 8, device)
         pol.weights = w.data_ptr()
         pol.mode = _POLICY_MODES[mode]
         pol.seed = int(seed) & (2 ** 64 - 1)

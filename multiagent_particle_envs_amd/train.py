@@ -14,11 +14,11 @@ import torch
 
 from . import _abi
 from .learner import Critics
+from .netset import Cache, Generations, check_tensor, module_views
 from .onpolicy import Values
 from .policy import Actors
 
-_W, _LW = _abi.MPE_POLICY_MAX_WIDTH, _abi.MPE_ACTOR_MAX_OUT
-
+_module_views = module_views      # (the name this file had for it: existing importers keep working)
 
 class MlpGradResult(object):
     """What mlp_grad_tensors wrote: packed, one flat float32 buffer in the layout and at the offsets of the set's packed weights
@@ -31,25 +31,6 @@ def _kind(net, who):
     if not isinstance(net, (Actors, Values, Critics)):
         raise _abi.MpeError("%s: net is an Actors, a Values or a Critics (got %s)" % (who, type(net).__name__))
     return type(net).__name__
-
-
-def _module_views(net, flat):
-    """per distinct module [(weight view [out, in], bias view [out])] of a flat buffer in the packed layout"""
-    out, seen, at = [], set(), 0
-    for (lins, _), m in zip(net._check(), net.modules):
-        if id(m) in seen:
-            continue
-        seen.add(id(m))
-        views = []
-        for k, lin in enumerate(lins):
-            n_in = lin.in_features if k == 0 else _W
-            wide = _LW if k + 1 == len(lins) else _W
-            w = flat[at:at + n_in * wide].view(n_in, wide)[:lin.in_features, :lin.out_features].t()
-            b = flat[at + n_in * wide:at + n_in * wide + lin.out_features]
-            views.append((w, b))
-            at += (n_in + 1) * wide
-        out.append(views)
-    return out, at
 
 
 def mlp_grad_tensors(net, in_n, dout_n, out=None, packed=None):
@@ -73,18 +54,13 @@ def mlp_grad_tensors(net, in_n, dout_n, out=None, packed=None):
     if not torch.is_tensor(x0) or x0.dim() != 2:
         raise _abi.MpeError("%s: in_n[0] is a contiguous float32 [M, %d] tensor on a GPU" % (who, layers[0][0][0].in_features))
     M, dev = int(x0.shape[0]), x0.device
-
-    def chk(x, name, shapes):
-        if not torch.is_tensor(x) or x.dtype != torch.float32 or tuple(x.shape) not in shapes or not x.is_contiguous() or x.device != dev:
-            raise _abi.MpeError("%s: %s is a contiguous float32 %s tensor on in_n[0]'s device"
-                                % (who, name, " or ".join(str(list(s)) for s in shapes)))
     for i, (lins, _) in enumerate(layers):
         n = lins[-1].out_features
-        chk(in_n[i], "in_n[%d]" % i, [(M, lins[0].in_features)])
-        chk(dout_n[i], "dout_n[%d]" % i, [(M, n)] + ([(M,)] if n == 1 else []))
+        check_tensor(who, in_n[i], "in_n[%d]" % i, [(M, lins[0].in_features)], "in_n[0]'s device", dev)
+        check_tensor(who, dout_n[i], "dout_n[%d]" % i, [(M, n)] + ([(M,)] if n == 1 else []), "in_n[0]'s device", dev)
     if not x0.is_cuda:
         raise _abi.MpeError("%s: in_n[0] is on %s (the tensors live on a GPU: there is no CPU path)" % (who, dev))
-    wts, aset = packed if packed is not None else (net._frozen if net._frozen is not None else net.pack(dev))
+    wts, aset = packed if packed is not None else net.packed(dev)
     n = _abi.lib().mpe_mlp_grad_work(C.byref(aset), M)      # (host only: the set and size checks)
     if n < 0:
         _abi.check(int(n), "mpe_mlp_grad_work")
@@ -93,16 +69,14 @@ def mlp_grad_tensors(net, in_n, dout_n, out=None, packed=None):
         if not isinstance(out, MlpGradResult) or out.shape != shape or out.packed.device != dev:
             raise _abi.MpeError("%s: out is an MlpGradResult of the same net and M = %d (what an earlier call returned)" % (who, M))
     else:
-        cache = net.__dict__.setdefault("_mlp_grad", {})
-        out = cache.get(shape)
-        if out is None:
-            if len(cache) >= 16:
-                cache.clear()
-            out = cache[shape] = MlpGradResult()
+        def make():
+            out = MlpGradResult()
             out.M, out.shape = M, shape
             out.packed = torch.zeros((shape[1],), dtype=torch.float32, device=dev)
             out.work = torch.empty((max(shape[2], 1),), dtype=torch.float32, device=dev)
-            out.modules, _ = _module_views(net, out.packed)
+            out.modules, _ = module_views(net, out.packed)
+            return out
+        out = net.__dict__.setdefault("_mlp_grad", Cache()).get(shape, make)
     ip = (C.c_void_p * A)(*[t.data_ptr() for t in in_n])
     dp = (C.c_void_p * A)(*[t.data_ptr() for t in dout_n])
     _abi.check(_abi.lib().mpe_mlp_grad(C.byref(aset), ip, dp, M, out.packed.data_ptr(), out.work.data_ptr(), _abi.raw_stream(dev)),
@@ -117,30 +91,9 @@ class _TrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, owner, inputs, *params):
-        net, dev = owner.net, owner.net.world.device
-        saved = net._frozen
-        packed = saved if saved is not None else net.pack(dev)
-        net._frozen = packed      # (the launch and the backward read ONE packed copy)
-        try:
-            if isinstance(net, Actors):
-                net.act_rows(inputs)
-                M, z = int(inputs[0].shape[0]), net.rows.logits
-                outs = [z[i, :, :n].clone(memory_format=torch.contiguous_format) for i, n in enumerate(net.n_out)]
-                in_n = list(inputs)
-            elif isinstance(net, Values):
-                v = net.v(inputs)
-                M = int(v.shape[1])
-                outs = [v[i].clone() for i in range(net.A)]
-                in_n = [net._cat[M]] * net.A if net.centralised else list(inputs)
-            else:
-                q = net.q(inputs)
-                M = int(q.shape[1])
-                outs = [q[i].clone() for i in range(net.A)]
-                in_n = [inputs] * net.A
-        finally:
-            net._frozen = saved
-        owner._generation[M] = owner._generation.get(M, 0) + 1
-        ctx.owner, ctx.in_n, ctx.packed, ctx.key = owner, in_n, packed, (M, owner._generation[M])
+        packed = owner.net.packed()      # (the launch and the backward read ONE packed copy)
+        M, outs, in_n = owner.net.train_forward(inputs, packed)
+        ctx.owner, ctx.in_n, ctx.packed, ctx.key = owner, in_n, packed, (M, owner._generation.next(M))
         ctx.shapes = [tuple(o.shape) for o in outs]
         return tuple(outs)
 
@@ -148,7 +101,7 @@ class _TrainFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, *grad_outputs):
         owner, (M, generation) = ctx.owner, ctx.key
-        if owner._generation.get(M) != generation:
+        if owner._generation.stale(M, generation):
             raise _abi.MpeError("Trainable: backward() behind a later forward with the same M (the set's outputs and the gradient's "
                                 "buffers are cached per M: call backward() before the next forward)")
         dev = owner.net.world.device
@@ -156,7 +109,7 @@ class _TrainFn(torch.autograd.Function):
         res = mlp_grad_tensors(owner.net, ctx.in_n, dout, packed=ctx.packed)
         owner.last_grad = res      # (what DeviceAdam.step() reads in place of the parameters' .grad)
         flat = res.packed.clone()      # out of place: the cached buffer is rewritten by the next backward of the same M
-        views, _ = _module_views(owner.net, flat)
+        views, _ = module_views(owner.net, flat)
         grads = []
         for mv, lins in zip(views, owner._lins):
             for (w, b), lin in zip(mv, lins):
@@ -179,13 +132,10 @@ class Trainable(object):
         if isinstance(net, Actors) and not net._want[2]:
             raise _abi.MpeError("Trainable: the Actors were built without logits=True (the forward hands autograd the launch's logits)")
         self.net = net
-        self._generation = {}
+        self._generation = Generations()
         self.last_grad = None      # the MlpGradResult of the last backward(); DeviceAdam.step() consumes it
-        self._lins, self._params, seen = [], [], set()
-        for (lins, _), m in zip(net._check(), net.modules):
-            if id(m) in seen:
-                continue
-            seen.add(id(m))
+        self._lins, self._params = [], []
+        for _, lins in net.distinct():
             self._lins.append(lins)
             for lin in lins:
                 self._params.append(lin.weight)

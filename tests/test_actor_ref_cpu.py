@@ -107,13 +107,16 @@ def test_case_table_covers_what_it_says():
 def test_pack_is_pack_actor16(width, n_layers):
     rs = np.random.RandomState(width * 4 + n_layers)
     hidden = {1: (), 2: (width,), 3: (width, 64 if width % 2 else 20)}[n_layers]
-    D = width if n_layers == 1 else 18
-    for n_out in (5, 16, 1):
+    for D, n_out in [(width if n_layers == 1 else 18, n) for n in (5, 16, 1)] + [(1, 5), (256, 16)]:      # + the input width's two ends
         layers = R.make_layers(rs, D, hidden, n_out)
         want = policy.pack_actor16(R.as_module(layers, R.TANH), n_out).numpy()
         got = R.pack(layers)
         assert got.dtype == np.float32 and got.size % 16 == 0
         assert got.tobytes() == want.tobytes()
+        # a Linear layer built with bias=False packs what a zero bias packs
+        m = R.as_module(layers, R.TANH)
+        m[0].bias = None
+        assert R.pack([(layers[0][0], np.zeros_like(layers[0][1]))] + layers[1:]).tobytes() == policy.pack_actor16(m, n_out).numpy().tobytes()
     if n_layers == 3:      # the narrow layer second
         layers = R.make_layers(rs, D, (64, width), 5)
         assert R.pack(layers).tobytes() == policy.pack_actor16(R.as_module(layers, R.RELU), 5).numpy().tobytes()

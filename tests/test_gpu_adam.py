@@ -20,7 +20,8 @@ from multiagent_particle_envs_amd import _abi
 from multiagent_particle_envs_amd.onpolicy import Minibatches, PpoLoss, Values, gae, ppo_loss_tensors
 from multiagent_particle_envs_amd.optim import DeviceAdam
 from multiagent_particle_envs_amd.policy import Actors, PolicyLoop
-from multiagent_particle_envs_amd.train import MlpGradResult, Trainable, _module_views, mlp_grad_tensors
+from multiagent_particle_envs_amd.netset import module_views as _module_views
+from multiagent_particle_envs_amd.train import MlpGradResult, Trainable, mlp_grad_tensors
 
 import _adam_ref as R
 import _mlp_grad_ref as G

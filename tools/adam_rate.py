@@ -43,7 +43,8 @@ from multiagent_particle_envs_amd import _abi  # noqa: E402
 from multiagent_particle_envs_amd.onpolicy import Minibatches, PpoLoss, Values, gae, ppo_loss_tensors  # noqa: E402
 from multiagent_particle_envs_amd.optim import DeviceAdam  # noqa: E402
 from multiagent_particle_envs_amd.policy import Actors, PolicyLoop, pack_actor16  # noqa: E402
-from multiagent_particle_envs_amd.train import MlpGradResult, Trainable, _module_views, mlp_grad_tensors  # noqa: E402
+from multiagent_particle_envs_amd.netset import module_views as _module_views  # noqa: E402
+from multiagent_particle_envs_amd.train import MlpGradResult, Trainable, mlp_grad_tensors  # noqa: E402
 from replay_rate import graph_of, rounds  # noqa: E402
 
 T_STEPS, PARTS, CLIP = 25, 4, 0.5
