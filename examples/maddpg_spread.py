@@ -1,11 +1,17 @@
 """A MADDPG-style learner on simple_spread, wired from the device-side pieces.
 
-    python examples/maddpg_spread.py [--worlds 1024] [--batch 1024] [--updates 200]
+    python examples/maddpg_spread.py [--worlds 1024] [--batch 1024] [--updates 200] [--fused-nets]
 
 The closed loop (PolicyLoop) fills a device replay ring with one launch per step; a minibatch with 3-step returns is one launch
 (ReplayBuffer.sample); the no-grad half of the update -- target actors on the next observations, target critics on the joint rows,
 the TD target y -- is two launches (TdTargets.compute).  The critic loss, the actor loss and the soft updates are plain torch
 autograd.  One JSON line per update.  A readable wiring, not a benchmark.
+
+--fused-nets: the networks' forward and backward passes run on the device kernels too (Trainable).  The critic loss goes through
+Trainable(Critics); the actor loss -Q_i(joint row with agent i's action columns replaced by softmax(mu_i(obs_i))) through
+Trainable(Actors, logits=True), torch's softmax and column write, and Trainable(Critics, input_grad=True, weight_grad=False, cols=...):
+the critics are a constant of it, and what it needs of them is their gradient with respect to those 5 input columns (one launch).
+The optimisers, the soft updates and the softmax Jacobian (a [M, 5] op) stay in torch.
 """
 import argparse
 import copy
@@ -18,7 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from multiagent_particle_envs_amd import Actors, Critics, PolicyLoop, ReplayBuffer, TdTargets, make_env  # noqa: E402
+from multiagent_particle_envs_amd import Actors, Critics, PolicyLoop, ReplayBuffer, TdTargets, Trainable, make_env  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--worlds", type=int, default=1024)
@@ -27,6 +33,7 @@ ap.add_argument("--updates", type=int, default=200)
 ap.add_argument("--steps-per-update", type=int, default=5)
 ap.add_argument("--gamma", type=float, default=0.95)
 ap.add_argument("--tau", type=float, default=0.01)
+ap.add_argument("--fused-nets", action="store_true", help="forward and backward passes of the actors and critics on the device kernels")
 args = ap.parse_args()
 EPISODE, N_STEP = 25, 3
 
@@ -49,6 +56,27 @@ td = TdTargets(target_actors, Critics(env, q_targ))       # both re-read their m
 opt_q = torch.optim.Adam([p for m in qs for p in m.parameters()], lr=1e-3)
 opt_mu = torch.optim.Adam([p for m in mu for p in m.parameters()], lr=1e-3)
 col = target_actors.col_move                              # agent i's action columns of a joint row
+if args.fused_nets:
+    q_train = Trainable(Critics(env, qs))                 # critic loss: the weights' gradients
+    pi_train = Trainable(Actors(env, mu, mode="softmax", logits=True))
+    q_const = Trainable(Critics(env, qs), input_grad=True, weight_grad=False, cols=[(c, 5) for c in col])      # actor loss: dQ_i / d(action columns)
+
+
+def critic_values(joint):
+    """Q_i of every agent on the batch's joint rows -> A tensors [M]"""
+    return q_train(joint) if args.fused_nets else [qs[i](joint)[:, 0] for i in range(A)]
+
+
+def actor_values(batch):
+    """Q_i(joint with agent i's own action columns replaced by its current policy's, the others' as played) -> A tensors [M]"""
+    logits = pi_train(batch.obs_n) if args.fused_nets else [mu[i](batch.obs_n[i]) for i in range(A)]
+    joints = []
+    for i in range(A):
+        joint = batch.joint.clone()
+        joint[:, col[i]:col[i] + 5] = F.softmax(logits[i], dim=1)
+        joints.append(joint)
+    return q_const(joints) if args.fused_nets else [qs[i](joints[i])[:, 0] for i in range(A)]
+
 
 loop.run(EPISODE, record=False, replay=buf)               # something to sample from
 for update in range(args.updates):
@@ -56,16 +84,15 @@ for update in range(args.updates):
     batch = buf.sample(args.batch, joint=True, n_step=N_STEP, gamma=args.gamma, episode_len=EPISODE)
     y = td.compute(batch)                                 # [A, M], two launches, no gradient
     # critics: Q_i(obs, actions) -> y_i
-    critic_loss = sum(F.mse_loss(qs[i](batch.joint)[:, 0], y[i]) for i in range(A))
+    q = critic_values(batch.joint)
+    critic_loss = sum(F.mse_loss(q[i], y[i]) for i in range(A))
     opt_q.zero_grad()
     critic_loss.backward()
     opt_q.step()
     # actors: agent i's own action columns replaced by its current policy's, the others' as played
     actor_loss = 0.0
-    for i in range(A):
-        joint = batch.joint.clone()
-        joint[:, col[i]:col[i] + 5] = F.softmax(mu[i](batch.obs_n[i]), dim=1)
-        actor_loss = actor_loss - qs[i](joint).mean()
+    for q_i in actor_values(batch):
+        actor_loss = actor_loss - q_i.mean()
     opt_mu.zero_grad()
     actor_loss.backward()
     opt_mu.step()

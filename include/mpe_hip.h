@@ -615,11 +615,45 @@ int mpe_ppo_loss(const MpePpoLoss *cfg, const float *const *logits_ptrs, const f
  * shapes (layers, widths, activation); two agents' blocks overlapping at different offsets; M < 0; M >= 2^31.  mpe_mlp_grad then:
  * set->weights NULL or not 16-byte aligned; in_ptrs, dout_ptrs, grad or work NULL; a NULL in_ptrs[i] or dout_ptrs[i]; a pointer that
  * is not 4-byte aligned.  M == 0 writes an all-zero grad (one launch) and succeeds.
- * Out of scope: dL/din (MADDPG's actor loss through the critic needs it), bf16.  The optimiser step that consumes grad in this
- * layout, in place on set->weights, is mpe_adam_step below.                                                                     */
+ * Out of scope: bf16.  dL/din is mpe_mlp_dinput below.  The optimiser step that consumes grad in this layout, in place on
+ * set->weights, is mpe_adam_step below.                                                                                          */
 int64_t mpe_mlp_grad_work(const MpeActorSet *set, int64_t M);
 int mpe_mlp_grad(const MpeActorSet *set, const float *const *in_ptrs, const float *const *dout_ptrs, int64_t M, float *grad,
                  float *work, void *stream);
+
+/* ---- MLP input gradients: dL/din over a window of input columns in ONE launch (csrc/mpe_mlp_dinput.hip) ---------------------------
+ * What MADDPG's actor loss needs of a critic: -Q_i(joint row with agent i's action columns replaced by its actor's output) reaches the
+ * actor through the critic's gradient with respect to those columns.  set, in_ptrs, dout_ptrs, M: as for mpe_mlp_grad.
+ * THE MLP INPUT GRADIENT RULE.  h_l and delta_l are THE MLP GRADIENT RULE's -- h_l recomputed from in with the
+ *   accurate tanhf, the inputs in ascending order, two per MFMA step; delta_l propagated back from delta_(L-1) = dout -- with ONE
+ *   difference: a hidden unit's accumulator starts at 0 and its bias is added LAST, rounded once (additions onto a bias of +-3
+ *   round at ulp(3), and 1 - h * h of a saturated unit multiplies that error a hundredfold: DESIGN.md 2.21).  delta_0 is the delta
+ *   behind layer 0's activation (for a one-layer net delta_0 = dout).  Agent i has a window col0_i, ncol_i with 0 <= col0_i, 1 <= ncol_i,
+ *   col0_i + ncol_i <= D_i.  For every row < M and every k in the window
+ *     din[row][k - col0_i] = sum_j delta_0[row][j] * W_0[k][j]
+ *   j ascending over layer 0's packed outputs (64, or 16 for a one-layer net; packed padding weights are 0), two j per
+ *   v_mfma_f32_32x32x2_f32 step.  EVERY sum of this rule -- a hidden unit's pre-activation, a delta step, din -- is four float32
+ *   chains from 0: MFMA step s goes to chain s mod 4, each chain in ascending order, folded as (c0 + c1) + (c2 + c3) (THE MLP
+ *   GRADIENT RULE's device for dW; one chain per sum missed the parity bound on windows of a few columns: DESIGN.md 2.21).
+ * A row's result depends on that row alone: the same bit pattern at any M, at any position in the batch and under any cut of the
+ * rows into workgroups (the cut is not part of the rule).  No atomics, no host synchronisation, no workspace.
+ * Output.  din_ptrs[i] (a HOST array of A device pointers): row r's window is written at floats r * ld_i .. r * ld_i + ncol_i - 1,
+ * ld_i >= ncol_i.  Nothing else is written: no float of a row >= M, no float between ncol_i and ld_i.  Stores are 16 bytes wide
+ * where din_ptrs[i] is 16-byte aligned and ld_i is a multiple of 4, else 4 bytes.  din may not overlap in, dout, the weights or
+ * another agent's din: this is NOT checked.
+ * Refused by name before any launch, in this order: every set check of mpe_mlp_grad, in its order (set NULL .. M >= 2^31); win NULL;
+ * per agent: col0 < 0, ncol < 1, col0 + ncol > D_i, ld < ncol; set->weights NULL or not 16-byte aligned; in_ptrs, dout_ptrs or
+ * din_ptrs NULL; a NULL in_ptrs[i], dout_ptrs[i] or din_ptrs[i]; a pointer that is not 4-byte aligned; M * ld_i >= 2^40 floats (the
+ * store's index arithmetic is 64-bit; the bound keeps a row's byte offset far below 2^63 and is 4 TB of output per agent).
+ * M == 0 returns 0 without a launch.
+ * Out of scope: the softmax Jacobian between an actor's logits and the window (a [M, 5] op, left to the caller), bf16.            */
+typedef struct MpeMlpDinput {
+  int32_t col0[MPE_ACTOR_MAX_AGENTS], ncol[MPE_ACTOR_MAX_AGENTS];
+  int64_t ld[MPE_ACTOR_MAX_AGENTS];
+} MpeMlpDinput;
+size_t mpe_sizeof_mlp_dinput(void);
+int mpe_mlp_dinput(const MpeActorSet *set, const MpeMlpDinput *win, const float *const *in_ptrs, const float *const *dout_ptrs,
+                   int64_t M, float *const *din_ptrs, void *stream);
 
 /* ---- the optimiser step: Adam / AdamW with global-norm clipping on the packed buffers, in place, in TWO launches (csrc/mpe_adam.hip) --
  * What stands between mpe_mlp_grad and the next forward: up to MPE_ADAM_MAX_SETS packed buffers -- each an MpeActorSet's `weights`,

@@ -10,7 +10,7 @@ from .policy import Actors, PolicyLoop  # noqa: F401
 from .learner import Critics, TdTargets  # noqa: F401
 from .onpolicy import Values, GaeResult, gae, gae_tensors, adv_stats, Minibatches, OnPolicyBatch  # noqa: F401
 from .onpolicy import PpoLoss, PpoLossResult, ppo_loss_tensors  # noqa: F401
-from .train import Trainable, MlpGradResult, mlp_grad_tensors  # noqa: F401
+from .train import Trainable, MlpGradResult, mlp_grad_tensors, mlp_dinput_tensors  # noqa: F401
 from .optim import DeviceAdam  # noqa: F401
 from .replay import (ReplayBuffer, ReplayBatch, NStepReplayBatch, PrioritizedReplayBuffer, PrioritizedReplayBatch,  # noqa: F401
                      PrioritizedNStepReplayBatch)
@@ -18,6 +18,6 @@ from .replay import (ReplayBuffer, ReplayBatch, NStepReplayBatch, PrioritizedRep
 __all__ = ["make_env", "MultiAgentEnv", "BatchMultiAgentEnv", "GraphedStep", "BaseScenario", "core", "scenarios", "MlpPolicy", "PolicyRollout",
            "PolicyTrajectory", "Actors", "PolicyLoop", "Critics", "TdTargets", "Values", "GaeResult", "gae", "gae_tensors",
            "adv_stats", "Minibatches", "OnPolicyBatch", "PpoLoss", "PpoLossResult", "ppo_loss_tensors",
-           "Trainable", "MlpGradResult", "mlp_grad_tensors", "DeviceAdam",
+           "Trainable", "MlpGradResult", "mlp_grad_tensors", "mlp_dinput_tensors", "DeviceAdam",
            "ReplayBuffer", "ReplayBatch",
            "PrioritizedReplayBuffer", "PrioritizedReplayBatch", "NStepReplayBatch", "PrioritizedNStepReplayBatch"]

@@ -121,6 +121,10 @@ class MpePpoLoss(C.Structure):         # include/mpe_hip.h: the heads and scalar
                 ("clip", C.c_float), ("value_clip", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float)]
 
 
+class MpeMlpDinput(C.Structure):       # include/mpe_hip.h: per agent the window of input columns and the row stride of mpe_mlp_dinput's output
+    _fields_ = [("col0", C.c_int32 * 16), ("ncol", C.c_int32 * 16), ("ld", C.c_int64 * 16)]
+
+
 class MpeReplay(C.Structure):          # include/mpe_hip.h: the replay ring of mpe_replay_push / mpe_replay_sample
     _fields_ = [("n_agents", C.c_int32), ("dim_c", C.c_int32), ("B", C.c_int64), ("S", C.c_int64),
                 ("obs_width", C.c_int32 * MPE_REPLAY_MAX_AGENTS), ("movable", C.c_uint8 * MPE_REPLAY_MAX_AGENTS),
@@ -259,6 +263,9 @@ EXPORTS = {
     "mpe_mlp_grad_work": (C.c_int64, [C.POINTER(MpeActorSet), C.c_int64]),
     "mpe_mlp_grad": (C.c_int, [C.POINTER(MpeActorSet), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int64, C.c_void_p, C.c_void_p,
                                C.c_void_p]),
+    "mpe_sizeof_mlp_dinput": (C.c_size_t, []),
+    "mpe_mlp_dinput": (C.c_int, [C.POINTER(MpeActorSet), C.POINTER(MpeMlpDinput), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int64,
+                                 C.POINTER(C.c_void_p), C.c_void_p]),
     "mpe_sizeof_adam": (C.c_size_t, []),
     "mpe_adam_work": (C.c_int64, [C.POINTER(MpeAdam)]),
     "mpe_adam_step": (C.c_int, [C.POINTER(MpeAdam), C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -317,6 +324,7 @@ def lib():
             handle.mpe_sizeof_onpolicy_traj() != C.sizeof(MpeOnPolicyTraj) or \
             handle.mpe_sizeof_ppo_loss() != C.sizeof(MpePpoLoss) or \
             handle.mpe_sizeof_adam() != C.sizeof(MpeAdam) or \
+            handle.mpe_sizeof_mlp_dinput() != C.sizeof(MpeMlpDinput) or \
             handle.mpe_sizeof_replay_nstep() != C.sizeof(MpeReplayNStep):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")
     _lib = handle

@@ -1658,6 +1658,51 @@ int mpe_mlp_grad(const MpeActorSet *s, const float *const *in_ptrs, const float 
   return hip_result(mpe::launch_mlp_grad(a, static_cast<hipStream_t>(stream)), what);
 }
 
+// ---- the MLP input gradients (mpe_mlp_dinput.hip) ---------------------------------------------------------------------------------
+size_t mpe_sizeof_mlp_dinput(void) { return sizeof(MpeMlpDinput); }
+int mpe_mlp_dinput(const MpeActorSet *s, const MpeMlpDinput *win, const float *const *in_ptrs, const float *const *dout_ptrs, int64_t M,
+                   float *const *din_ptrs, void *stream) {
+  const char *what = "mpe_mlp_dinput";
+  mpe::MlpGradArgs g;      // (the set checks are mpe_mlp_grad's; its workspace offsets are not used here)
+  if (int rc = check_mlp_grad(s, M, what, g)) return rc;
+  if (!win) return fail(MPE_EINVAL, "%s: win is NULL", what);
+  mpe::MlpDinputArgs a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  a.A = g.A, a.M = g.M;
+  for (int i = 0; i < a.A; ++i) {
+    const int D = g.width[i][0];
+    if (win->col0[i] < 0) return fail(MPE_EINVAL, "%s: agent %d: col0 = %d (need >= 0)", what, i, win->col0[i]);
+    if (win->ncol[i] < 1) return fail(MPE_EINVAL, "%s: agent %d: ncol = %d (need >= 1)", what, i, win->ncol[i]);
+    if (win->ncol[i] > D - win->col0[i])
+      return fail(MPE_EINVAL, "%s: agent %d: the window of %d columns from %d ends beyond the input's %d", what, i, win->ncol[i], win->col0[i], D);
+    if (win->ld[i] < win->ncol[i])
+      return fail(MPE_EINVAL, "%s: agent %d: ld = %lld (need >= ncol = %d)", what, i, (long long)win->ld[i], win->ncol[i]);
+    a.col0[i] = (int16_t)win->col0[i], a.ncol[i] = (int16_t)win->ncol[i], a.ld[i] = win->ld[i];
+    a.off[i] = g.off[i], a.nl[i] = g.nl[i], a.act[i] = g.act[i];
+    std::memcpy(a.width[i], g.width[i], sizeof(a.width[i]));
+  }
+  if (!s->weights || ((uintptr_t)s->weights & 15)) return fail(MPE_EINVAL, "%s: set->weights is NULL or not 16-byte aligned", what);
+  const struct { const void *p; const char *name; } need[] = {{in_ptrs, "in_ptrs"}, {dout_ptrs, "dout_ptrs"}, {din_ptrs, "din_ptrs"}};
+  for (const auto &f : need)
+    if (!f.p) return fail(MPE_EINVAL, "%s: %s is NULL", what, f.name);
+  uintptr_t f4 = 0;
+  for (int i = 0; i < a.A; ++i) {
+    if (!in_ptrs[i]) return fail(MPE_EINVAL, "%s: in_ptrs[%d] is NULL", what, i);
+    if (!dout_ptrs[i]) return fail(MPE_EINVAL, "%s: dout_ptrs[%d] is NULL", what, i);
+    if (!din_ptrs[i]) return fail(MPE_EINVAL, "%s: din_ptrs[%d] is NULL", what, i);
+    f4 |= (uintptr_t)in_ptrs[i] | (uintptr_t)dout_ptrs[i] | (uintptr_t)din_ptrs[i];
+    a.in[i] = in_ptrs[i], a.dout[i] = dout_ptrs[i], a.din[i] = din_ptrs[i];
+    a.vec[i] = mpe::md_vec((uintptr_t)din_ptrs[i], a.ld[i]);
+  }
+  if (f4 & 3) return fail(MPE_EINVAL, "%s: every pointer must be 4-byte aligned", what);
+  for (int i = 0; i < a.A; ++i)      // (M < 2^31, so the product cannot overflow below)
+    if (a.ld[i] >= (1ll << 40) || M * a.ld[i] >= (1ll << 40))
+      return fail(MPE_EINVAL, "%s: agent %d: M * ld = %lld * %lld floats (need M * ld < 2^40)", what, i, (long long)M, (long long)a.ld[i]);
+  if (M == 0) return 0;
+  a.w = s->weights;
+  return hip_result(mpe::launch_mlp_dinput(a, static_cast<hipStream_t>(stream)), what);
+}
+
 // ---- the optimiser step (mpe_adam.hip) ------------------------------------------------------------------------------------------
 size_t mpe_sizeof_adam(void) { return sizeof(MpeAdam); }
 // the checks mpe_adam_step and mpe_adam_work share, in the header's order; fills everything of the launch's arguments but state and work

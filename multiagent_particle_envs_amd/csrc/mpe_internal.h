@@ -6,6 +6,7 @@
 #include "mpe_onpolicy.h"
 #include "mpe_ppo_loss.h"
 #include "mpe_mlp_grad.h"
+#include "mpe_mlp_dinput.h"
 #include "mpe_adam.h"
 
 namespace mpe {
@@ -164,6 +165,8 @@ int launch_ppo_loss(const PpoArgs &a, hipStream_t stream);                  // t
 static_assert(kMgMaxAgents == MPE_ACTOR_MAX_AGENTS && kMgHW == MPE_POLICY_MAX_WIDTH && kMgLW == MPE_ACTOR_MAX_OUT &&
               kMgMaxIn == MPE_ACTOR_MAX_INPUT && MPE_POLICY_MAX_LAYERS == 3, "mpe_mlp_grad.h restates them");
 int launch_mlp_grad(const MlpGradArgs &a, hipStream_t stream);              // two launches: the chunks' partials, then the ordered final pass
+// the MLP input gradients (mpe_mlp_dinput.hip; MlpDinputArgs and the indices of P8 and the store: mpe_mlp_dinput.h), checked by the caller
+int launch_mlp_dinput(const MlpDinputArgs &a, hipStream_t stream);          // one launch, M > 0
 
 // the optimiser step (mpe_adam.hip; AdamArgs, the tiling and the arithmetic: mpe_adam.h), checked by the caller
 static_assert(kAdamMaxSets == MPE_ADAM_MAX_SETS && kAdamTile == MPE_ADAM_TILE && kAdamMaxPartials == MPE_ADAM_MAX_PARTIALS &&

@@ -7,23 +7,11 @@
 // barriers and the MFMA.  The phases P0..P7 are described there.
 #include "mpe_device.h"
 #include "mpe_internal.h"
+#include "mpe_mlp_device.h"      // mfma, at / at64, delta_in_place: shared with mpe_mlp_dinput.hip
 
 namespace mpe {
 namespace {
 
-typedef float f16v __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ f16v mfma(float a, float b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float at(const float *p, int idx) { return idx >= 0 ? p[idx] : 0.f; }
-__device__ __forceinline__ float at64(const float *__restrict__ p, int64_t idx) { return idx >= 0 ? p[idx] : 0.f; }
-
-// a delta step (P4, P6): the tile's floats this lane read as h become (acc) * act'(h), in place
-__device__ __forceinline__ void delta_in_place(float *T, const f16v &acc, int i, int h, int wt, int m, bool tnh) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int o = mg_fwd_out(r, i, h, wt, m);
-    T[o] = mg_dact(acc[r], T[o], tnh);
-  }
-}
 // one group's 32 steps of a dW tile: four interleaved chains from 0, folded pairwise, added to the chunk's accumulator
 template <class FA, class FB>
 __device__ __forceinline__ void group_dw(f16v &acc, FA a_of, FB b_of) {

@@ -42,31 +42,41 @@ class Critics(NetSet):
         return "Critics: agent %d's critic takes %d inputs, the joint row has %d" % (i, n, D)
 
     def _rows_check(self, rows, who):
-        if not torch.is_tensor(rows) or rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != self.joint_width or \
-                not rows.is_contiguous() or rows.device != self.world.device:
-            raise _abi.MpeError("%s: rows is a contiguous float32 [M, %d] tensor on the env's device" % (who, self.joint_width))
-        return int(rows.shape[0])
+        """rows: ONE tensor every critic reads, or a list of A tensors (agent i's critic reads rows[i]) -> (M, the A tensors)"""
+        many = isinstance(rows, (list, tuple))
+        each = list(rows) if many else [rows]
+        if many and len(each) != self.A:
+            raise _abi.MpeError("%s: rows is one tensor every critic reads, or a list of %d tensors, one per agent (got %d)"
+                                % (who, self.A, len(each)))
+        for i, r in enumerate(each):
+            if not torch.is_tensor(r) or r.dtype != torch.float32 or r.dim() != 2 or r.shape[1] != self.joint_width or \
+                    not r.is_contiguous() or r.device != self.world.device or r.shape[0] != each[0].shape[0]:
+                raise _abi.MpeError("%s: rows%s is a contiguous float32 [M, %d] tensor on the env's device"
+                                    % (who, "[%d]" % i if many else "", self.joint_width))
+        return int(each[0].shape[0]), each if many else each * self.A
 
-    def _launch(self, rows, M, td=None, _packed=None):
-        """The one launch: q [A, M] (and y [A, M] when td, an MpeTdTarget, is given) -> (q, y); tensors cached per M."""
+    def _launch(self, rows_n, M, td=None, _packed=None):
+        """The one launch: q [A, M] (and y [A, M] when td, an MpeTdTarget, is given) -> (q, y); tensors cached per M.  rows_n[i]:
+        the rows agent i's critic reads."""
         q, y = self._out.get(M, lambda: tuple(torch.zeros((self.A, M), dtype=torch.float32, device=self.world.device) for _ in range(2)))
         wts, aset = _packed if _packed is not None else self.packed()
-        ptrs = (C.c_void_p * self.A)(*([rows.data_ptr()] * self.A))
+        ptrs = (C.c_void_p * self.A)(*[r.data_ptr() for r in rows_n])
         _abi.check(_abi.lib().mpe_critic_q(C.byref(aset), ptrs, M, q.data_ptr(), C.byref(td) if td is not None else None,
                                            y.data_ptr() if td is not None else None, _abi.raw_stream(self.world.device)), "mpe_critic_q")
         del wts
         return q, (y if td is not None else None)
 
     def q(self, rows):
-        """One launch: every agent's critic on the joint rows [M, joint_width] -> q [A, M] (this object's tensor per M)."""
-        M = self._rows_check(rows, "Critics.q")
-        return self._launch(rows, M)[0]
+        """One launch: every agent's critic on the joint rows [M, joint_width] -- ONE tensor, or a list of A (agent i's critic reads
+        rows[i]: MADDPG's actor loss gives every critic its own rows) -> q [A, M] (this object's tensor per M)."""
+        M, rows_n = self._rows_check(rows, "Critics.q")
+        return self._launch(rows_n, M)[0]
 
     def train_forward(self, rows, packed):
         """The forward Trainable runs, on the packed pair it hands to the backward: q -> (M, q[i] [M] per agent, the input rows)."""
-        M = self._rows_check(rows, "Critics.q")
-        q = self._launch(rows, M, _packed=packed)[0]
-        return M, [q[i].clone() for i in range(self.A)], [rows] * self.A
+        M, rows_n = self._rows_check(rows, "Critics.q")
+        q = self._launch(rows_n, M, _packed=packed)[0]
+        return M, [q[i].clone() for i in range(self.A)], rows_n
 
     def reference(self, rows):
         """The fp64 torch forward pass, on whatever device the modules and rows are -> [A, M] float64."""
@@ -123,5 +133,5 @@ class TdTargets(object):
             self.t += 1
         self.actors.act_rows(batch.next_obs_n, t, joint=True)
         self.joint_next_act = self.actors.joint_rows
-        self.q_next, self.y = self.critics._launch(self.joint_next_act, M, td)
+        self.q_next, self.y = self.critics._launch([self.joint_next_act] * self.critics.A, M, td)
         return self.y
