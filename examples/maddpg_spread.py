@@ -1,6 +1,6 @@
 """A MADDPG-style learner on simple_spread, wired from the device-side pieces.
 
-    python examples/maddpg_spread.py [--worlds 1024] [--batch 1024] [--updates 200] [--fused-nets]
+    python examples/maddpg_spread.py [--worlds 1024] [--batch 1024] [--updates 200] [--fused-nets | --device-update]
 
 The closed loop (PolicyLoop) fills a device replay ring with one launch per step; a minibatch with 3-step returns is one launch
 (ReplayBuffer.sample); the no-grad half of the update -- target actors on the next observations, target critics on the joint rows,
@@ -12,6 +12,12 @@ Trainable(Critics); the actor loss -Q_i(joint row with agent i's action columns 
 Trainable(Actors, logits=True), torch's softmax and column write, and Trainable(Critics, input_grad=True, weight_grad=False, cols=...):
 the critics are a constant of it, and what it needs of them is their gradient with respect to those 5 input columns (one launch).
 The optimisers, the soft updates and the softmax Jacobian (a [M, 5] op) stay in torch.
+
+--device-update (implies --fused-nets): the rest of the update leaves torch too.  The critic loss is TdLoss
+(mpe_td_loss), the actor loss ActorLoss (mpe_policy_rows, the critics, their input gradient, mpe_policy_rows_grad); two DeviceAdam
+hold the critics' and the actors' packed weights as the master copies, the sampling Actors joins the actors' buffer through share(),
+and the soft updates are one launch on the packed buffers (PolyakTargets).  The modules' own parameters are stale until
+write_back().
 """
 import argparse
 import copy
@@ -24,7 +30,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from multiagent_particle_envs_amd import Actors, Critics, PolicyLoop, ReplayBuffer, TdTargets, Trainable, make_env  # noqa: E402
+from multiagent_particle_envs_amd import (ActorLoss, Actors, Critics, DeviceAdam, PolicyLoop, PolyakTargets, ReplayBuffer, TdLoss,  # noqa: E402
+                                          TdTargets, Trainable, make_env)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--worlds", type=int, default=1024)
@@ -34,7 +41,9 @@ ap.add_argument("--steps-per-update", type=int, default=5)
 ap.add_argument("--gamma", type=float, default=0.95)
 ap.add_argument("--tau", type=float, default=0.01)
 ap.add_argument("--fused-nets", action="store_true", help="forward and backward passes of the actors and critics on the device kernels")
+ap.add_argument("--device-update", action="store_true", help="--fused-nets, and the losses, the optimisers and the soft updates on the device too")
 args = ap.parse_args()
+args.fused_nets = args.fused_nets or args.device_update
 EPISODE, N_STEP = 25, 3
 
 
@@ -52,14 +61,36 @@ mu_targ, q_targ = copy.deepcopy(mu), copy.deepcopy(qs)
 behaviour = Actors(env, mu, mode="sample")                # explores by sampling its softmax
 loop = PolicyLoop(env, behaviour, episode_len=EPISODE)
 target_actors = Actors(env, mu_targ, mode="softmax")      # MADDPG's relaxed one-hot actions
-td = TdTargets(target_actors, Critics(env, q_targ))       # both re-read their modules at every call: soft updates are seen
-opt_q = torch.optim.Adam([p for m in qs for p in m.parameters()], lr=1e-3)
-opt_mu = torch.optim.Adam([p for m in mu for p in m.parameters()], lr=1e-3)
+target_critics = Critics(env, q_targ)
+td = TdTargets(target_actors, target_critics)             # both re-read their modules at every call: soft updates are seen
+if not args.device_update:
+    opt_q = torch.optim.Adam([p for m in qs for p in m.parameters()], lr=1e-3)
+    opt_mu = torch.optim.Adam([p for m in mu for p in m.parameters()], lr=1e-3)
 col = target_actors.col_move                              # agent i's action columns of a joint row
 if args.fused_nets:
     q_train = Trainable(Critics(env, qs))                 # critic loss: the weights' gradients
     pi_train = Trainable(Actors(env, mu, mode="softmax", logits=True))
     q_const = Trainable(Critics(env, qs), input_grad=True, weight_grad=False, cols=[(c, 5) for c in col])      # actor loss: dQ_i / d(action columns)
+if args.device_update:
+    opt_q = DeviceAdam([q_train], lr=1e-3)                # the packed buffers are the master copies from here on
+    opt_mu = DeviceAdam([pi_train], lr=1e-3)
+    opt_mu.share(pi_train, behaviour)                     # the closed loop samples from the live actors
+    polyak = PolyakTargets([(pi_train, target_actors), (q_train, target_critics)], args.tau)
+    critic_head, actor_head = TdLoss(), ActorLoss(pi_train.net, q_train.net)      # the critics are a constant of the actor loss
+
+
+def device_update(batch, y):
+    """The whole update as a straight line of device launches: the two losses behind autograd, Adam and the soft updates in place"""
+    critic_loss = critic_head(q_train(batch.joint), y)
+    critic_loss.backward()
+    opt_q.step()
+    actor_loss = actor_head(pi_train(batch.obs_n), batch.joint)      # reads the critics the step above just updated
+    actor_loss.backward()
+    opt_mu.step()
+    polyak.step()
+    for p in q_train.parameters() + pi_train.parameters():          # (.grad of the stale module parameters is not used)
+        p.grad = None
+    return critic_loss, actor_loss
 
 
 def critic_values(joint):
@@ -83,6 +114,11 @@ for update in range(args.updates):
     loop.run(args.steps_per_update, record=False, replay=buf)
     batch = buf.sample(args.batch, joint=True, n_step=N_STEP, gamma=args.gamma, episode_len=EPISODE)
     y = td.compute(batch)                                 # [A, M], two launches, no gradient
+    if args.device_update:
+        critic_loss, actor_loss = device_update(batch, y)
+        print(json.dumps({"update": update, "critic_loss": float(critic_loss), "actor_loss": float(actor_loss),
+                          "mean_reward": float(batch.rew.mean()), "mean_y": float(y.mean())}), flush=True)
+        continue
     # critics: Q_i(obs, actions) -> y_i
     q = critic_values(batch.joint)
     critic_loss = sum(F.mse_loss(q[i], y[i]) for i in range(A))

@@ -723,6 +723,110 @@ size_t mpe_sizeof_adam(void);
 int64_t mpe_adam_work(const MpeAdam *cfg);
 int mpe_adam_step(const MpeAdam *cfg, double *state, double *work, void *stream);
 
+/* ---- the off-policy update: TD loss head, relaxed action rows and their gradient, soft target updates (csrc/mpe_ddpg.hip) --------
+ * What a MADDPG-style update needs beside mpe_critic_q, mpe_mlp_grad, mpe_mlp_dinput and mpe_adam_step, so that {sample, TD targets,
+ * critic update, actor update, soft updates} is one capturable straight line of this library's launches.  All of it
+ * is float32 with every operation rounded on its own, in the order written (no fused multiply-add); no atomics, no host
+ * synchronisation, no scratch.  Agents are i < A <= MPE_ACTOR_MAX_AGENTS, rows m < M, Mf = (float) M.  M == 0 returns 0 without a
+ * launch.  Sums: "in THE PPO LOSS RULE's order" means: float64; a chunk is the 256 rows of a block, one per lane (a lane at or beyond
+ * M holds +0.0); the 256 lane values are folded as THE ADVANTAGE STATISTICS RULE folds its lane sums; a one-block second launch adds
+ * the chunk partials in ascending chunk order.  A partial is 6 doubles per (agent, chunk), as mpe_ppo_loss's.
+ *
+ * THE TD LOSS RULE (mpe_td_loss, two launches).  q_ptrs[i]: agent i's [M] values (a HOST array of A device pointers, as value_ptrs
+ * is); y [A][M] (mpe_critic_q's y); w [M] or NULL: the importance weights of a prioritized batch.  Per agent and row
+ *   d = q - y;  wd = w * d (w NULL: wd = d);  sq = wd * d;  dq = (2 * wd) / Mf
+ * Per row td_abs[m] = the largest |d_i| over the agents, taken in ascending i as a select: t = |d_0|, then t = |d_i| where
+ * |d_i| > t or |d_i| is NaN -- a NaN |d_i| makes td_abs[m] NaN.  Each td_abs[m] is written once, by one lane.  Per agent sq, |d|, q
+ * and y are summed in THE PPO LOSS RULE's order; stats [A][8] = mean sq (= L_i), mean |d|, mean q, mean y (each S / M in float64,
+ * rounded when stored), 0, 0, L_i, 0; loss = (float) of the L_i added in ascending i in float64.  Outputs: dq [A][M]; td_abs [M]
+ * (optional); work: mpe_td_loss_work(A, M) doubles, 8-byte aligned, every one written before it is read; stats; loss [1].  Only +,
+ * -, x and correctly rounded / appear: the results are a function of the inputs alone, bit-equal to a NumPy restatement
+ * (tests/_ddpg_ref.py).
+ * Refused by name before any launch, in this order: q_ptrs, y, dq, work, stats or loss NULL; A outside 1..MPE_ACTOR_MAX_AGENTS;
+ * M < 0; a NULL q_ptrs[i]; a float pointer not 4-byte or work not 8-byte aligned; A * M >= 2^31.  mpe_td_loss_work (host only)
+ * applies the A, M and size checks and returns the count, or a negative code.
+ *
+ * THE POLICY ROWS RULE (mpe_policy_rows, one launch).  cfg: W, the joint row's width, 1..MPE_ACTOR_MAX_INPUT; dim_c; per agent
+ * col[i], movable[i], speaks[i] (speaks counts only with dim_c > 0).  n_i = 5 * movable + dim_c * speaks logits, 1 <= n_i <=
+ * MPE_ACTOR_MAX_OUT, and the window col[i] .. col[i] + n_i - 1 lies inside the row: the joint-row rule puts an agent's move row
+ * directly in front of its utterance row, so ONE window covers both heads in the logits' own order.  joint: contiguous [M][W];
+ * logits_ptrs[i]: contiguous [M][n_i]; out_ptrs[i]: contiguous [M][W], overlapping neither joint nor another agent's output (NOT
+ * checked).  For every row and column c
+ *   outside the window: out_i[m][c] = joint[m][c], bit for bit (NaN payloads included);
+ *   inside, per head: THE PPO LOSS RULE's head, zm = max z; e_j = exp(z_j - zm); s = ((e_0 + e_1) + ..); p_j = e_j / s
+ * with mpe_actor_act's fast exponential: the window carries the very bits an MPE_POLICY_SOFTMAX mpe_actor_act_rows launch writes
+ * for the same logits.  EVERY output float is written exactly once, by one lane: a block computes the windows of its 64 rows into
+ * LDS, then walks its rows' output as ONE flat run, each lane picking each of its floats from joint or from the LDS window -- 16
+ * bytes wide where out_ptrs[i] is 16-byte aligned (a run of count floats: count / 4 pieces, then count % 4 single floats), 4 bytes
+ * wide otherwise.  Nothing at or beyond row M is read or written.  A row depends on that row alone: the same bits at any M and at
+ * any position (the cut into workgroups is not part of the rule).
+ * Refused by name before any launch, in this order: cfg, joint, logits_ptrs or out_ptrs NULL; A outside 1..MPE_ACTOR_MAX_AGENTS;
+ * dim_c outside 0..MPE_ACTOR_MAX_OUT; an agent with no head, or with more than MPE_ACTOR_MAX_OUT logits; a window that
+ * leaves the row (col < 0 or col + n_i > W); W outside 1..MPE_ACTOR_MAX_INPUT; M < 0; a NULL logits_ptrs[i] or out_ptrs[i]; a
+ * pointer not 4-byte aligned; A * M >= 2^31; M * W >= 2^40 (which the bounds on M and W already exclude: the flat run's index
+ * arithmetic is 64-bit).
+ *
+ * THE POLICY ROWS GRADIENT RULE (mpe_policy_rows_grad, one launch; two with stats).  From dL/d(window) back to dL/dlogits.  cfg: as
+ * above, and reg_coef (finite, >= 0) and ld[i] >= n_i.  logits_ptrs[i] as above (p is recomputed; the rows launch saves nothing);
+ * g_ptrs[i]: row m's upstream gradient is at floats m * ld_i .. m * ld_i + n_i - 1 (ld = n_i: mpe_mlp_dinput's packed window, staged
+ * through the wave tile; ld = W with the pointer on column col[i]: a full-row gradient read in place).  Per head
+ *   dot = ((p_0 * g_0 + p_1 * g_1) + ..) in float64 (each product of two floats is exact there);
+ *   u_j = (float) ((double) g_j - dot);  dz_j = p_j * u_j
+ * (a float32 dot is off by a few ulps of |g| where g_j - dot cancels to a fraction of it, and missed the parity bound: DESIGN.md 2.22)
+ * and with cr_i = (float) (2 * reg_coef / ((double) M * n_i)) the result is dz_j + cr_i * z_j (the term is left out when reg_coef
+ * == 0): the gradient of reg_coef * mean(z^2), the mean over the rows and the agent's n_i logits.  dlogits_ptrs[i]: contiguous
+ * [M][n_i], staged out through the wave tile as mpe_ppo_loss does.  Stats (stats, loss and work all given, or none): q [A][M] is
+ * then required, the critics' values on the rows of THE POLICY ROWS RULE.  Per agent q, the row's z^2 = ((z_0 * z_0 + z_1 * z_1) +
+ * ..) in float32, and the row's entropy H (THE PPO LOSS RULE's, added over the heads in float32) are summed in THE PPO LOSS RULE's
+ * order; stats [A][8] = mean q, mean z^2 = S / ((double) M * n_i), mean H, 0, 0, 0, L_i, 0 with L_i = (-mean q) + reg_coef * mean z^2
+ * in float64; loss = (float) of the L_i added in ascending i.  work: mpe_policy_rows_grad_work(A, M) doubles.
+ * Refused by name before any launch, in this order: cfg, logits_ptrs, g_ptrs or dlogits_ptrs NULL; some but not all of work, stats
+ * and loss given; stats given and q NULL; then THE POLICY ROWS RULE's checks of A, dim_c, the heads, the windows, W and M; reg_coef
+ * not finite or negative; ld[i] < n_i; a NULL logits_ptrs[i], g_ptrs[i] or dlogits_ptrs[i]; a pointer not 4-byte or work not 8-byte
+ * aligned; A * M >= 2^31; M * ld[i] >= 2^40.
+ *
+ * THE POLYAK RULE (mpe_polyak, one launch).  Up to MPE_ADAM_MAX_SETS pairs {target, online, n} under mpe_adam_step's buffer
+ * conditions (n a multiple of 16, at least 16; 16-byte aligned pointers; nothing overlaps; the n sum below 2^31); tau in [0, 1], or
+ * tau_ptr, a DEVICE float the launch reads instead (as lr_ptr).  Per float, with t = (float) tau, x the target's and w the online
+ * float, d = w - x: torch.lerp's branch form
+ *   t < 0.5f:  x = x + t * d        otherwise:  x = w - d * (1 - t)
+ * so tau = 1 yields the online values and tau = 0 leaves the target's (bit for bit but for a -0.0, which +0.0 may replace), and
+ * padding stays +0.0.  All accesses are 16 bytes wide.  Bit-equal to a NumPy restatement.
+ * Refused by name before any launch, in this order: cfg NULL; n_sets outside 1..MPE_ADAM_MAX_SETS; per set: target or online NULL;
+ * one of them not 16-byte aligned; n < 16 or no multiple of 16; two buffers that overlap; N >= 2^31; tau (when tau_ptr is NULL) not
+ * finite or outside [0, 1]; tau_ptr not 4-byte aligned.                                                                           */
+typedef struct MpePolicyRows {
+  int32_t n_agents;                               /* A, 1..MPE_ACTOR_MAX_AGENTS                                             */
+  int32_t W;                                      /* floats of a joint row, 1..MPE_ACTOR_MAX_INPUT                          */
+  int32_t dim_c, reserved_;
+  int32_t col[MPE_ACTOR_MAX_AGENTS];              /* first column of agent i's window                                       */
+  uint8_t movable[MPE_ACTOR_MAX_AGENTS], speaks[MPE_ACTOR_MAX_AGENTS];
+  int64_t ld[MPE_ACTOR_MAX_AGENTS];               /* mpe_policy_rows_grad: floats from row to row of g_ptrs[i]              */
+  double reg_coef;                                /* mpe_policy_rows_grad: finite, >= 0                                     */
+} MpePolicyRows;
+typedef struct MpePolyakSet {
+  float *target;                                  /* updated in place                                                       */
+  const float *online;
+  int64_t n;                                      /* floats, a multiple of 16                                               */
+} MpePolyakSet;
+typedef struct MpePolyak {
+  double tau;
+  const float *tau_ptr;                           /* optional DEVICE float read by the launch instead of tau                */
+  int32_t n_sets, reserved_;
+  MpePolyakSet set[MPE_ADAM_MAX_SETS];
+} MpePolyak;
+size_t mpe_sizeof_policy_rows(void);
+size_t mpe_sizeof_polyak(void);
+int64_t mpe_td_loss_work(int32_t A, int64_t M);
+int mpe_td_loss(int32_t A, const float *const *q_ptrs, const float *y, const float *w, int64_t M, float *dq, float *td_abs,
+                double *work, float *stats, float *loss, void *stream);
+int mpe_policy_rows(const MpePolicyRows *cfg, const float *joint, const float *const *logits_ptrs, int64_t M, float *const *out_ptrs,
+                    void *stream);
+int64_t mpe_policy_rows_grad_work(int32_t A, int64_t M);
+int mpe_policy_rows_grad(const MpePolicyRows *cfg, const float *const *logits_ptrs, const float *const *g_ptrs, int64_t M,
+                         float *const *dlogits_ptrs, const float *q, double *work, float *stats, float *loss, void *stream);
+int mpe_polyak(const MpePolyak *cfg, void *stream);
+
 /* ---- the replay buffer: the last S steps of all B worlds in device memory (csrc/mpe_replay.hip) ------------------------------
  * What an off-policy learner keeps beside the loop above: a ring of transitions (obs, action, reward, done, next obs) of every
  * agent, filled by ONE launch per step (mpe_replay_push) and sampled by ONE launch per minibatch (mpe_replay_sample), the same

@@ -8,10 +8,12 @@ from . import core, scenarios  # noqa: F401
 from .rollout import MlpPolicy, PolicyRollout, PolicyTrajectory  # noqa: F401
 from .policy import Actors, PolicyLoop  # noqa: F401
 from .learner import Critics, TdTargets  # noqa: F401
+from .learner import (TdLoss, TdLossResult, td_loss_tensors, ActorLoss, RowsLayout, PolicyRowsGradResult,  # noqa: F401
+                      policy_rows_tensors, policy_rows_grad_tensors)
 from .onpolicy import Values, GaeResult, gae, gae_tensors, adv_stats, Minibatches, OnPolicyBatch  # noqa: F401
 from .onpolicy import PpoLoss, PpoLossResult, ppo_loss_tensors  # noqa: F401
 from .train import Trainable, MlpGradResult, mlp_grad_tensors, mlp_dinput_tensors  # noqa: F401
-from .optim import DeviceAdam  # noqa: F401
+from .optim import DeviceAdam, PolyakTargets  # noqa: F401
 from .replay import (ReplayBuffer, ReplayBatch, NStepReplayBatch, PrioritizedReplayBuffer, PrioritizedReplayBatch,  # noqa: F401
                      PrioritizedNStepReplayBatch)
 
@@ -19,5 +21,7 @@ __all__ = ["make_env", "MultiAgentEnv", "BatchMultiAgentEnv", "GraphedStep", "Ba
            "PolicyTrajectory", "Actors", "PolicyLoop", "Critics", "TdTargets", "Values", "GaeResult", "gae", "gae_tensors",
            "adv_stats", "Minibatches", "OnPolicyBatch", "PpoLoss", "PpoLossResult", "ppo_loss_tensors",
            "Trainable", "MlpGradResult", "mlp_grad_tensors", "mlp_dinput_tensors", "DeviceAdam",
+           "TdLoss", "TdLossResult", "td_loss_tensors", "ActorLoss", "RowsLayout", "PolicyRowsGradResult", "policy_rows_tensors",
+           "policy_rows_grad_tensors", "PolyakTargets",
            "ReplayBuffer", "ReplayBatch",
            "PrioritizedReplayBuffer", "PrioritizedReplayBatch", "NStepReplayBatch", "PrioritizedNStepReplayBatch"]

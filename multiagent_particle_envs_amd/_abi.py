@@ -112,6 +112,20 @@ class MpeAdam(C.Structure):            # include/mpe_hip.h: the scalars and the 
                 ("set", MpeAdamSet * MPE_ADAM_MAX_SETS)]
 
 
+class MpePolicyRows(C.Structure):      # include/mpe_hip.h: the joint row's layout of mpe_policy_rows / mpe_policy_rows_grad
+    _fields_ = [("n_agents", C.c_int32), ("W", C.c_int32), ("dim_c", C.c_int32), ("reserved_", C.c_int32), ("col", C.c_int32 * 16),
+                ("movable", C.c_uint8 * 16), ("speaks", C.c_uint8 * 16), ("ld", C.c_int64 * 16), ("reg_coef", C.c_double)]
+
+
+class MpePolyakSet(C.Structure):       # include/mpe_hip.h: one {target, online} pair of packed buffers of mpe_polyak
+    _fields_ = [("target", C.c_void_p), ("online", C.c_void_p), ("n", C.c_int64)]
+
+
+class MpePolyak(C.Structure):          # include/mpe_hip.h: THE POLYAK RULE's tau and pairs (mpe_polyak)
+    _fields_ = [("tau", C.c_double), ("tau_ptr", C.c_void_p), ("n_sets", C.c_int32), ("reserved_", C.c_int32),
+                ("set", MpePolyakSet * MPE_ADAM_MAX_SETS)]
+
+
 MPE_REPLAY_MAX_AGENTS, MPE_REPLAY_MAX_WIDTH = 16, 4096
 MPE_STREAM_REPLAY = 0x5245504C
 
@@ -269,6 +283,15 @@ EXPORTS = {
     "mpe_sizeof_adam": (C.c_size_t, []),
     "mpe_adam_work": (C.c_int64, [C.POINTER(MpeAdam)]),
     "mpe_adam_step": (C.c_int, [C.POINTER(MpeAdam), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mpe_sizeof_policy_rows": (C.c_size_t, []),
+    "mpe_sizeof_polyak": (C.c_size_t, []),
+    "mpe_td_loss_work": (C.c_int64, [C.c_int32, C.c_int64]),
+    "mpe_td_loss": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6),
+    "mpe_policy_rows": (C.c_int, [C.POINTER(MpePolicyRows), C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_void_p), C.c_void_p]),
+    "mpe_policy_rows_grad_work": (C.c_int64, [C.c_int32, C.c_int64]),
+    "mpe_policy_rows_grad": (C.c_int, [C.POINTER(MpePolicyRows), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int64,
+                                       C.POINTER(C.c_void_p)] + [C.c_void_p] * 5),
+    "mpe_polyak": (C.c_int, [C.POINTER(MpePolyak), C.c_void_p]),
     "mpe_sizeof_replay": (C.c_size_t, []),
     "mpe_replay_supported": (C.c_int, [C.POINTER(MpeReplay)]),
     "mpe_replay_push": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
@@ -325,6 +348,7 @@ def lib():
             handle.mpe_sizeof_ppo_loss() != C.sizeof(MpePpoLoss) or \
             handle.mpe_sizeof_adam() != C.sizeof(MpeAdam) or \
             handle.mpe_sizeof_mlp_dinput() != C.sizeof(MpeMlpDinput) or \
+            handle.mpe_sizeof_policy_rows() != C.sizeof(MpePolicyRows) or handle.mpe_sizeof_polyak() != C.sizeof(MpePolyak) or \
             handle.mpe_sizeof_replay_nstep() != C.sizeof(MpeReplayNStep):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")
     _lib = handle

@@ -1776,6 +1776,164 @@ int mpe_adam_step(const MpeAdam *cfg, double *state, double *work, void *stream)
   return hip_result(mpe::launch_adam(a, static_cast<hipStream_t>(stream)), what);
 }
 
+// ---- the off-policy update (mpe_ddpg.hip) ------------------------------------------------------------------------------------------
+size_t mpe_sizeof_policy_rows(void) { return sizeof(MpePolicyRows); }
+size_t mpe_sizeof_polyak(void) { return sizeof(MpePolyak); }
+static int64_t ddpg_work(int32_t A, int64_t M, const char *what) {
+  if (int rc = check_ppo_agents(A, what)) return rc;
+  if (int rc = check_ppo_rows(M, what)) return rc;
+  if (int rc = check_ppo_size(A, M, what)) return rc;
+  return (int64_t)((uint64_t)mpe::kPpoSums * (uint64_t)A * mpe::ppo_chunks((uint64_t)M));
+}
+int64_t mpe_td_loss_work(int32_t A, int64_t M) { return ddpg_work(A, M, "mpe_td_loss_work"); }
+int64_t mpe_policy_rows_grad_work(int32_t A, int64_t M) { return ddpg_work(A, M, "mpe_policy_rows_grad_work"); }
+int mpe_td_loss(int32_t A, const float *const *q_ptrs, const float *y, const float *w, int64_t M, float *dq, float *td_abs, double *work,
+                float *stats, float *loss, void *stream) {
+  const char *what = "mpe_td_loss";
+  const struct { const void *p; const char *name; } need[] = {{q_ptrs, "q_ptrs"}, {y, "y"}, {dq, "dq"}, {work, "work"}, {stats, "stats"}, {loss, "loss"}};
+  for (const auto &f : need)
+    if (!f.p) return fail(MPE_EINVAL, "%s: %s is NULL", what, f.name);
+  if (int rc = check_ppo_agents(A, what)) return rc;
+  if (int rc = check_ppo_rows(M, what)) return rc;
+  uintptr_t f4 = (uintptr_t)y | (uintptr_t)w | (uintptr_t)dq | (uintptr_t)td_abs | (uintptr_t)stats | (uintptr_t)loss;
+  for (int i = 0; i < A; ++i) {
+    if (!q_ptrs[i]) return fail(MPE_EINVAL, "%s: q_ptrs[%d] is NULL", what, i);
+    f4 |= (uintptr_t)q_ptrs[i];
+  }
+  if ((f4 & 3) || ((uintptr_t)work & 7)) return fail(MPE_EINVAL, "%s: every float tensor must be 4-byte and work 8-byte aligned", what);
+  if (int rc = check_ppo_size(A, M, what)) return rc;
+  if (M == 0) return 0;
+  mpe::TdArgs a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  for (int i = 0; i < A; ++i) a.q[i] = q_ptrs[i];
+  a.y = y, a.w = w, a.dq = dq, a.td_abs = td_abs, a.work = work, a.stats = stats, a.loss = loss;
+  a.M = (uint64_t)M, a.A = A;
+  return hip_result(mpe::launch_td_loss(a, static_cast<hipStream_t>(stream)), what);
+}
+// the cfg checks mpe_policy_rows and mpe_policy_rows_grad share, in the header's order; fills the layout of the launch's arguments
+static int check_policy_rows(const MpePolicyRows *c, int64_t M, const char *what, mpe::PolRowsArgs &a) {
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  const int32_t A = c->n_agents;
+  if (int rc = check_ppo_agents(A, what)) return rc;
+  if (c->dim_c < 0 || c->dim_c > MPE_ACTOR_MAX_OUT) return fail(MPE_EINVAL, "%s: dim_c = %d (0..%d)", what, c->dim_c, MPE_ACTOR_MAX_OUT);
+  for (int i = 0; i < A; ++i) {
+    const bool mv = c->movable[i] != 0, sp = c->speaks[i] != 0 && c->dim_c > 0;
+    const int n = MPE_ACTION_DIM * mv + c->dim_c * sp;
+    if (n < 1) return fail(MPE_EINVAL, "%s: agent %d has no head (neither movable nor speaking with dim_c > 0)", what, i);
+    if (n > MPE_ACTOR_MAX_OUT)
+      return fail(MPE_EUNSUPPORTED, "%s: agent %d: %d logits (5 * movable + dim_c * speaks) > MPE_ACTOR_MAX_OUT = %d", what, i, n, MPE_ACTOR_MAX_OUT);
+    a.movable[i] = mv, a.speaks[i] = sp;
+  }
+  for (int i = 0; i < A; ++i) {
+    const int n = MPE_ACTION_DIM * a.movable[i] + c->dim_c * a.speaks[i];
+    if (c->col[i] < 0 || (int64_t)c->col[i] + n > (int64_t)c->W)
+      return fail(MPE_EINVAL, "%s: agent %d: the window of %d columns from %d leaves the row of W = %d", what, i, n, c->col[i], c->W);
+    a.col[i] = c->col[i];
+  }
+  if (c->W < 1 || c->W > MPE_ACTOR_MAX_INPUT) return fail(MPE_EINVAL, "%s: W = %d (1..MPE_ACTOR_MAX_INPUT = %d)", what, c->W, MPE_ACTOR_MAX_INPUT);
+  if (int rc = check_ppo_rows(M, what)) return rc;
+  a.A = A, a.W = c->W, a.dim_c = c->dim_c, a.M = (uint64_t)M;
+  return 0;
+}
+int mpe_policy_rows(const MpePolicyRows *cfg, const float *joint, const float *const *logits_ptrs, int64_t M, float *const *out_ptrs,
+                    void *stream) {
+  const char *what = "mpe_policy_rows";
+  const struct { const void *p; const char *name; } need[] = {{cfg, "cfg"}, {joint, "joint"}, {logits_ptrs, "logits_ptrs"}, {out_ptrs, "out_ptrs"}};
+  for (const auto &f : need)
+    if (!f.p) return fail(MPE_EINVAL, "%s: %s is NULL", what, f.name);
+  mpe::PolRowsArgs a;
+  if (int rc = check_policy_rows(cfg, M, what, a)) return rc;
+  uintptr_t f4 = (uintptr_t)joint;
+  for (int i = 0; i < a.A; ++i) {
+    if (!logits_ptrs[i]) return fail(MPE_EINVAL, "%s: logits_ptrs[%d] is NULL", what, i);
+    if (!out_ptrs[i]) return fail(MPE_EINVAL, "%s: out_ptrs[%d] is NULL", what, i);
+    f4 |= (uintptr_t)logits_ptrs[i] | (uintptr_t)out_ptrs[i];
+    a.logits[i] = logits_ptrs[i], a.out[i] = out_ptrs[i];
+  }
+  if (f4 & 3) return fail(MPE_EINVAL, "%s: every pointer must be 4-byte aligned", what);
+  if (int rc = check_ppo_size(a.A, M, what)) return rc;
+  if (M * (int64_t)a.W >= (1ll << 40)) return fail(MPE_EINVAL, "%s: M * W = %lld * %d floats (need M * W < 2^40)", what, (long long)M, a.W);
+  if (M == 0) return 0;
+  a.joint = joint;
+  return hip_result(mpe::launch_policy_rows(a, static_cast<hipStream_t>(stream)), what);
+}
+int mpe_policy_rows_grad(const MpePolicyRows *cfg, const float *const *logits_ptrs, const float *const *g_ptrs, int64_t M,
+                         float *const *dlogits_ptrs, const float *q, double *work, float *stats, float *loss, void *stream) {
+  const char *what = "mpe_policy_rows_grad";
+  const struct { const void *p; const char *name; } need[] = {{cfg, "cfg"}, {logits_ptrs, "logits_ptrs"}, {g_ptrs, "g_ptrs"}, {dlogits_ptrs, "dlogits_ptrs"}};
+  for (const auto &f : need)
+    if (!f.p) return fail(MPE_EINVAL, "%s: %s is NULL", what, f.name);
+  const int given = (work != nullptr) + (stats != nullptr) + (loss != nullptr);
+  if (given != 0 && given != 3) return fail(MPE_EINVAL, "%s: work, stats and loss are given together or not at all", what);
+  if (given && !q) return fail(MPE_EINVAL, "%s: stats is given and q is NULL", what);
+  mpe::PolRowsArgs a;
+  if (int rc = check_policy_rows(cfg, M, what, a)) return rc;
+  if (!std::isfinite(cfg->reg_coef) || cfg->reg_coef < 0.0) return fail(MPE_EINVAL, "%s: reg_coef = %g (need a finite value >= 0)", what, cfg->reg_coef);
+  for (int i = 0; i < a.A; ++i) {
+    const int n = (int)mpe::pr_n(a, (uint32_t)i);
+    if (cfg->ld[i] < n) return fail(MPE_EINVAL, "%s: agent %d: ld = %lld (need >= n = %d)", what, i, (long long)cfg->ld[i], n);
+    a.ld[i] = cfg->ld[i];
+  }
+  uintptr_t f4 = (uintptr_t)q | (uintptr_t)stats | (uintptr_t)loss;
+  for (int i = 0; i < a.A; ++i) {
+    if (!logits_ptrs[i]) return fail(MPE_EINVAL, "%s: logits_ptrs[%d] is NULL", what, i);
+    if (!g_ptrs[i]) return fail(MPE_EINVAL, "%s: g_ptrs[%d] is NULL", what, i);
+    if (!dlogits_ptrs[i]) return fail(MPE_EINVAL, "%s: dlogits_ptrs[%d] is NULL", what, i);
+    f4 |= (uintptr_t)logits_ptrs[i] | (uintptr_t)g_ptrs[i] | (uintptr_t)dlogits_ptrs[i];
+    a.logits[i] = logits_ptrs[i], a.g[i] = g_ptrs[i], a.dlogits[i] = dlogits_ptrs[i];
+  }
+  if ((f4 & 3) || ((uintptr_t)work & 7)) return fail(MPE_EINVAL, "%s: every float tensor must be 4-byte and work 8-byte aligned", what);
+  if (int rc = check_ppo_size(a.A, M, what)) return rc;
+  for (int i = 0; i < a.A; ++i)      // (M < 2^31, so the product cannot overflow below)
+    if (a.ld[i] >= (1ll << 40) || M * a.ld[i] >= (1ll << 40))
+      return fail(MPE_EINVAL, "%s: agent %d: M * ld = %lld * %lld floats (need M * ld < 2^40)", what, i, (long long)M, (long long)a.ld[i]);
+  if (M == 0) return 0;
+  a.q = q, a.work = work, a.has_stats = given != 0, a.has_reg = cfg->reg_coef != 0.0;
+  for (int i = 0; i < a.A; ++i) a.cr[i] = (float)(2.0 * cfg->reg_coef / ((double)M * (double)mpe::pr_n(a, (uint32_t)i)));
+  return hip_result(mpe::launch_policy_rows_grad(a, cfg->reg_coef, stats, loss, static_cast<hipStream_t>(stream)), what);
+}
+int mpe_polyak(const MpePolyak *c, void *stream) {
+  const char *what = "mpe_polyak";
+  if (!c) return fail(MPE_EINVAL, "%s: cfg is NULL", what);
+  if (c->n_sets < 1 || c->n_sets > MPE_ADAM_MAX_SETS)
+    return fail(MPE_EINVAL, "%s: n_sets = %d (1..MPE_ADAM_MAX_SETS = %d)", what, c->n_sets, MPE_ADAM_MAX_SETS);
+  const int S = c->n_sets;
+  static const char *const names[2] = {"target", "online"};
+  for (int s = 0; s < S; ++s) {
+    const MpePolyakSet &q = c->set[s];
+    const void *ptr[2] = {q.target, q.online};
+    for (int k = 0; k < 2; ++k)
+      if (!ptr[k]) return fail(MPE_EINVAL, "%s: set[%d].%s is NULL", what, s, names[k]);
+    for (int k = 0; k < 2; ++k)
+      if ((uintptr_t)ptr[k] & 15) return fail(MPE_EINVAL, "%s: set[%d].%s is not 16-byte aligned", what, s, names[k]);
+    if (q.n < 16 || q.n % 16) return fail(MPE_EINVAL, "%s: set[%d].n = %lld floats (a multiple of 16, at least 16)", what, s, (long long)q.n);
+  }
+  for (int s = 0; s < S; ++s)
+    for (int k = 0; k < 2; ++k)
+      for (int s2 = 0; s2 <= s; ++s2)
+        for (int k2 = 0; k2 < (s2 == s ? k : 2); ++k2) {
+          const void *pa[2] = {c->set[s2].target, c->set[s2].online};
+          const void *pb[2] = {c->set[s].target, c->set[s].online};
+          const unsigned __int128 a0 = (uintptr_t)pa[k2], a1 = a0 + (unsigned __int128)c->set[s2].n * 4;
+          const unsigned __int128 b0 = (uintptr_t)pb[k], b1 = b0 + (unsigned __int128)c->set[s].n * 4;
+          if (a0 < b1 && b0 < a1) return fail(MPE_EINVAL, "%s: set[%d].%s and set[%d].%s overlap", what, s2, names[k2], s, names[k]);
+        }
+  int64_t N = 0;
+  for (int s = 0; s < S; ++s) {
+    if (c->set[s].n > 0x7fffffffll - N) return fail(MPE_EINVAL, "%s: the sets hold 2^31 floats or more (need N < 2^31)", what);
+    N += c->set[s].n;
+  }
+  if (!c->tau_ptr && (!std::isfinite(c->tau) || c->tau < 0.0 || c->tau > 1.0)) return fail(MPE_EINVAL, "%s: tau = %g (need 0 <= tau <= 1)", what, c->tau);
+  if ((uintptr_t)c->tau_ptr & 3) return fail(MPE_EINVAL, "%s: tau_ptr is not 4-byte aligned", what);
+  mpe::PolyakArgs a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  for (int s = 0; s < S; ++s) a.x[s] = c->set[s].target, a.w[s] = c->set[s].online, a.n[s] = (uint32_t)c->set[s].n;
+  a.n_sets = (uint32_t)S;
+  mpe::polyak_tiling(a);
+  a.tau = c->tau_ptr ? 0.f : (float)c->tau, a.tau_ptr = c->tau_ptr;
+  return hip_result(mpe::launch_polyak(a, static_cast<hipStream_t>(stream)), what);
+}
+
 // ---- the replay buffer (mpe_replay.hip) ---------------------------------------------------------------------------------------
 size_t mpe_sizeof_replay(void) { return sizeof(MpeReplay); }
 static int check_replay(const MpeReplay *r, const char *what, bool pointers) {

@@ -8,6 +8,7 @@
 #include "mpe_mlp_grad.h"
 #include "mpe_mlp_dinput.h"
 #include "mpe_adam.h"
+#include "mpe_ddpg.h"
 
 namespace mpe {
 
@@ -172,6 +173,14 @@ int launch_mlp_dinput(const MlpDinputArgs &a, hipStream_t stream);          // o
 static_assert(kAdamMaxSets == MPE_ADAM_MAX_SETS && kAdamTile == MPE_ADAM_TILE && kAdamMaxPartials == MPE_ADAM_MAX_PARTIALS &&
               kAdamStateDoubles == MPE_ADAM_STATE_DOUBLES, "mpe_adam.h restates them");
 int launch_adam(const AdamArgs &a, hipStream_t stream);                     // two launches: the norm's partials and the commit, then the update
+
+// the off-policy update's loss heads, relaxed rows and soft updates (mpe_ddpg.hip; the arguments, every index and the rows'
+// arithmetic: mpe_ddpg.h), checked by the caller
+static_assert(kDdpgMaxWidth == MPE_ACTOR_MAX_INPUT, "mpe_ddpg.h restates it");
+int launch_td_loss(const TdArgs &a, hipStream_t stream);                    // two launches: the rows and chunk sums, then the ordered final pass
+int launch_policy_rows(const PolRowsArgs &a, hipStream_t stream);           // one launch, M > 0
+int launch_policy_rows_grad(const PolRowsArgs &a, double reg_coef, float *stats, float *loss, hipStream_t stream);      // one launch; two with stats
+int launch_polyak(const PolyakArgs &a, hipStream_t stream);                 // one launch
 
 // the replay buffer (mpe_replay.hip): both launches' arguments, checked and filled by the caller (mpe_replay_push / _sample)
 constexpr int kReplayMaxSegs = 2 * MPE_REPLAY_MAX_AGENTS + 4;     // obs and next obs per agent, act, utter, rew, done

@@ -2,7 +2,10 @@
 rows in ONE launch (mpe_critic_q: the actor kernel's MFMA body with a one-output last layer and no head), and `TdTargets` turns a
 sampled ReplayBatch into the TD target in TWO launches -- the target actors decide on batch.next_obs_n and write complete critic
 input rows (Actors.act_rows, joint=True), the target critics read those rows and write Q' and y.  DESIGN.md 2.14; the two rules
-(joint rows, y) are stated in include/mpe_hip.h.  Backward passes stay in torch autograd.
+(joint rows, y) are stated in include/mpe_hip.h.  The loss heads of the update are here too: `TdLoss` (the critics'
+weighted squared TD error and its gradient, mpe_td_loss) and `ActorLoss` (the relaxed action rows, the critics on them, their input
+gradient and the softmax Jacobian: mpe_policy_rows, mpe_critic_q, mpe_mlp_dinput, mpe_policy_rows_grad), both behind torch autograd
+with a one-multiply backward; the networks' own backward passes are train.py's.
 
     mu_t, q_t = Actors(env, target_actor_modules, mode="softmax"), Critics(env, target_critic_modules)
     td = TdTargets(mu_t, q_t)
@@ -15,7 +18,7 @@ import math
 import torch
 
 from . import _abi
-from .netset import Cache, NetSet
+from .netset import Cache, Generations, NetSet, check_tensor
 from .policy import Actors, env_joint_layout
 from .replay import NStepReplayBatch, ReplayBatch
 
@@ -135,3 +138,317 @@ class TdTargets(object):
         self.joint_next_act = self.actors.joint_rows
         self.q_next, self.y = self.critics._launch([self.joint_next_act] * self.critics.A, M, td)
         return self.y
+
+
+# ---- the TD loss head: the weighted squared TD error and its gradient in two launches (mpe_td_loss) -------------------
+class TdLossResult(object):
+    """What td_loss_tensors wrote: loss [1]; stats [A, 8] (per agent the means of the weighted squared error, |d|, q and y, then 0,
+    0, L_i, 0); dq [A, M] = dL/dq, already scaled by 2 / M (and the weights); td_abs [M], per row the largest |q_i - y_i| over the
+    agents (what PrioritizedReplayBuffer.update_td takes); work, the launches' workspace."""
+    __slots__ = ("A", "M", "loss", "stats", "dq", "td_abs", "work")
+
+    STATS = ("loss", "abs_td", "q", "y", "reserved", "reserved", "loss", "reserved")
+
+
+def _work(name, A, M, dev):
+    n = getattr(_abi.lib(), name)(A, M)      # (host only: the size checks)
+    if n < 0:
+        _abi.check(int(n), name)
+    return torch.empty((max(int(n), 1),), dtype=torch.float64, device=dev)
+
+
+def td_loss_tensors(q_n, y, weights=None, out=None):
+    """THE TD LOSS RULE in two launches for every agent, no host synchronisation (captures into a HIP graph).  q_n[i]: agent i's
+    [M] or [M, 1] float32 values; y [A, M]: TdTargets.y; weights [M]: the importance weights of a prioritized batch (None: 1).
+    out: a TdLossResult to rewrite.  -> TdLossResult."""
+    who = "td_loss_tensors"
+    if not isinstance(q_n, (list, tuple)) or not 1 <= len(q_n) <= _abi.MPE_ACTOR_MAX_AGENTS:
+        raise _abi.MpeError("%s: q_n is a list of 1..MPE_ACTOR_MAX_AGENTS = %d tensors, one per agent" % (who, _abi.MPE_ACTOR_MAX_AGENTS))
+    A, q0 = len(q_n), q_n[0]
+    if not torch.is_tensor(q0) or q0.dim() not in (1, 2):
+        raise _abi.MpeError("%s: q_n[0] is a contiguous float32 [M] or [M, 1] tensor on a GPU" % who)
+    M, dev = int(q0.shape[0]), q0.device
+    for i, q in enumerate(q_n):
+        check_tensor(who, q, "q_n[%d]" % i, [(M,), (M, 1)], "q_n[0]'s device", dev)
+    check_tensor(who, y, "y", [(A, M)], "q_n[0]'s device", dev)
+    if weights is not None:
+        check_tensor(who, weights, "weights", [(M,)], "q_n[0]'s device", dev)
+    if out is not None and (not isinstance(out, TdLossResult) or out.A != A or out.M != M or out.dq.device != dev):
+        raise _abi.MpeError("%s: out is a TdLossResult of %d agents and M = %d (what an earlier call returned)" % (who, A, M))
+    if not q0.is_cuda:
+        raise _abi.MpeError("%s: q_n[0] is on %s (the tensors live on a GPU: there is no CPU path)" % (who, dev))
+    if out is None:
+        out = TdLossResult()
+        out.A, out.M = A, M
+        out.dq = torch.zeros((A, M), dtype=torch.float32, device=dev)
+        out.td_abs = torch.zeros((M,), dtype=torch.float32, device=dev)
+        out.stats = torch.zeros((A, 8), dtype=torch.float32, device=dev)
+        out.loss = torch.zeros((1,), dtype=torch.float32, device=dev)
+        out.work = _work("mpe_td_loss_work", A, M, dev)
+    qp = (C.c_void_p * A)(*[q.data_ptr() for q in q_n])
+    _abi.check(_abi.lib().mpe_td_loss(A, qp, y.data_ptr(), weights.data_ptr() if weights is not None else None, M, out.dq.data_ptr(),
+                                      out.td_abs.data_ptr(), out.work.data_ptr(), out.stats.data_ptr(), out.loss.data_ptr(),
+                                      _abi.raw_stream(dev)), "mpe_td_loss")
+    return out
+
+
+class _TdLossFn(torch.autograd.Function):
+    """forward: the two launches; backward: grad_output * the gradients the forward wrote (ONE multiply)"""
+
+    @staticmethod
+    def forward(ctx, head, y, weights, *q_n):
+        qs = [q.detach() for q in q_n]
+        M = int(qs[0].shape[0]) if torch.is_tensor(qs[0]) and qs[0].dim() in (1, 2) else -1
+        key = (len(qs), M, qs[0].device if torch.is_tensor(qs[0]) else None)
+        res = td_loss_tensors(qs, y, weights, out=head._out.get(key))
+        head._out.get(key, lambda: res)
+        ctx.res, ctx.shapes, ctx.owner = res, [tuple(q.shape) for q in q_n], (head, key, head._generation.next(key))
+        head.last = res
+        return res.loss.view(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        res = ctx.res
+        head, key, generation = ctx.owner
+        if head._generation.stale(key, generation) or head._out.get(key) is not res:
+            raise _abi.MpeError("TdLoss: backward() of a loss whose buffers a later forward with the same M has rewritten (the "
+                                "buffers are cached per M: call backward() before the next forward)")
+        g = grad_output * res.dq      # out of place: the buffer is rewritten by the next forward of the same M
+        return (None, None, None) + tuple(g[i].view(s) for i, s in enumerate(ctx.shapes))
+
+
+class TdLoss(object):
+    """The TD loss head behind torch autograd: loss = TdLoss()(q_n, y, weights=None) is the sum over the agents of
+    mean(weights * (q_i - y_i)^2) -- F.mse_loss per agent without weights.  The forward is mpe_td_loss's two launches for all
+    agents, the backward ONE multiply of grad_output with the gradients the forward wrote; no host read anywhere.  loss.stats
+    [A, 8] (device) carries TdLossResult.STATS; .last is the TdLossResult of the last call (its td_abs [M] is what a prioritized
+    buffer's update_td takes).  The buffers are cached per M and rewritten by the next call with the same M: call backward()
+    before the next forward; a backward() behind such a forward is refused.  Once differentiable."""
+
+    def __init__(self):
+        self._out, self._generation, self.last = Cache(), Generations(), None
+
+    def __call__(self, q_n, y, weights=None):
+        who = "TdLoss"
+        if not isinstance(q_n, (list, tuple)) or not q_n:
+            raise _abi.MpeError("%s: q_n is a list of tensors, one per agent" % who)
+        for i, t in enumerate(q_n):
+            if not torch.is_tensor(t):
+                raise _abi.MpeError("%s: q_n[%d] is not a tensor" % (who, i))
+        if torch.is_tensor(y) and y.requires_grad:
+            raise _abi.MpeError("%s: y requires grad (the TD target is a constant of the loss)" % who)
+        loss = _TdLossFn.apply(self, y, weights, *q_n)
+        loss.stats = self.last.stats
+        return loss
+
+
+# ---- the relaxed action rows and their gradient (mpe_policy_rows, mpe_policy_rows_grad, DESIGN.md 2.22) ------------------------------
+class RowsLayout(object):
+    """Where each agent's action window sits in the critic's joint row: W floats per row, dim_c, and per agent col (the first column of
+    its window), movable and speaks; n[i] = 5 * movable + dim_c * speaks logits fill the window.  RowsLayout.of(actors) reads an
+    Actors' joint layout."""
+
+    def __init__(self, W, dim_c, col, movable, speaks):
+        self.W, self.dim_c = int(W), int(dim_c)
+        self.col, self.movable, self.speaks = [int(c) for c in col], [bool(m) for m in movable], [bool(s) and self.dim_c > 0 for s in speaks]
+        self.A = len(self.col)
+        if not 1 <= self.A <= _abi.MPE_ACTOR_MAX_AGENTS or len(self.movable) != self.A or len(self.speaks) != self.A:
+            raise _abi.MpeError("RowsLayout: col, movable and speaks are lists of 1..MPE_ACTOR_MAX_AGENTS = %d entries, one per agent"
+                                % _abi.MPE_ACTOR_MAX_AGENTS)
+        self.n = [_abi.MPE_ACTION_DIM * m + self.dim_c * s for m, s in zip(self.movable, self.speaks)]
+
+    @staticmethod
+    def of(layout, who="RowsLayout"):
+        if isinstance(layout, RowsLayout):
+            return layout
+        if isinstance(layout, Actors):
+            col = [m if m is not None else u for m, u in zip(layout.col_move, layout.col_utter)]
+            return RowsLayout(layout.joint_width, layout.dim_c, col, layout.movable, layout.speaks)
+        raise _abi.MpeError("%s: layout is an Actors or a RowsLayout(W, dim_c, col, movable, speaks)" % who)
+
+    def cfg(self):
+        c = _abi.MpePolicyRows()
+        c.n_agents, c.W, c.dim_c = self.A, self.W, self.dim_c
+        for i in range(self.A):
+            c.col[i], c.movable[i], c.speaks[i], c.ld[i] = self.col[i], int(self.movable[i]), int(self.speaks[i]), self.n[i]
+        return c
+
+
+def _logits_check(who, lay, logits_n):
+    if not isinstance(logits_n, (list, tuple)) or len(logits_n) != lay.A:
+        raise _abi.MpeError("%s: logits_n is a list of %d tensors, one per agent" % (who, lay.A))
+    z0 = logits_n[0]
+    if not torch.is_tensor(z0) or z0.dim() != 2:
+        raise _abi.MpeError("%s: logits_n[0] is a contiguous float32 [M, %d] tensor on a GPU" % (who, lay.n[0]))
+    M, dev = int(z0.shape[0]), z0.device
+    for i, z in enumerate(logits_n):
+        check_tensor(who, z, "logits_n[%d]" % i, [(M, lay.n[i])], "logits_n[0]'s device", dev)
+    return M, dev
+
+
+def _ptrs(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def policy_rows_tensors(layout, joint, logits_n, out=None):
+    """THE POLICY ROWS RULE in one launch, no host synchronisation: per agent the batch's joint rows with its own action window
+    replaced by the softmax of its logits, head by head.  layout: an Actors or a RowsLayout; joint: contiguous float32 [M, W];
+    logits_n[i]: [M, n_i].  out: a list of A contiguous [M, W] tensors to rewrite (they overlap neither joint nor one another: not
+    checked).  -> the list of A tensors."""
+    who = "policy_rows_tensors"
+    lay = RowsLayout.of(layout, who)
+    M, dev = _logits_check(who, lay, logits_n)
+    check_tensor(who, joint, "joint", [(M, lay.W)], "logits_n[0]'s device", dev)
+    if out is not None:
+        if not isinstance(out, (list, tuple)) or len(out) != lay.A:
+            raise _abi.MpeError("%s: out is a list of %d tensors, one per agent" % (who, lay.A))
+        for i, o in enumerate(out):
+            check_tensor(who, o, "out[%d]" % i, [(M, lay.W)], "logits_n[0]'s device", dev)
+    if not joint.is_cuda:
+        raise _abi.MpeError("%s: joint is on %s (the tensors live on a GPU: there is no CPU path)" % (who, dev))
+    if out is None:
+        out = [torch.zeros((M, lay.W), dtype=torch.float32, device=dev) for _ in range(lay.A)]
+    cfg = lay.cfg()
+    _abi.check(_abi.lib().mpe_policy_rows(C.byref(cfg), joint.data_ptr(), _ptrs(logits_n), M, _ptrs(out), _abi.raw_stream(dev)),
+               "mpe_policy_rows")
+    return list(out)
+
+
+class PolicyRowsGradResult(object):
+    """What policy_rows_grad_tensors wrote: dlogits_n, A views [M, n_i] of ONE flat float32 buffer `grads` (every block starts at a
+    multiple of 4 floats); with stats: loss [1] and stats [A, 8] (per agent mean q, mean z^2, mean entropy, 0, 0, 0, L_i, 0)."""
+    __slots__ = ("M", "n", "grads", "dlogits_n", "stats", "loss", "work")
+
+    STATS = ("q", "logits_sq", "entropy", "reserved", "reserved", "reserved", "loss", "reserved")
+
+
+def _rows_grad_result(n, M, dev):
+    r = PolicyRowsGradResult()
+    off, at = [], 0
+    for k in n:
+        off.append(at)
+        at += (M * k + 3) // 4 * 4
+    r.M, r.n = M, list(n)
+    r.grads = torch.zeros((max(at, 1),), dtype=torch.float32, device=dev)
+    r.dlogits_n = [r.grads[o:o + M * k].view(M, k) for o, k in zip(off, n)]
+    r.stats = torch.zeros((len(n), 8), dtype=torch.float32, device=dev)
+    r.loss = torch.zeros((1,), dtype=torch.float32, device=dev)
+    r.work = _work("mpe_policy_rows_grad_work", len(n), M, dev)
+    return r
+
+
+def policy_rows_grad_tensors(layout, logits_n, g_n, reg_coef=0.0, q=None, out=None):
+    """THE POLICY ROWS GRADIENT RULE in one launch (two with stats), no host synchronisation: dL/d(window) -> dL/dlogits through
+    the softmax Jacobian, plus the gradient of reg_coef * mean(logits^2).  g_n[i]: float32 [M, >= n_i] whose last dimension is
+    contiguous -- its row stride is the launch's ld (mlp_dinput_tensors' packed [M, n_i] window, or a [M, W] gradient's columns
+    col_i..: full[:, col_i:col_i + n_i]).  q [A, M]: the critics' values on policy_rows_tensors' rows; given: the launch also writes
+    the loss -mean q + reg_coef * mean z^2 and the stats.  out: a PolicyRowsGradResult to rewrite.  -> PolicyRowsGradResult."""
+    who = "policy_rows_grad_tensors"
+    lay = RowsLayout.of(layout, who)
+    M, dev = _logits_check(who, lay, logits_n)
+    if not isinstance(g_n, (list, tuple)) or len(g_n) != lay.A:
+        raise _abi.MpeError("%s: g_n is a list of %d tensors, one per agent" % (who, lay.A))
+    for i, (g, k) in enumerate(zip(g_n, lay.n)):
+        if not torch.is_tensor(g) or g.dtype != torch.float32 or g.dim() != 2 or g.shape[0] != M or g.shape[1] < k or \
+                (g.shape[1] > 1 and g.stride(1) != 1) or (M > 1 and g.stride(0) < k) or g.device != dev:
+            raise _abi.MpeError("%s: g_n[%d] is a float32 [%d, >= %d] tensor on logits_n[0]'s device, its last dimension contiguous and "
+                                "its row stride at least %d" % (who, i, M, k, k))
+    if not math.isfinite(float(reg_coef)) or float(reg_coef) < 0:
+        raise _abi.MpeError("%s: reg_coef = %r (a finite value >= 0)" % (who, reg_coef))
+    if q is not None:
+        check_tensor(who, q, "q", [(lay.A, M)], "logits_n[0]'s device", dev)
+    if out is not None and (not isinstance(out, PolicyRowsGradResult) or out.M != M or out.n != lay.n or out.grads.device != dev):
+        raise _abi.MpeError("%s: out is a PolicyRowsGradResult of the same heads and M = %d (what an earlier call returned)" % (who, M))
+    if not logits_n[0].is_cuda:
+        raise _abi.MpeError("%s: logits_n[0] is on %s (the tensors live on a GPU: there is no CPU path)" % (who, dev))
+    if out is None:
+        out = _rows_grad_result(lay.n, M, dev)
+    cfg = lay.cfg()
+    cfg.reg_coef = float(reg_coef)
+    for i, (g, k) in enumerate(zip(g_n, lay.n)):
+        cfg.ld[i] = max(int(g.stride(0)), k) if M > 1 else k
+    st = q is not None
+    _abi.check(_abi.lib().mpe_policy_rows_grad(C.byref(cfg), _ptrs(logits_n), _ptrs(g_n), M, _ptrs(out.dlogits_n),
+                                               q.data_ptr() if st else None, out.work.data_ptr() if st else None,
+                                               out.stats.data_ptr() if st else None, out.loss.data_ptr() if st else None,
+                                               _abi.raw_stream(dev)), "mpe_policy_rows_grad")
+    return out
+
+
+class _ActorLossFn(torch.autograd.Function):
+    """forward: rows, critics, dQ/d(window), softmax Jacobian -- four launches and the finish; backward: ONE multiply"""
+
+    @staticmethod
+    def forward(ctx, head, joint, *logits_n):
+        from .train import mlp_dinput_tensors      # (train.py imports this file)
+        lay, critics = head.layout, head.critics
+        zs = [z.detach() for z in logits_n]
+        M, dev = _logits_check("ActorLoss", lay, zs)
+        key = (M, dev)
+        bufs = head._out.get(key)
+        if bufs is None:
+            if not zs[0].is_cuda:
+                raise _abi.MpeError("ActorLoss: logits_n[0] is on %s (the tensors live on a GPU: there is no CPU path)" % (dev,))
+            bufs = head._out.get(key, lambda: ([torch.zeros((M, lay.W), dtype=torch.float32, device=dev) for _ in range(lay.A)],
+                                               torch.full((M,), -1.0, dtype=torch.float32, device=dev) / torch.tensor(float(M), dtype=torch.float32, device=dev),
+                                               _rows_grad_result(lay.n, M, dev)))
+        rows, dout, res = bufs
+        policy_rows_tensors(lay, joint, zs, out=rows)
+        packed = critics.packed()      # (one pair for the forward and the input gradient: a DeviceAdam's live buffer is followed)
+        q = critics._launch(rows, M, _packed=packed)[0]
+        g = mlp_dinput_tensors(critics, rows, [dout] * lay.A, cols=[(c, k) for c, k in zip(lay.col, lay.n)], packed=packed)
+        policy_rows_grad_tensors(lay, zs, g, head.reg_coef, q=q, out=res)
+        ctx.res, ctx.shapes, ctx.owner = res, [tuple(z.shape) for z in logits_n], (head, key, head._generation.next(key))
+        head.last = res
+        return res.loss.view(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        res = ctx.res
+        head, key, generation = ctx.owner
+        if head._generation.stale(key, generation):
+            raise _abi.MpeError("ActorLoss: backward() of a loss whose buffers a later forward with the same M has rewritten (the "
+                                "buffers are cached per M: call backward() before the next forward)")
+        g = grad_output * res.grads      # out of place: the buffer is rewritten by the next forward of the same M
+        at, grads = 0, []
+        for k, shape in zip(res.n, ctx.shapes):
+            grads.append(g[at:at + res.M * k].view(shape))
+            at += (res.M * k + 3) // 4 * 4
+        return (None, None) + tuple(grads)
+
+
+class ActorLoss(object):
+    """MADDPG's actor loss behind torch autograd: loss = ActorLoss(actors, critics, reg_coef=0.0)(logits_n, batch.joint) is the sum
+    over the agents of -mean Q_i(joint row with agent i's action window replaced by softmax(logits_i)) + reg_coef *
+    mean(logits_i^2).  The forward runs mpe_policy_rows, critics.q on the A row tensors, mlp_dinput_tensors (dout = -1 / M, the
+    windows) and mpe_policy_rows_grad with stats; the backward is ONE multiply of grad_output with the stored dlogits.  The
+    critics are a constant of the loss: whatever critics.packed() is at the call is read, so a DeviceAdam's live buffer is
+    followed.  actors: an Actors (its joint layout and heads), or a RowsLayout.  loss.stats [A, 8] carries
+    PolicyRowsGradResult.STATS; .last the result of the last call.  Buffers cached per M, as PpoLoss's."""
+
+    def __init__(self, actors, critics, reg_coef=0.0):
+        self.layout = RowsLayout.of(actors, "ActorLoss")
+        if not isinstance(critics, Critics):
+            raise _abi.MpeError("ActorLoss: critics is a Critics(env, modules)")
+        if critics.A != self.layout.A or critics.joint_width != self.layout.W:
+            raise _abi.MpeError("ActorLoss: the critics read %d agents' rows of %d floats, the layout has %d agents and W = %d"
+                                % (critics.A, critics.joint_width, self.layout.A, self.layout.W))
+        if not math.isfinite(float(reg_coef)) or float(reg_coef) < 0:
+            raise _abi.MpeError("ActorLoss: reg_coef = %r (a finite value >= 0)" % (reg_coef,))
+        self.critics, self.reg_coef = critics, float(reg_coef)
+        self._out, self._generation, self.last = Cache(), Generations(), None
+
+    def __call__(self, logits_n, joint):
+        who = "ActorLoss"
+        if not isinstance(logits_n, (list, tuple)) or len(logits_n) != self.layout.A:
+            raise _abi.MpeError("%s: logits_n is a list of %d tensors, one per agent" % (who, self.layout.A))
+        for i, t in enumerate(logits_n):
+            if not torch.is_tensor(t):
+                raise _abi.MpeError("%s: logits_n[%d] is not a tensor" % (who, i))
+        if not torch.is_tensor(joint) or joint.requires_grad:
+            raise _abi.MpeError("%s: joint is the batch's joint rows, a tensor that does not require grad" % who)
+        loss = _ActorLossFn.apply(self, joint, *logits_n)
+        loss.stats = self.last.stats
+        return loss

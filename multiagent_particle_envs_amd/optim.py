@@ -2,7 +2,8 @@
 MASTER copy in device memory, with Adam's moments in the same layout and the step count beside them, and `step()` updates all of
 them in place in TWO launches (mpe_adam_step: THE ADAM RULE of include/mpe_hip.h) from the packed gradients
 mpe_mlp_grad wrote.  The live buffers are attached to the nets (NetSet.attach): every forward launch reads the new weights, nothing
-repacks, and a captured PolicyLoop graph keeps working across updates.
+repacks, and a captured PolicyLoop graph keeps working across updates.  `PolyakTargets` is the soft target update of an off-policy
+learner on the same buffers: target = lerp(target, online, tau) for every pair in ONE launch (mpe_polyak).
 
     pi, V = Trainable(Actors(env, actor_modules, logits=True)), Trainable(Values(env, critic_modules))
     opt = DeviceAdam([pi, V], lr=3e-4, max_grad_norm=0.5)
@@ -224,3 +225,106 @@ class DeviceAdam(object):
     def skipped(self):
         """Steps skipped because the gradient norm was not finite.  This call SYNCHRONISES."""
         return int(self._read(8))
+
+
+class PolyakTargets(object):
+    """The soft target updates of an off-policy learner on the packed buffers, ONE launch for all pairs (mpe_polyak: THE POLYAK RULE of
+    include/mpe_hip.h): target = lerp(target, online, tau).  pairs: 1..MPE_ADAM_MAX_SETS of (online_net,
+    target_net), each an Actors / Values / Critics (or its Trainable).  The online net must be attached -- to a DeviceAdam, whose
+    live buffer is then read at every step, or through freeze() --; each target net is packed ONCE here into a persistent buffer
+    and reads that buffer from now on (net.attach): its modules' own parameters are NOT updated until write_back().  The packed
+    layouts of a pair are checked equal, as DeviceAdam.share checks them.  tau_tensor: a one-element float32 device tensor the
+    launch reads instead of tau (a schedule under a captured graph)."""
+
+    def __init__(self, pairs, tau, tau_tensor=None):
+        who = "PolyakTargets"
+        if not isinstance(pairs, (list, tuple)) or not 1 <= len(pairs) <= _abi.MPE_ADAM_MAX_SETS or \
+                any(not isinstance(p, (list, tuple)) or len(p) != 2 for p in pairs):
+            raise _abi.MpeError("%s: pairs is a list of 1..MPE_ADAM_MAX_SETS = %d (online_net, target_net) pairs" % (who, _abi.MPE_ADAM_MAX_SETS))
+        strip = lambda n: n.net if isinstance(n, Trainable) else n      # noqa: E731
+        self.online, self.targets = [strip(p[0]) for p in pairs], [strip(p[1]) for p in pairs]
+        for k, (on, tg) in enumerate(zip(self.online, self.targets)):
+            for name, net in (("online", on), ("target", tg)):
+                if not isinstance(net, (Actors, Values, Critics)):
+                    raise _abi.MpeError("%s: pairs[%d]'s %s net is an Actors, a Values or a Critics, or a Trainable of one (got %s)"
+                                        % (who, k, name, type(net).__name__))
+            if on is tg or any(a is b for a in on.modules for b in tg.modules):
+                raise _abi.MpeError("%s: pairs[%d]: the target net holds the online net's module objects (a target is a copy)" % (who, k))
+            if any(tg is other for other in self.targets[:k]):
+                raise _abi.MpeError("%s: pairs[%d]'s target net is pairs[%d]'s again" % (who, k, [tg is o for o in self.targets].index(True)))
+            if on.attached() is None:
+                raise _abi.MpeError("%s: pairs[%d]'s online net is not attached (give it to a DeviceAdam, or freeze() it: the step reads "
+                                    "its packed buffer)" % (who, k))
+            if tg.attached() is not None:
+                raise _abi.MpeError("%s: pairs[%d]'s target net is already frozen (unfreeze() it: the targets are packed once here)" % (who, k))
+        tau = float(tau)
+        if not math.isfinite(tau) or not 0.0 <= tau <= 1.0:
+            raise _abi.MpeError("%s: tau = %r (need 0 <= tau <= 1)" % (who, tau))
+        dev = self.online[0].world.device
+        for k, net in enumerate(self.online + self.targets):
+            if net.world.device != dev:
+                raise _abi.MpeError("%s: a net of pairs[%d] is on %s, pairs[0]'s online net on %s" % (who, k % len(pairs), net.world.device, dev))
+        if tau_tensor is not None:
+            if not torch.is_tensor(tau_tensor) or tau_tensor.dtype != torch.float32 or tau_tensor.numel() != 1 or tau_tensor.device != dev:
+                raise _abi.MpeError("%s: tau_tensor is a one-element float32 tensor on the nets' device (%s)" % (who, dev))
+        if dev.type != "cuda":
+            raise _abi.MpeError("%s: pairs[0]'s online net is on %s (the buffers live on a GPU: there is no CPU path)" % (who, dev))
+        self.device, self.tau, self.tau_tensor = dev, tau, tau_tensor
+        self._cfg = _abi.MpePolyak()
+        self._cfg.tau, self._cfg.n_sets = tau, len(pairs)
+        self._cfg.tau_ptr = tau_tensor.data_ptr() if tau_tensor is not None else None
+        self.weights, self._online_w = [], []
+        packs = []
+        for k, (on, tg) in enumerate(zip(self.online, self.targets)):
+            wts, aset = tg.pack(dev)
+            wts = wts.contiguous()
+            own, oset = on.attached()
+            if wts.numel() != own.numel() or list(aset.offset) != list(oset.offset):
+                raise _abi.MpeError("%s: pairs[%d]: the target's packed layout differs from the online net's (offsets %s against %s)"
+                                    % (who, k, list(aset.offset)[:tg.A], list(oset.offset)[:on.A]))
+            aset.weights = wts.data_ptr()
+            packs.append((wts, aset))
+            self.weights.append(wts)
+            self._online_w.append(own)
+            s = self._cfg.set[k]
+            s.target, s.online, s.n = wts.data_ptr(), own.data_ptr(), wts.numel()
+        for tg, pair in zip(self.targets, packs):
+            tg.attach(pair)
+
+    def _check(self, who):
+        for k, (on, tg) in enumerate(zip(self.online, self.targets)):
+            pair = tg.attached()
+            if pair is None or pair[0] is not self.weights[k]:
+                raise _abi.MpeError("%s: pairs[%d]'s target net no longer reads the live buffer (freeze() / unfreeze() was called on it: "
+                                    "the step would update weights nobody reads -- release() first)" % (who, k))
+            pair = on.attached()
+            if pair is None or pair[0] is not self._online_w[k]:
+                raise _abi.MpeError("%s: pairs[%d]'s online net no longer reads the buffer the step was built on (freeze() / unfreeze() "
+                                    "was called on it, or its optimiser was released)" % (who, k))
+
+    def step(self):
+        """One mpe_polyak for all pairs, no host synchronisation (captures into a HIP graph)."""
+        self._check("PolyakTargets.step")
+        _abi.check(_abi.lib().mpe_polyak(C.byref(self._cfg), _abi.raw_stream(self.device)), "mpe_polyak")
+
+    def hard_update(self):
+        """target := online, a plain copy of every buffer."""
+        self._check("PolyakTargets.hard_update")
+        for wts, own in zip(self.weights, self._online_w):
+            wts.copy_(own)
+        return self
+
+    def write_back(self):
+        """Copy the target buffers into the target modules' parameters (plain torch, off the hot path)."""
+        for net, wts in zip(self.targets, self.weights):
+            at = 0
+            for _, lins in net.distinct():
+                at += unpack_layers(lins, wts, at=at)
+        return self
+
+    def release(self):
+        """write_back(), then every target net packs from its modules again (nothing stays attached)."""
+        self.write_back()
+        for net in self.targets:
+            net.attach(None)
+        return self
