@@ -211,6 +211,26 @@ int mpe_random_comm(float *comm, int32_t n_agents, int64_t B, int32_t dim_c, uin
  * 1-2 adversaries; 1-3 good agents with 2-5 adversaries), 0 beyond it.                                */
 int mpe_step_supported(const MpeScenarioDesc *desc);
 
+/* mpe_wide_plan: which kernel of csrc/mpe_wide.hip (the shapes beyond the small-entity families: simple_spread / simple_tag / World.step
+ * with more than 16 entities) a call with these arguments launches -- host arithmetic only, nothing reaches the HIP runtime; the launch
+ * switches on the same function's result, so the answer is what runs.  phys / out: the call's halves (mpe_step 1 1, mpe_world_step 1 0,
+ * mpe_observe 0 1); roll: mpe_rollout_random / mpe_rollout_actions (needs phys and out).  The choice reads the descriptor, B and the
+ * alignment of bufs->obs; bufs->entity_table must be set as for the launch.  Returns an MpeWidePlan value, MPE_WIDE_NONE (0) when a
+ * kernel of another family takes the call, < 0 as the launch would (MPE_EUNSUPPORTED: no kernel; a movable landmark: mpe_world_step
+ * rewrites such a descriptor itself and is not answered here).  *homo (may be NULL): 1 when the kernel takes the agents' constants from
+ * its arguments -- identical agents, no colliding landmark -- 0 when it reads them from bufs->entity_table.                          */
+enum MpeWidePlan {
+  MPE_WIDE_NONE = 0,
+  MPE_WIDE_WAVE = 1,     /* k_wave: one wave per world                                             */
+  MPE_WIDE_MULTI8 = 2,   /* k_multi: several worlds per wave, 8 / 16 / 32 lanes per world           */
+  MPE_WIDE_MULTI16 = 3,
+  MPE_WIDE_MULTI32 = 4,
+  MPE_WIDE_DUO = 5,      /* k_duo: two waves per world (the fused spread step of 33..64 identical agents) */
+  MPE_WIDE_DUO_ROLL = 6  /* k_duo_roll: the T-step rollout on k_duo's plan                         */
+};
+int mpe_wide_plan(const MpeScenarioDesc *desc, const MpeBuffers *bufs, int64_t B, int32_t phys, int32_t out, int32_t roll,
+                  int32_t *homo_out);
+
 /* Episode bookkeeping -- NEW API, no reference counterpart: `done` is always False in the reference
  * (environment.py:132-135, make_env.py:41-43: no done_callback) and the caller counts steps itself
  * (bin/interactive.py, MADDPG's 25-step episodes).  After a step: episode_step[w] += 1 for every

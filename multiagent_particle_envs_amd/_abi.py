@@ -13,6 +13,8 @@ MPE_SCN_GENERIC, MPE_SCN_SIMPLE, MPE_SCN_SPREAD, MPE_SCN_TAG, MPE_SCN_ADVERSARY,
 MPE_SCN_SPEAKER_LISTENER, MPE_SCN_REFERENCE, MPE_SCN_CRYPTO, MPE_SCN_WORLD_COMM = 6, 7, 8, 9
 COMM_KINDS = (MPE_SCN_SPEAKER_LISTENER, MPE_SCN_REFERENCE, MPE_SCN_CRYPTO, MPE_SCN_WORLD_COMM)   # agents speak: MpeBuffers.comm
 MPE_MAX_CHOICES = 4
+# enum MpeWidePlan: what mpe_wide_plan answers (csrc/mpe_wide.hip's kernels)
+MPE_WIDE_NONE, MPE_WIDE_WAVE, MPE_WIDE_MULTI8, MPE_WIDE_MULTI16, MPE_WIDE_MULTI32, MPE_WIDE_DUO, MPE_WIDE_DUO_ROLL = range(7)
 # the composable output stage (include/mpe_hip.h, enum MpeRowOp)
 MPE_ROWS_MAX_ENTITIES = 64
 MPE_ROW_SELF = 255
@@ -192,7 +194,9 @@ EXPORTS = {
     "mpe_fill_obs_layout": (C.c_int, [C.POINTER(MpeScenarioDesc)]),
     "mpe_fill_entity_table": (C.c_int, [C.POINTER(MpeScenarioDesc), C.POINTER(C.c_float)]),
     "mpe_step_supported": (C.c_int, [C.POINTER(MpeScenarioDesc)]),
-    "mpe_step": (C.c_int, [C.POINTER(MpeScenarioDesc), C.POINTER(MpeBuffers), C.c_int64, C.c_void_p]),
+    "mpe_wide_plan": (C.c_int, [C.POINTER(MpeScenarioDesc), C.POINTER(MpeBuffers), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                C.POINTER(C.c_int32)]),
+    "mpe_step":(C.c_int, [C.POINTER(MpeScenarioDesc), C.POINTER(MpeBuffers), C.c_int64, C.c_void_p]),
     "mpe_step_thread": (C.c_int, [C.POINTER(MpeScenarioDesc), C.POINTER(MpeBuffers), C.c_int64, C.c_void_p]),
     "mpe_observe": (C.c_int, [C.POINTER(MpeScenarioDesc), C.POINTER(MpeBuffers), C.c_int64, C.c_void_p]),
     "mpe_world_step": (C.c_int, [C.POINTER(MpeScenarioDesc), C.POINTER(MpeBuffers), C.c_int64, C.c_void_p]),
@@ -360,6 +364,15 @@ def replay_prio_layout(n_leaves):
     levels, off, n = C.c_int32(0), (C.c_int64 * (MPE_REPLAY_PRIO_MAX_LEVELS + 1))(), C.c_int64(0)
     check(lib().mpe_replay_prio_layout(int(n_leaves), C.byref(levels), off, C.byref(n)), "mpe_replay_prio_layout")
     return list(off[:levels.value + 1]), n.value
+
+
+def wide_plan(desc, bufs, B, phys=True, out=True, roll=False):
+    """mpe_wide_plan (host only) -> (MPE_WIDE_* of the kernel such a call launches, homo)."""
+    homo = C.c_int32(0)
+    plan = lib().mpe_wide_plan(C.byref(desc), C.byref(bufs), int(B), int(phys), int(out), int(roll), C.byref(homo))
+    if plan < 0:
+        check(plan, "mpe_wide_plan")
+    return plan, bool(homo.value)
 
 
 def raw_stream(device):

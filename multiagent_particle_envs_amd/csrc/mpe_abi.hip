@@ -308,6 +308,14 @@ int mpe_fill_entity_table(const MpeScenarioDesc *d, float *out) {
   return mpe::kEntityTableCols * E;
 }
 
+// does a step / observe call go to the wave-per-agent kernels (mpe_split.hip)?  `use` is d, or d as kind GENERIC for a physics-only call
+// (an observe-only call goes to the thread-per-world kernel where one exists -- no barrier, no exchange block needed --
+//  and to the wave-per-agent kernel's observe half for the shapes that exist there only)
+static bool takes_split(const MpeScenarioDesc *d, const MpeScenarioDesc *use, bool phys, bool out, int kind, StepImpl impl) {
+  const bool comm_kind = kind >= MPE_SCN_SPEAKER_LISTENER;   // these exist as wave-per-agent kernels only
+  return out && (phys || comm_kind || !use_narrow(use)) && (comm_kind || impl != StepImpl::Thread) && has_kernel(d, mpe::split_supports);
+}
+
 static int run(const char *what, bool phys, bool out, const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B,
                void *stream, StepImpl impl = StepImpl::Split) {
   if (int rc = check_desc(d, what)) return rc;
@@ -347,11 +355,7 @@ static int run(const char *what, bool phys, bool out, const MpeScenarioDesc *d, 
     dd.n_agents = n_dyn;
     use = &dd;
   }
-  const bool comm_kind = kind >= MPE_SCN_SPEAKER_LISTENER;   // these exist as wave-per-agent kernels only
-  // (an observe-only call goes to the thread-per-world kernel where one exists -- no barrier, no exchange block needed --
-  //  and to the wave-per-agent kernel's observe half for the shapes that exist there only)
-  if (out && (phys || comm_kind || !use_narrow(use)) && (comm_kind || impl != StepImpl::Thread) &&
-      has_kernel(d, mpe::split_supports)) {
+  if (takes_split(d, use, phys, out, kind, impl)) {
     // the fused step: wave-per-agent / lane-per-world (mpe_split.hip)
     const mpe::NarrowDesc n = make_narrow(use, b, (size_t)B);
     mpe::RollArgs ra = roll_args(1, 0, 0, 0.f, 0, 0, 0, nullptr);
@@ -384,6 +388,48 @@ int mpe_step_supported(const MpeScenarioDesc *d) {
   mpe::WideDesc w = make_wide(d);
   w.kind = d->kind;
   return mpe::wide_supports(w, true) ? 1 : 0;
+}
+
+int mpe_wide_plan(const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B, int32_t phys, int32_t out, int32_t roll, int32_t *homo) {
+  const char *what = "mpe_wide_plan";
+  if (int rc = check_desc(d, what)) return rc;
+  if (!b) return fail(MPE_EINVAL, "%s: bufs is NULL", what);
+  if (B < 0) return fail(MPE_EINVAL, "%s: B < 0", what);
+  if (!phys && !out) return fail(MPE_EINVAL, "%s: a call has a physics half, an output half or both (phys = out = 0)", what);
+  if (roll && !(phys && out)) return fail(MPE_EINVAL, "%s: a rollout steps and writes outputs (roll needs phys and out)", what);
+  if (out && d->kind == MPE_SCN_GENERIC) return fail(MPE_EINVAL, "%s: kind GENERIC has no output stage", what);
+  if (out) if (int rc = need(b->obs, what, "obs")) return rc;   // (its alignment is part of the choice)
+  if (first_movable_landmark(d) >= 0)
+    return fail(MPE_EUNSUPPORTED, "%s: movable landmarks are stepped by mpe_world_step on a descriptor of its own making", what);
+  const int kind = out ? d->kind : MPE_SCN_GENERIC;
+  MpeScenarioDesc dd;
+  const MpeScenarioDesc *use = d;
+  if (!out && d->kind != MPE_SCN_GENERIC) {  // physics-only call on a built-in scenario, as run() takes it
+    dd = *d;
+    dd.kind = MPE_SCN_GENERIC;
+    use = &dd;
+  }
+  // the shapes that never reach mpe_wide.hip: run()'s and rollout_fused()'s own order
+  if (roll ? has_kernel(d, mpe::split_supports) : (takes_split(d, use, phys, out, kind, StepImpl::Split) || use_narrow(use))) {
+    if (homo) *homo = 0;
+    return MPE_WIDE_NONE;
+  }
+  if (kind != MPE_SCN_GENERIC && kind != MPE_SCN_SPREAD && kind != MPE_SCN_TAG)
+    return fail(MPE_EUNSUPPORTED, "%s: no kernel for kind=%d A=%d L=%d n_adv=%d", what, d->kind, d->n_agents, d->n_landmarks,
+                d->n_adversaries);
+  if (int rc = need(b->entity_table, what, "entity_table (required by the wave-per-world kernel)")) return rc;
+  mpe::WideDesc w = make_wide(use);
+  w.kind = kind;
+  if (homo) *homo = w.homo;
+  const mpe::WidePlan plan = mpe::wide_plan(phys, out, w, *b, (size_t)B, roll != 0);
+  switch (plan.kernel) {
+    case mpe::WideKernel::Wave: return MPE_WIDE_WAVE;
+    case mpe::WideKernel::Multi: return plan.AP == 8 ? MPE_WIDE_MULTI8 : plan.AP == 16 ? MPE_WIDE_MULTI16 : MPE_WIDE_MULTI32;
+    case mpe::WideKernel::Duo: return MPE_WIDE_DUO;
+    case mpe::WideKernel::DuoRoll: return MPE_WIDE_DUO_ROLL;
+    case mpe::WideKernel::Unsupported: break;
+  }
+  return hip_result(MPE_EUNSUPPORTED, what);
 }
 
 int mpe_step(const MpeScenarioDesc *d, const MpeBuffers *b, int64_t B, void *stream) {

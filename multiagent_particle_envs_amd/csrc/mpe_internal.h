@@ -36,6 +36,13 @@ struct WideDesc {
 constexpr int kEntityTableCols = 6;  // size, mass, accel, max_speed, movable, collide  -> [6][E] floats
 struct RollArgs;
 bool wide_supports(const WideDesc &d, bool out);
+// which kernel of mpe_wide.hip a call takes (host arithmetic, no HIP call): launch_wide switches on it, mpe_wide_plan reports it
+enum class WideKernel { Unsupported, Wave, Multi, Duo, DuoRoll };
+struct WidePlan {
+  WideKernel kernel;
+  int AP;   // Multi: lanes per world slot (8, 16 or 32)
+};
+WidePlan wide_plan(bool phys, bool out, const WideDesc &d, const MpeBuffers &b, size_t B, bool roll);
 int launch_wide(bool phys, bool out, const WideDesc &d, const MpeBuffers &b, size_t B, hipStream_t stream,
                 const RollArgs *roll = nullptr);
 

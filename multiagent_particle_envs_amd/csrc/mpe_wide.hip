@@ -8,7 +8,8 @@
 //   k_duo<G>                two waves per world, G worlds per workgroup: the fused spread step of 33..64 identical agents
 //                           (the N = 64 headline shape).
 //   k_duo_roll<G>           the fused T-step rollout on k_duo's plan.
-// launch_wide picks one.  The steps whose results must agree bit for bit (tests/test_gpu_parity.py, _rollout.py) are shared:
+// wide_plan picks one and launch_wide switches on it (mpe_wide_plan tells a caller which).  The steps whose results must agree
+// bit for bit (tests/test_gpu_parity.py, _rollout.py) are shared:
 //   near_mask32 / add_contacts   the two passes of the contact loop (all four; k_multi keeps its own copy of pass 2)
 //   rollout_move, EpisodeClock, reset_entity   a rollout step's move, its episode clock and in-launch reset_world draws
 //                                (k_wave<ROLL>, k_multi<ROLL>, k_duo_roll)
@@ -1464,19 +1465,42 @@ bool wide_supports(const WideDesc &d, bool out) {
   return cv.shared_bytes + kWavesPerWg * cv.wave_bytes <= kMaxLds;
 }
 
+// THE PLAN: which of the four kernels a call takes.  Host arithmetic only -- launch_wide switches on it, mpe_wide_plan reports
+// it, so the launch and the query cannot diverge.  (What is left to launch_wide is not a choice: grids, LDS bytes, rows_nt.)
+WidePlan wide_plan(bool phys, bool out, const WideDesc &d, const MpeBuffers &b, size_t B, bool roll) {
+  const WidePlan none = {WideKernel::Unsupported, 0};
+  if (out && d.kind != MPE_SCN_SPREAD && d.kind != MPE_SCN_TAG) return none;
+  if (out && (d.dim_c != 2 || (d.D & 1))) return none;
+  const Carve cv = carve(d.A, d.L);
+  if (cv.shared_bytes + kWavesPerWg * cv.wave_bytes > kMaxLds) return none;
+  const size_t groups = (B + kWavesPerWg - 1) / kWavesPerWg;
+  if ((groups + 63) / 64 * 64 > 0xffffffffull) return none;
+  const int amax = d.A > d.L ? d.A : d.L;
+  const size_t padded_w = (B + 255) / 256 * 256;   // whole 256-world blocks of the duo plan's XCD map
+  if (roll && duo_eligible(d, b, B, phys, out, false) && MPE_DUO_ROLL && padded_w <= 0x7fffffffull) return {WideKernel::DuoRoll, 0};
+  if (duo_eligible(d, b, B, phys, out, roll) && padded_w <= 0x7fffffffull) return {WideKernel::Duo, 0};
+  if ((!roll || (phys && out && amax <= MPE_MULTI_ROLL_MAX_N)) && amax <= 32 && d.A + d.L <= kWave && !(out && d.kind != MPE_SCN_SPREAD)) {
+    // several worlds per wave (k_multi): AP lanes per world slot
+    const int AP = amax <= 8 ? 8 : amax <= 16 ? 16 : 32, WPW = kWave / AP;
+    const size_t mlds = cv.shared_bytes + (size_t)kWavesPerWg * WPW * (2 * (d.A + d.L) + 2 * d.A) * sizeof(float2);
+    if (mlds <= 64 * 1024) return {WideKernel::Multi, AP};
+  }
+  if (roll && !(phys && out)) return none;
+  return {WideKernel::Wave, 0};
+}
+
 int launch_wide(bool phys, bool out, const WideDesc &d_in, const MpeBuffers &b, size_t B, hipStream_t stream,
                 const RollArgs *roll) {
   WideDesc d = d_in;
+  const WidePlan plan = wide_plan(phys, out, d, b, B, roll != nullptr);
+  if (plan.kernel == WideKernel::Unsupported) return MPE_EUNSUPPORTED;
   // rows may go out nontemporal when no 128-byte line is shared between two wave stores (mpe_device.h): a row (k_wave /
   // k_duo) resp. the rows of a wave's worlds for one agent index (k_multi, set below) is a whole number of lines
   const bool lines = out && d.kind == MPE_SCN_SPREAD && (reinterpret_cast<uintptr_t>(b.obs) & 127) == 0 &&
                      (((size_t)B * d.D * sizeof(float)) & 127) == 0;
   d.rows_nt = lines && ((d.D * sizeof(float)) & 127) == 0;
-  if (out && d.kind != MPE_SCN_SPREAD && d.kind != MPE_SCN_TAG) return MPE_EUNSUPPORTED;
-  if (out && (d.dim_c != 2 || (d.D & 1))) return MPE_EUNSUPPORTED;
   const Carve cv = carve(d.A, d.L);
   const size_t lds = cv.shared_bytes + kWavesPerWg * cv.wave_bytes;
-  if (lds > kMaxLds) return MPE_EUNSUPPORTED;
   static const int n_cu = [] {   // (a C++11 magic static: concurrent first calls from several host threads are fine)
     int dev = 0, v = 0;
     if (hipGetDevice(&dev) == hipSuccess &&
@@ -1489,7 +1513,6 @@ int launch_wide(bool phys, bool out, const WideDesc &d_in, const MpeBuffers &b, 
   // hence of 8: a workgroup's later iterations stay on its XCD's share of the worlds)
   const size_t groups = (B + kWavesPerWg - 1) / kWavesPerWg;
   const size_t padded = (groups + 63) / 64 * 64;
-  if (padded > 0xffffffffull) return MPE_EUNSUPPORTED;
   constexpr int bpc = 8;
   size_t cap = (size_t)n_cu * (size_t)bpc / 64 * 64;
   if (cap < 64) cap = 64;
@@ -1497,32 +1520,23 @@ int launch_wide(bool phys, bool out, const WideDesc &d_in, const MpeBuffers &b, 
   const unsigned np = (unsigned)padded;
   RollArgs ra;
   std::memset(&ra, 0, sizeof(ra));
-  const int amax = d.A > d.L ? d.A : d.L;
-  if (roll && duo_eligible(d, b, B, phys, out, false) && MPE_DUO_ROLL) {
-    constexpr int G = MPE_DUO_G;
-    const size_t padded_w = (B + 255) / 256 * 256;
-    if (padded_w <= 0x7fffffffull) {
+  constexpr int G = MPE_DUO_G;
+  const size_t padded_w = (B + 255) / 256 * 256;   // two waves per world: worlds padded to whole 256-world blocks of the XCD map
+  switch (plan.kernel) {
+    case WideKernel::DuoRoll: {
       const size_t dlds = (size_t)G * duo_roll_carve(d.A, d.L).slot_bytes;
       hipLaunchKernelGGL(k_duo_roll<G>, dim3((unsigned)(padded_w / G)), dim3(2 * G * kWave), dlds, stream, d, b, B, *roll);
       return (int)hipGetLastError();
     }
-  }
-  if (duo_eligible(d, b, B, phys, out, roll != nullptr)) {
-    // two waves per world (k_duo): one workgroup per world, worlds padded to whole 256-world blocks of the XCD map
-    constexpr int G = MPE_DUO_G;
-    const size_t padded_w = (B + 255) / 256 * 256;   // whole 256-world blocks of the XCD map
-    if (padded_w <= 0x7fffffffull) {
+    case WideKernel::Duo: {
       const size_t dlds = (size_t)G * duo_carve(d.A, d.L).slot_bytes + (MPE_DUO_LDS_PAD);
       hipLaunchKernelGGL(k_duo<G>, dim3((unsigned)(padded_w / G)), dim3(2 * G * kWave), dlds, stream, d, b, B);
       return (int)hipGetLastError();
     }
-  }
-  if ((!roll || (phys && out && amax <= MPE_MULTI_ROLL_MAX_N)) && amax <= 32 && d.A + d.L <= kWave && !(out && d.kind != MPE_SCN_SPREAD)) {
-    // several worlds per wave (k_multi): AP lanes per world slot
-    const int AP = amax <= 8 ? 8 : amax <= 16 ? 16 : 32, WPW = kWave / AP;
-    d.rows_nt = lines && (((size_t)WPW * d.D * sizeof(float)) & 127) == 0;
-    const size_t mlds = cv.shared_bytes + (size_t)kWavesPerWg * WPW * (2 * (d.A + d.L) + 2 * d.A) * sizeof(float2);
-    if (mlds <= 64 * 1024) {
+    case WideKernel::Multi: {
+      const int AP = plan.AP, WPW = kWave / AP;
+      d.rows_nt = lines && (((size_t)WPW * d.D * sizeof(float)) & 127) == 0;
+      const size_t mlds = cv.shared_bytes + (size_t)kWavesPerWg * WPW * (2 * (d.A + d.L) + 2 * d.A) * sizeof(float2);
       const size_t mg = (B + (size_t)kWavesPerWg * WPW - 1) / ((size_t)kWavesPerWg * WPW);
       const size_t mp = (mg + 63) / 64 * 64;
       const dim3 mgrid((unsigned)(mp < cap ? mp : cap));
@@ -1532,6 +1546,9 @@ int launch_wide(bool phys, bool out, const WideDesc &d_in, const MpeBuffers &b, 
       else hipLaunchKernelGGL((k_multi<false, true, false>), mgrid, block, mlds, stream, d, b, B, (unsigned)mp, AP, ra);
       return (int)hipGetLastError();
     }
+    case WideKernel::Wave:
+    case WideKernel::Unsupported:
+      break;
   }
   if (lds > 64 * 1024) {  // beyond the default dynamic-LDS window: ask for it (a workgroup may own all 160 KiB of a gfx950 CU)
     const void *fn = roll ? (const void *)k_wave<true, true, true>
@@ -1542,10 +1559,8 @@ int launch_wide(bool phys, bool out, const WideDesc &d_in, const MpeBuffers &b, 
       return MPE_EUNSUPPORTED;
     }
   }
-  if (roll) {
-    if (!(phys && out)) return MPE_EUNSUPPORTED;
-    hipLaunchKernelGGL((k_wave<true, true, true>), grid, block, lds, stream, d, b, B, np, *roll);
-  } else if (phys && out) hipLaunchKernelGGL((k_wave<true, true, false>), grid, block, lds, stream, d, b, B, np, ra);
+  if (roll) hipLaunchKernelGGL((k_wave<true, true, true>), grid, block, lds, stream, d, b, B, np, *roll);
+  else if (phys && out) hipLaunchKernelGGL((k_wave<true, true, false>), grid, block, lds, stream, d, b, B, np, ra);
   else if (phys) hipLaunchKernelGGL((k_wave<true, false, false>), grid, block, lds, stream, d, b, B, np, ra);
   else hipLaunchKernelGGL((k_wave<false, true, false>), grid, block, lds, stream, d, b, B, np, ra);
   return (int)hipGetLastError();

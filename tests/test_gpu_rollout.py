@@ -79,9 +79,15 @@ def test_split_and_thread_kernels_bit_identical(name, kw, B):
                                             # >= 12 MB of rows per step: the rollout kernels built with nontemporal row stores
                                             ("simple_spread", {}, 65536, 3, 2), ("simple_world_comm", {}, 20000, 3, 2)])
 def test_fused_rollout_equals_stepwise(name, kw, B, T, ep):
+    fused_rollout_equals_stepwise(lambda seed: mpe.make_env(name, batch_size=B, seed=seed, **kw), B, T, ep)
+
+
+def fused_rollout_equals_stepwise(make, B, T, ep):
+    """The comparison itself, for any env: make(seed) -> a fresh env of B worlds (tests/test_gpu_wide_custom.py runs it on envs with
+    customised constants)."""
     seed, offset, step0 = 0xABCDEF0123, 4096, 50 if ep in (25, 0) else 14
     # --- stepwise: explicit reset / random_actions / step through the C ABI ----------------------
-    env_a = mpe.make_env(name, batch_size=B, seed=seed, **kw)
+    env_a = make(seed)
     env_a.world.world_offset = offset
     env_a._ensure_buffers()
     A = len(env_a.world.agents)
@@ -108,7 +114,7 @@ def test_fused_rollout_equals_stepwise(name, kw, B, T, ep):
         want_obs.append([o.clone() for o in env_a._sets[0].obs_n])
         want_rew.append(env_a._sets[0].rew.clone())
     # --- fused: one launch, trajectory outputs -----------------------------------------------------
-    env_b = mpe.make_env(name, batch_size=B, seed=seed, **kw)
+    env_b = make(seed)
     env_b.world.world_offset = offset
     env_b.world.pos.copy_(start_pos)
     env_b.world.vel.copy_(start_vel)
@@ -138,7 +144,7 @@ def test_fused_rollout_equals_stepwise(name, kw, B, T, ep):
             else:
                 assert not sample.pool_c[2][i].any()
     # --- overwrite mode leaves the last step's outputs in the env's buffers --------------------------
-    env_c = mpe.make_env(name, batch_size=B, seed=seed, **kw)
+    env_c = make(seed)
     env_c.world.world_offset = offset
     env_c.world.pos.copy_(start_pos)
     env_c.world.vel.copy_(start_vel)
