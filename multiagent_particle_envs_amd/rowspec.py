@@ -433,7 +433,10 @@ class RowProgram(object):
         functions the program's code ops call (symtrace.hip_source), appended to the generated header of the compiled form.
         reset_boxes: one (lo_x, hi_x, lo_y, hi_y) per entity -- reset_world places entity e uniformly in that box
         (`np.random.uniform(lo, hi, dim_p)`); every restart the library draws for this program (episode ends inside the launch,
-        rollouts, mpe_reset_rows) then uses it.  None: the reference's placement (agents [-1,1)^2, landmarks [-r,r)^2)."""
+        rollouts, mpe_reset_rows) then uses it.  None: the reference's placement (agents [-1,1)^2, landmarks [-r,r)^2).
+        The draw is lo + fl((hi - lo) * u) in float32 with u in [0, 1): never below lo nor above fl(lo + (hi - lo)), and below hi unless |lo| is large
+        next to the span (lo = 100, hi = 100.5 reaches 100.5 by rounding, as np.random.uniform may in float64) --
+        tests/test_oracle_philox.py walks all 2^24 values of u."""
         fuse = FUSE if fuse is None else fuse
         self.source = source
         A = len(world.agents)

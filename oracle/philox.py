@@ -4,7 +4,8 @@ Restates csrc/mpe_device.h's counter layout independently so that the device-sid
 (`mpe_reset`) and synthetic actions (`mpe_random_actions`) can be checked BIT-EXACTLY:
 integer work, so the bar is equality.  The generator itself is pinned to the published
 known-answer vectors of Random123 (Salmon et al., SC'11; `kat_vectors` philox4x32-10 rows) in
-tests/test_oracle_philox.py.
+tests/test_oracle_philox.py, which also holds the device functions themselves (compiled for the host) to this file at every
+counter edge; tests/test_gpu_draws.py holds the entry points of csrc/mpe_rng.hip to it on the device.
 """
 import numpy as np
 
@@ -61,6 +62,31 @@ def reset_positions(seed, batch, episode, n_agents, n_landmarks, landmark_range,
     return pos
 
 
+def reset_positions_box(seed, batch, episode, boxes, world_offset=0):
+    """pos [B, E, 2] float32 as mpe_reset_rows draws them with per-entity boxes (csrc/mpe_device.h reset_draw_box):
+    reset_positions' counter layout; boxes[e] = (lo_x, span_x, lo_y, span_y) as float32; x = lo + fl(span * u), every operation
+    rounded to float32, no fused multiply-add."""
+    boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
+    E = boxes.shape[0]
+    b = np.arange(batch, dtype=np.uint64) + np.uint64(world_offset)
+    pos = np.zeros((batch, E, 2), np.float32)
+    for pair in range((E + 1) // 2):
+        c0 = b & MASK
+        c1 = ((b >> np.uint64(32)) ^ np.uint64((episode >> 32) & 0xFFFFFFFF)) & MASK
+        c2 = np.full(batch, pair, np.uint64)
+        c3 = np.full(batch, (STREAM_RESET ^ (episode & 0xFFFFFFFF)) & 0xFFFFFFFF, np.uint64)
+        o = philox4x32_10(c0, c1, c2, c3, seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+        for half in range(2):
+            e = 2 * pair + half
+            if e >= E:
+                break
+            for axis in range(2):
+                u = (o[2 * half + axis] >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+                p = (boxes[e, 2 * axis + 1] * u).astype(np.float32)
+                pos[:, e, axis] = (boxes[e, 2 * axis] + p).astype(np.float32)
+    return pos
+
+
 def reset_choices(seed, batch, episode, pops, world_offset=0):
     """choice [K, B] int32 as mpe_reset draws the per-world picks (goal landmark, ...) for `episode`."""
     b = np.arange(batch, dtype=np.uint64) + np.uint64(world_offset)
@@ -113,6 +139,16 @@ def comm_ids(seed, batch, step, n_agents, dim_c, world_offset=0):
                 break
             ids[i] = ((o[k].astype(np.uint64) * np.uint64(dim_c)) >> np.uint64(32)).astype(np.int32)
     return ids
+
+
+def action_ids_block(seed, batch, step0, T, n_agents, world_offset=0):
+    """ids [T, A, B] int32 as mpe_random_actions_block draws them for the global steps step0 .. step0 + T - 1 (64-bit wrap)."""
+    return np.stack([action_ids(seed, batch, (step0 + s) & 0xFFFFFFFFFFFFFFFF, n_agents, world_offset) for s in range(T)])
+
+
+def comm_ids_block(seed, batch, step0, T, n_agents, dim_c, world_offset=0):
+    """words [T, A, B] int32 as mpe_random_comm draws them for the global steps step0 .. step0 + T - 1."""
+    return np.stack([comm_ids(seed, batch, (step0 + s) & 0xFFFFFFFFFFFFFFFF, n_agents, dim_c, world_offset) for s in range(T)])
 
 
 def one_hot(ids, n=5):

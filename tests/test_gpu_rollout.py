@@ -82,10 +82,10 @@ def test_fused_rollout_equals_stepwise(name, kw, B, T, ep):
     fused_rollout_equals_stepwise(lambda seed: mpe.make_env(name, batch_size=B, seed=seed, **kw), B, T, ep)
 
 
-def fused_rollout_equals_stepwise(make, B, T, ep):
+def fused_rollout_equals_stepwise(make, B, T, ep, seed=0xABCDEF0123, offset=4096, step0=None):
     """The comparison itself, for any env: make(seed) -> a fresh env of B worlds (tests/test_gpu_wide_custom.py runs it on envs with
-    customised constants)."""
-    seed, offset, step0 = 0xABCDEF0123, 4096, 50 if ep in (25, 0) else 14
+    customised constants; tests/test_gpu_draws.py at the counters' edges: seed, offset, step0)."""
+    step0 = (50 if ep in (25, 0) else 14) if step0 is None else step0
     # --- stepwise: explicit reset / random_actions / step through the C ABI ----------------------
     env_a = make(seed)
     env_a.world.world_offset = offset
