@@ -395,7 +395,7 @@ __host__ __device__ inline uint64_t replay_bits(uint64_t seed, uint64_t k, uint6
   return (k & 1) ? ((uint64_t)o.z << 32 | o.w) : ((uint64_t)o.x << 32 | o.y);
 }
 
-// ---- actors: the activation and the head rule, shared by k_split<POL> and mpe_policy.hip ----------------
+// ---- actors: pol_act, shared by k_split<POL> and mpe_policy.hip; pol_head, mpe_policy.hip's (decide() has its own copy)
 // Tanh is 1 - 2 / (exp(2x) + 1) on v_exp_f32 (absolute error < 2e-7).
 __device__ __forceinline__ float pol_act(float x, bool tnh) {
   if (tnh) return 1.f - __fdividef(2.f, __builtin_amdgcn_exp2f(x * 2.88539008177792681f) + 1.f);
