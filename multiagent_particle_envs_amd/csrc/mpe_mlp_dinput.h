@@ -5,7 +5,8 @@
 // workspace and the second launch are gone.  What is new is P8 and the store.  Plain C++ with no device builtin:
 // csrc/mpe_mlp_dinput.hip adds the grid, the LDS, the barriers and the MFMA, and tests/c/mlp_dinput_host_walk.cpp compiles these
 // functions with the host compiler and walks every workgroup, wave, lane and step under the sanitizers.  -1: an operand that is not
-// read (the lane hands the MFMA +0.0f), or a result that goes nowhere.
+// read (the lane hands the MFMA +0.0f), or a result that goes nowhere.  The shared phases are the functions of csrc/mpe_mlp_device.h
+// (the walks': tests/c/mlp_walk.h), taken here with SumFour -- the four chains and md_pre below -- where k_mlp_grad takes SumForward.
 //
 // Grid (blocks, A), 256 lanes = 4 waves.  A block walks md_span(M) consecutive groups of 64 rows, ascending, with W1, WL and the biases
 // staged once.  Per group, behind P0 -> P1 (-> P2) -> P4 (-> P6), delta_0 stands in tile T1 (tile DL for a one-layer net), and the

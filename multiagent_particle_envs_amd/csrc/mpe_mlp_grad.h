@@ -5,6 +5,8 @@
 // (adding the grid, the LDS, the barriers and the MFMA itself), and tests/c/mlp_grad_host_walk.cpp compiles the very same functions
 // with the host compiler and walks every chunk, wave, lane and step of both launches under AddressSanitizer on exact-size buffers,
 // the MFMA replaced by its definition.  An index of -1 stands for an operand that is not read: the lane hands the MFMA +0.0f.
+// The staging and P0, P1, P2, P4, P6 below are k_mlp_dinput's as well (mpe_mlp_dinput.h): they are written once for the device in
+// csrc/mpe_mlp_device.h and once for the two host walks in tests/c/mlp_walk.h, with the way a sum is taken as a template argument.
 //
 // The first launch.  Grid (chunks, A), 256 lanes = 4 waves.  A chunk is `span` consecutive GROUPS of 64 rows; the workgroup walks its
 // groups in ascending order and keeps the chunk's dW tiles in accumulator registers (a group's own 32 steps: mg_chain).  Per group (tiles are [unit][row], stride 65):

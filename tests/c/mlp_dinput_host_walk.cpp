@@ -1,69 +1,20 @@
 // mlp_dinput_host_walk.cpp -- every workgroup, wave, lane and step of mpe_mlp_dinput's launch on the host: the index functions of
 // csrc/mpe_mlp_dinput.h (and those of csrc/mpe_mlp_grad.h it uses), compiled by the host compiler, address exact-size heap buffers
 // (global memory and the workgroup's LDS arrays alike) under -fsanitize=address,undefined; the MFMA is replaced by its definition
-// (D[row][col] = fma(A[row][1], B[1][col], fma(A[row][0], B[0][col], C[row][col])), operands and results in the lanes mpe_mlp_grad.h
-// states), so what the walk writes is din itself.  Between two barriers a float of LDS may be written by one lane only and read by no
+// (mlp_walk.h), so what the walk writes is din itself.  Between two barriers a float of LDS may be written by one lane only and read by no
 // other lane than its writer.  Every float of din is counted: a live row's window floats are written exactly once, nothing else at all.
+// The staging and P0, P1, P2, P4, P6 are mlp_walk.h's, taken with the four-chain sum; P8, ST, the store accounting and every
+// barrier() are here.
 //   mlp_dinput_host_walk <in> <out>
 //   in:  int32 A; int64 M; per agent int32 nl, act, width[4], off, col0, ncol, ld, rows (>= M: rows of the din buffer), shift (floats
 //        the window's first float stands behind a 16-byte boundary); int32 n_weights; float weights[]; per agent float in[M * D],
 //        float dout[M * n_out]
 //   out: per agent float din[PAD + shift + rows * ld + PAD] as the walk left it (filled with SENTINEL before)
 //   stdout: "<blocks> blocks of <span> groups; agent <i>: <16-byte stores> 16-byte stores, <4-byte stores> 4-byte stores" ...
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "mpe_mlp_dinput.h"
-
-using namespace mpe;
-
-#define CHECK(c, ...) do { if (!(c)) { std::fprintf(stderr, __VA_ARGS__); std::fprintf(stderr, "\n"); std::exit(2); } } while (0)
+#include "mlp_walk.h"      // CHECK, Lds, Acc, the MFMA, the two sums and the walks of the phases mlp_grad_host_walk.cpp runs as well
 
 constexpr int PAD = 8;
 constexpr float SENTINEL = -777.25f;
-
-struct Lds {      // one __shared__ array: exact size, and who touched what since the last barrier
-  float *p;
-  int n;
-  std::vector<int> w, r;
-  explicit Lds(int n_) : p(new float[n_]), n(n_), w(n_, -1), r(n_, -1) {}
-  ~Lds() { delete[] p; }
-  float rd(int idx, int tid) {
-    r[idx] = r[idx] == -1 || r[idx] == tid ? tid : -2;
-    return p[idx];
-  }
-  void wr(int idx, int tid, float v) {
-    CHECK(w[idx] == -1, "two writes of LDS float %d between two barriers (lanes %d, %d)", idx, w[idx], tid);
-    w[idx] = tid;
-    p[idx] = v;
-  }
-  void barrier() {
-    for (int k = 0; k < n; ++k) {
-      CHECK(w[k] == -1 || r[k] == -1 || r[k] == w[k], "LDS float %d: written by lane %d and read by another between two barriers", k, w[k]);
-      w[k] = r[k] = -1;
-    }
-  }
-};
-
-typedef float Acc[64][16];
-static void mfma(const float *a, const float *b, Acc acc) {
-  for (int lane = 0; lane < 64; ++lane)
-    for (int r = 0; r < 16; ++r) {
-      const int row = mg_trow(r, lane >> 5), col = lane & 31;
-      acc[lane][r] = fmaf(a[row + 32], b[col + 32], fmaf(a[row], b[col], acc[lane][r]));
-    }
-}
-static void zero(Acc a) { std::memset(a, 0, sizeof(Acc)); }
-// a sum's steps: chains[mg_chain(s)] takes step s; the sum is their fold
-static Acc chains[kMgChains];
-static void chains_zero() { for (int q = 0; q < kMgChains; ++q) zero(chains[q]); }
-static void chains_fold(Acc acc) {
-  for (int lane = 0; lane < 64; ++lane)
-    for (int r = 0; r < 16; ++r) acc[lane][r] = mg_fold4(chains[0][lane][r], chains[1][lane][r], chains[2][lane][r], chains[3][lane][r]);
-}
 
 struct Walk {
   MlpDinputArgs a;
@@ -84,16 +35,7 @@ void Walk::block(int ag, uint64_t blk) {
   const int64_t ld = a.ld[ag];
   const float *Wg = a.w + a.off[ag], *in = a.in[ag], *dout = a.dout[ag];
   float *din = a.din[ag];
-  for (int tid = 0; tid < kMgThreads; ++tid) {
-    if (nl >= 2) {
-      for (int idx = tid; idx < kMgHW * kMgLW; idx += kMgThreads) sWL.wr(mg_wl_at(idx), tid, Wg[mg_off_wl(nl, D) + idx]);
-      if (tid < kMgHW) sB0.wr(tid, tid, Wg[mg_off_b0(nl, D) + tid]);
-    }
-    if (nl == 3) {
-      for (int idx = tid; idx < kMgHW * kMgHW; idx += kMgThreads) sW1.wr(mg_w1_at(idx), tid, Wg[mg_off_w1(D) + idx]);
-      if (tid < kMgHW) sB1.wr(tid, tid, Wg[mg_off_b1(D) + tid]);
-    }
-  }
+  walk_stage(sWL, sB0, sW1, sB1, Wg, nl, D);
   static Acc acc;
   Lds &TH = nl == 3 ? sT2 : sT1;
   Lds &D0 = nl == 1 ? sDL : sT1;
@@ -102,82 +44,21 @@ void Walk::block(int ag, uint64_t blk) {
   const uint64_t g0 = blk * span, g1 = g0 + span < groups ? g0 + span : groups;
   CHECK(g0 < g1, "block %llu of agent %d has no group", (unsigned long long)blk, ag);
   float av[64], bv[64];
-  // a forward layer's results of one wave (bias: the layer's staged biases, added last) or a delta step's (bias: none)
-  auto store_act = [&](Lds &T, int wave, Lds *bias) {
-    for (int lane = 0; lane < 64; ++lane)
-      for (int r = 0; r < 16; ++r) {
-        const int i = lane & 31, h = lane >> 5, o = mg_fwd_out(r, i, h, wave & 1, wave >> 1), tid = 64 * wave + lane;
-        if (bias) T.wr(o, tid, mg_act(md_pre(acc[lane][r], bias->rd(mg_fwd_unit(r, h, wave >> 1), tid)), tnh));
-        else T.wr(o, tid, mg_dact(acc[lane][r], T.rd(o, tid), tnh));
-      }
-  };
   for (uint64_t g = g0; g < g1; ++g) {
     const uint64_t row0 = g * kMgRows;
     barrier();
-    for (int tid = 0; tid < kMgThreads; ++tid)      // P0
-      for (int idx = tid; idx < kMgLW * kMgRows; idx += kMgThreads) {
-        const int64_t src = mg_p0_src(idx, row0, M, n);
-        sDL.wr(mg_p0_dst(idx), tid, src >= 0 ? dout[src] : 0.f);
-      }
-    if (nl >= 2)      // P1
-      for (int wave = 0; wave < kMgWaves; ++wave) {
-        const int wt = wave & 1, m = wave >> 1;
-        chains_zero();
-        for (int s = 0; s < mg_p1_steps(D); ++s) {
-          for (int lane = 0; lane < 64; ++lane) {
-            const int ia = mg_p1_a(s, lane & 31, lane >> 5, m, D);
-            const int64_t ib = mg_p1_b(s, lane & 31, lane >> 5, wt, D, row0, M);
-            av[lane] = ia >= 0 ? Wg[ia] : 0.f, bv[lane] = ib >= 0 ? in[ib] : 0.f;
-          }
-          mfma(av, bv, chains[mg_chain(s)]);
-        }
-        chains_fold(acc);
-        store_act(sT1, wave, &sB0);
-      }
+    walk_p0(sDL, dout, row0, M, n);
+    if (nl >= 2) walk_p1<SumFour>(sT1, sB0, Wg, in, D, row0, M, tnh);
     barrier();
-    if (nl == 3) {      // P2
-      for (int wave = 0; wave < kMgWaves; ++wave) {
-        const int wt = wave & 1, m = wave >> 1;
-        chains_zero();
-        for (int s = 0; s < mg_p2_steps(w1); ++s) {
-          for (int lane = 0; lane < 64; ++lane) {
-            av[lane] = sW1.rd(mg_p2_a(s, lane & 31, lane >> 5, m), 64 * wave + lane);
-            bv[lane] = sT1.rd(mg_p2_b(s, lane & 31, lane >> 5, wt), 64 * wave + lane);
-          }
-          mfma(av, bv, chains[mg_chain(s)]);
-        }
-        chains_fold(acc);
-        store_act(sT2, wave, &sB1);
-      }
+    if (nl == 3) {
+      walk_p2<SumFour>(sT2, sW1, sB1, sT1, w1, tnh);
       barrier();
     }
     if (nl >= 2) {
-      for (int wave = 0; wave < kMgWaves; ++wave) {      // P4
-        chains_zero();
-        for (int s = 0; s < kMgLW / 2; ++s) {
-          for (int lane = 0; lane < 64; ++lane) {
-            av[lane] = sWL.rd(mg_p4_a(s, lane & 31, lane >> 5, wave >> 1), 64 * wave + lane);
-            bv[lane] = sDL.rd(mg_p4_b(s, lane & 31, lane >> 5, wave & 1), 64 * wave + lane);
-          }
-          mfma(av, bv, chains[mg_chain(s)]);
-        }
-        chains_fold(acc);
-        store_act(TH, wave, nullptr);
-      }
+      walk_p4<SumFour>(TH, sWL, sDL, tnh);
       barrier();
       if (nl == 3) {
-        for (int wave = 0; wave < kMgWaves; ++wave) {      // P6
-          chains_zero();
-          for (int s = 0; s < 32; ++s) {
-            for (int lane = 0; lane < 64; ++lane) {
-              av[lane] = sW1.rd(mg_p6_a(s, lane & 31, lane >> 5, wave >> 1), 64 * wave + lane);
-              bv[lane] = sT2.rd(mg_p4_b(s, lane & 31, lane >> 5, wave & 1), 64 * wave + lane);
-            }
-            mfma(av, bv, chains[mg_chain(s)]);
-          }
-          chains_fold(acc);
-        store_act(sT1, wave, nullptr);
-        }
+        walk_p6<SumFour>(sT1, sW1, sT2, tnh);
         barrier();
       }
     }
@@ -186,16 +67,16 @@ void Walk::block(int ag, uint64_t blk) {
       for (int wave = 0; wave < kMgWaves; ++wave) {      // P8
         int kt, wt;
         if (!md_p8_tile(t, wave, ncol, kt, wt)) continue;
-        chains_zero();
+        SumFour sum;
         for (int s = 0; s < steps8; ++s) {
           for (int lane = 0; lane < 64; ++lane) {
             const int ia = md_p8_a(s, lane & 31, lane >> 5, kt, col0, ncol, nl);
             av[lane] = ia >= 0 ? Wg[ia] : 0.f;
             bv[lane] = D0.rd(mg_p4_b(s, lane & 31, lane >> 5, wt), 64 * wave + lane);
           }
-          mfma(av, bv, chains[mg_chain(s)]);
+          sum.step(s, av, bv);
         }
-        chains_fold(acc);
+        sum.sum(acc);
         for (int lane = 0; lane < 64; ++lane)
           for (int r = 0; r < 16; ++r) {
             const int o = md_p8_scatter(r, lane & 31, lane >> 5, kt, wt, ncol);

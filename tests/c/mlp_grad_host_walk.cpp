@@ -1,64 +1,22 @@
 // mlp_grad_host_walk.cpp -- every chunk, wave, lane and step of mpe_mlp_grad's two launches on the host: the index functions of
 // csrc/mpe_mlp_grad.h, compiled by the host compiler, address exact-size heap buffers (global memory and the workgroup's LDS arrays
-// alike) under -fsanitize=address,undefined; the MFMA is replaced by its definition (D[row][col] = fma(A[row][1], B[1][col],
-// fma(A[row][0], B[0][col], C[row][col])), operands and results in the lanes mpe_mlp_grad.h states), so what the walk writes is the
+// alike) under -fsanitize=address,undefined; the MFMA is replaced by its definition (mlp_walk.h), so what the walk writes is the
 // gradient itself and the test compares it with the float64 restatement.  Between two barriers a float of LDS may be written by one
 // lane only and read by no other lane than its writer: every phase is checked for that.  Every float of `work` is written once.
+// The staging and P0, P1, P2, P4, P6 are mlp_walk.h's, taken with the forward's chain; P3, P5, P7, the partial, the second launch
+// and every barrier() are here.
 //   mlp_grad_host_walk <in> <out>
 //   in:  int32 A; int64 M; per agent int32 nl, act, width[4], off; int32 n_weights; float weights[]; per agent float in[M * D],
 //        float dout[M * n_out]
 //   out: float grad[n_weights] (behind it nothing); stdout: "<chunks> chunks of <span> groups, <n> floats of workspace"
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "mlp_walk.h"      // CHECK, Lds, Acc, the MFMA, the two sums and the walks of the phases mlp_dinput_host_walk.cpp runs as well
 
-#include "mpe_mlp_grad.h"
-
-using namespace mpe;
-
-#define CHECK(c, ...) do { if (!(c)) { std::fprintf(stderr, __VA_ARGS__); std::fprintf(stderr, "\n"); std::exit(2); } } while (0)
-
-struct Lds {      // one __shared__ array: exact size, and who touched what since the last barrier
-  float *p;
-  int n;
-  std::vector<int> w, r;
-  explicit Lds(int n_) : p(new float[n_]), n(n_), w(n_, -1), r(n_, -1) {}
-  ~Lds() { delete[] p; }
-  float rd(int idx, int tid) {
-    r[idx] = r[idx] == -1 || r[idx] == tid ? tid : -2;
-    return p[idx];
-  }
-  float rd_opt(int idx, int tid) { return idx >= 0 ? rd(idx, tid) : 0.f; }
-  void wr(int idx, int tid, float v) {
-    CHECK(w[idx] == -1, "two writes of LDS float %d between two barriers (lanes %d, %d)", idx, w[idx], tid);
-    w[idx] = tid;
-    p[idx] = v;
-  }
-  void barrier() {
-    for (int k = 0; k < n; ++k) {
-      CHECK(w[k] == -1 || r[k] == -1 || r[k] == w[k], "LDS float %d: written by lane %d and read by another between two barriers", k, w[k]);
-      w[k] = r[k] = -1;
-    }
-  }
-};
-
-typedef float Acc[64][16];
-static void mfma(const float *a, const float *b, Acc acc) {
+// a dW tile's group: the four-chain sum of its 32 steps, added to the chunk's accumulator
+static void add_sum(Acc acc, const SumFour &sum) {
+  Acc t;
+  sum.sum(t);
   for (int lane = 0; lane < 64; ++lane)
-    for (int r = 0; r < 16; ++r) {
-      const int row = mg_trow(r, lane >> 5), col = lane & 31;
-      acc[lane][r] = fmaf(a[row + 32], b[col + 32], fmaf(a[row], b[col], acc[lane][r]));
-    }
-}
-static void zero(Acc a) { std::memset(a, 0, sizeof(Acc)); }
-// one group's steps of a dW tile: chains[mg_chain(t)] took step t; their fold is added to the chunk's accumulator
-static Acc chains[kMgChains];
-static void chains_zero() { for (int q = 0; q < kMgChains; ++q) zero(chains[q]); }
-static void chains_fold(Acc acc) {
-  for (int lane = 0; lane < 64; ++lane)
-    for (int r = 0; r < 16; ++r) acc[lane][r] += mg_fold4(chains[0][lane][r], chains[1][lane][r], chains[2][lane][r], chains[3][lane][r]);
+    for (int r = 0; r < 16; ++r) acc[lane][r] += t[lane][r];
 }
 
 struct Walk {
@@ -76,17 +34,8 @@ void Walk::block(int ag, uint64_t chunk) {
   const bool tnh = a.act[ag] != 0;
   const uint64_t M = a.M;
   const float *Wg = a.w + a.off[ag], *in = a.in[ag], *dout = a.dout[ag];
-  for (int tid = 0; tid < kMgThreads; ++tid) {
-    if (nl >= 2) {
-      for (int idx = tid; idx < kMgHW * kMgLW; idx += kMgThreads) sWL.wr(mg_wl_at(idx), tid, Wg[mg_off_wl(nl, D) + idx]);
-      if (tid < kMgHW) sB0.wr(tid, tid, Wg[mg_off_b0(nl, D) + tid]);
-    }
-    if (nl == 3) {
-      for (int idx = tid; idx < kMgHW * kMgHW; idx += kMgThreads) sW1.wr(mg_w1_at(idx), tid, Wg[mg_off_w1(D) + idx]);
-      if (tid < kMgHW) sB1.wr(tid, tid, Wg[mg_off_b1(D) + tid]);
-    }
-  }
-  static Acc acc0[kMgWaves][kMgTiles0], acc1[kMgWaves], accL[kMgWaves], acc;
+  walk_stage(sWL, sB0, sW1, sB1, Wg, nl, D);
+  static Acc acc0[kMgWaves][kMgTiles0], acc1[kMgWaves], accL[kMgWaves];
   for (int w = 0; w < kMgWaves; ++w) {
     for (int t = 0; t < kMgTiles0; ++t) zero(acc0[w][t]);
     zero(acc1[w]), zero(accL[w]);
@@ -101,106 +50,47 @@ void Walk::block(int ag, uint64_t chunk) {
     if (mg_bias_entry(tid, nl, D) < 0) return;
     for (int r = 0; r < kMgRows; ++r) db[tid] += (double)T.rd(mg_tile_at(tid & 63, r), tid);
   };
-  // a forward layer's / a delta step's results of one wave
-  auto store_act = [&](Lds &T, int wave, bool from_bias_act) {
-    for (int lane = 0; lane < 64; ++lane)
-      for (int r = 0; r < 16; ++r) {
-        const int i = lane & 31, h = lane >> 5, o = mg_fwd_out(r, i, h, wave & 1, wave >> 1), tid = 64 * wave + lane;
-        if (from_bias_act) T.wr(o, tid, mg_act(acc[lane][r], tnh));
-        else T.wr(o, tid, mg_dact(acc[lane][r], T.rd(o, tid), tnh));
-      }
-  };
   for (uint64_t g = g0; g < g1; ++g) {
     const uint64_t row0 = g * kMgRows;
     barrier();
-    for (int tid = 0; tid < kMgThreads; ++tid)      // P0
-      for (int idx = tid; idx < kMgLW * kMgRows; idx += kMgThreads) {
-        const int64_t src = mg_p0_src(idx, row0, M, n);
-        sDL.wr(mg_p0_dst(idx), tid, src >= 0 ? dout[src] : 0.f);
-      }
-    if (nl >= 2)      // P1
-      for (int wave = 0; wave < kMgWaves; ++wave) {
-        const int wt = wave & 1, m = wave >> 1;
-        for (int lane = 0; lane < 64; ++lane)
-          for (int r = 0; r < 16; ++r) acc[lane][r] = sB0.rd(mg_fwd_unit(r, lane >> 5, m), 64 * wave + lane);
-        for (int s = 0; s < mg_p1_steps(D); ++s) {
-          for (int lane = 0; lane < 64; ++lane) {
-            const int ia = mg_p1_a(s, lane & 31, lane >> 5, m, D);
-            const int64_t ib = mg_p1_b(s, lane & 31, lane >> 5, wt, D, row0, M);
-            av[lane] = ia >= 0 ? Wg[ia] : 0.f, bv[lane] = ib >= 0 ? in[ib] : 0.f;
-          }
-          mfma(av, bv, acc);
-        }
-        store_act(sT1, wave, true);
-      }
+    walk_p0(sDL, dout, row0, M, n);
+    if (nl >= 2) walk_p1<SumForward>(sT1, sB0, Wg, in, D, row0, M, tnh);
     barrier();
-    if (nl == 3) {      // P2
-      for (int wave = 0; wave < kMgWaves; ++wave) {
-        const int wt = wave & 1, m = wave >> 1;
-        for (int lane = 0; lane < 64; ++lane)
-          for (int r = 0; r < 16; ++r) acc[lane][r] = sB1.rd(mg_fwd_unit(r, lane >> 5, m), 64 * wave + lane);
-        for (int s = 0; s < mg_p2_steps(w1); ++s) {
-          for (int lane = 0; lane < 64; ++lane) {
-            av[lane] = sW1.rd(mg_p2_a(s, lane & 31, lane >> 5, m), 64 * wave + lane);
-            bv[lane] = sT1.rd(mg_p2_b(s, lane & 31, lane >> 5, wt), 64 * wave + lane);
-          }
-          mfma(av, bv, acc);
-        }
-        store_act(sT2, wave, true);
-      }
+    if (nl == 3) {
+      walk_p2<SumForward>(sT2, sW1, sB1, sT1, w1, tnh);
       barrier();
     }
     if (nl >= 2) {
       for (int wave = 0; wave < 2; ++wave) {      // P3
-        chains_zero();
+        SumFour sum;
         for (int t = 0; t < 32; ++t) {
           for (int lane = 0; lane < 64; ++lane) {
             av[lane] = TH.rd(mg_dw_a_tile(t, lane & 31, lane >> 5, wave), 64 * wave + lane);
             bv[lane] = sDL.rd_opt(mg_dw_b_last(t, lane & 31, lane >> 5), 64 * wave + lane);
           }
-          mfma(av, bv, chains[mg_chain(t)]);
+          sum.step(t, av, bv);
         }
-        chains_fold(accL[wave]);
+        add_sum(accL[wave], sum);
       }
       for (int lane = 0; lane < 64; ++lane) row_sum(sDL, 128 + lane);
       barrier();
-      for (int wave = 0; wave < kMgWaves; ++wave) {      // P4
-        zero(acc);
-        for (int s = 0; s < kMgLW / 2; ++s) {
-          for (int lane = 0; lane < 64; ++lane) {
-            av[lane] = sWL.rd(mg_p4_a(s, lane & 31, lane >> 5, wave >> 1), 64 * wave + lane);
-            bv[lane] = sDL.rd(mg_p4_b(s, lane & 31, lane >> 5, wave & 1), 64 * wave + lane);
-          }
-          mfma(av, bv, acc);
-        }
-        store_act(TH, wave, false);
-      }
+      walk_p4<SumForward>(TH, sWL, sDL, tnh);
       barrier();
       if (nl == 3) {
         for (int wave = 0; wave < kMgWaves; ++wave) {      // P5
-          chains_zero();
+          SumFour sum;
           for (int t = 0; t < 32; ++t) {
             for (int lane = 0; lane < 64; ++lane) {
               av[lane] = sT1.rd(mg_dw_a_tile(t, lane & 31, lane >> 5, wave >> 1), 64 * wave + lane);
               bv[lane] = sT2.rd(mg_dw_b_tile(t, lane & 31, lane >> 5, wave & 1), 64 * wave + lane);
             }
-            mfma(av, bv, chains[mg_chain(t)]);
+            sum.step(t, av, bv);
           }
-          chains_fold(acc1[wave]);
+          add_sum(acc1[wave], sum);
         }
         for (int lane = 0; lane < 64; ++lane) row_sum(sT2, 64 + lane);
         barrier();
-        for (int wave = 0; wave < kMgWaves; ++wave) {      // P6
-          zero(acc);
-          for (int s = 0; s < 32; ++s) {
-            for (int lane = 0; lane < 64; ++lane) {
-              av[lane] = sW1.rd(mg_p6_a(s, lane & 31, lane >> 5, wave >> 1), 64 * wave + lane);
-              bv[lane] = sT2.rd(mg_p4_b(s, lane & 31, lane >> 5, wave & 1), 64 * wave + lane);
-            }
-            mfma(av, bv, acc);
-          }
-          store_act(sT1, wave, false);
-        }
+        walk_p6<SumForward>(sT1, sW1, sT2, tnh);
         barrier();
       }
     }
@@ -208,7 +98,7 @@ void Walk::block(int ag, uint64_t chunk) {
       for (int t = 0; t < kMgTiles0; ++t) {
         int kt, jm;
         if (!mg_p7_tile(t, wave, nl, D, kt, jm)) continue;
-        chains_zero();
+        SumFour sum;
         for (int u = 0; u < 32; ++u) {
           for (int lane = 0; lane < 64; ++lane) {
             const int64_t ia = mg_dw_a_in(u, lane & 31, lane >> 5, kt, D, row0, M);
@@ -216,9 +106,9 @@ void Walk::block(int ag, uint64_t chunk) {
             bv[lane] = nl == 1 ? sDL.rd_opt(mg_dw_b_last(u, lane & 31, lane >> 5), 64 * wave + lane)
                                : sT1.rd(mg_dw_b_tile(u, lane & 31, lane >> 5, jm), 64 * wave + lane);
           }
-          mfma(av, bv, chains[mg_chain(u)]);
+          sum.step(u, av, bv);
         }
-        chains_fold(acc0[wave][t]);
+        add_sum(acc0[wave][t], sum);
       }
     for (int lane = 0; lane < 64; ++lane) row_sum(nl == 1 ? sDL : sT1, lane);
   }
