@@ -262,33 +262,7 @@ int mpe_fill_obs_layout(MpeScenarioDesc *d) {
   if (int rc = check_desc(d, "mpe_fill_obs_layout")) return rc;
   const int A = d->n_agents, L = d->n_landmarks;
   d->obs_off[0] = 0;
-  for (int i = 0; i < A; ++i) {
-    int D = 0;
-    switch (d->kind) {
-      case MPE_SCN_SIMPLE: D = 2 + 2 * L; break;                                   // simple.py:45-50
-      case MPE_SCN_SPREAD: D = 4 + 2 * L + 2 * (A - 1) + d->dim_c * (A - 1); break;  // simple_spread.py:84-100
-      case MPE_SCN_TAG: {                                                          // simple_tag.py:131-147
-        const int good_others = (A - d->n_adversaries) - (i >= d->n_adversaries ? 1 : 0);
-        D = 4 + 2 * L + 2 * (A - 1) + 2 * good_others;
-        break;
-      }
-      case MPE_SCN_ADVERSARY:                                                      // simple_adversary.py:121-139
-        D = (i < d->n_adversaries ? 0 : 2) + 2 * L + 2 * (A - 1);
-        break;
-      case MPE_SCN_PUSH:                                                           // simple_push.py:78-96
-        D = i < d->n_adversaries ? 2 + 2 * L + 2 * (A - 1) : 2 + 2 + 3 + 2 * L + 3 * L + 2 * (A - 1);
-        break;
-      case MPE_SCN_SPEAKER_LISTENER: D = i == 0 ? 3 : 2 + 2 * L + d->dim_c; break;  // simple_speaker_listener.py:69-92
-      case MPE_SCN_REFERENCE: D = 2 + 2 * L + 3 + d->dim_c; break;                  // simple_reference.py:63-83
-      case MPE_SCN_CRYPTO: D = i == 0 ? d->dim_c : 2 * d->dim_c; break;             // simple_crypto.py:127-169
-      case MPE_SCN_WORLD_COMM:                                                      // simple_world_comm.py:231-289
-        D = i < d->n_adversaries ? 4 + 2 * L + 2 * (A - 1) + 2 * (A - d->n_adversaries) + 2 + d->dim_c
-                                 : 4 + 2 * L + 2 * (A - 1) + 2 + 2 * (A - d->n_adversaries - 1);
-        break;
-      default: D = 0;
-    }
-    d->obs_off[i + 1] = d->obs_off[i] + D;
-  }
+  for (int i = 0; i < A; ++i) d->obs_off[i + 1] = d->obs_off[i] + mpe::obs_width(d->kind, i, A, L, d->n_adversaries, d->dim_c);
   return d->obs_off[A];
 }
 

@@ -12,6 +12,32 @@
 
 namespace mpe {
 
+// The width of agent i's observation row in the built-in scenarios (0: a kind without rows): mpe_fill_obs_layout's rule, and
+// what the kernels' row assembly is held to at compile time (ObsTile in mpe_narrow.hip, scn_widths_agree in mpe_split_scn.h).
+__host__ __device__ constexpr int obs_width(int kind, int i, int A, int L, int nadv, int dim_c) {
+  switch (kind) {
+    case MPE_SCN_SIMPLE: return 2 + 2 * L;                                        // simple.py:45-50
+    case MPE_SCN_SPREAD: return 4 + 2 * L + 2 * (A - 1) + dim_c * (A - 1);        // simple_spread.py:84-100
+    case MPE_SCN_TAG:                                                             // simple_tag.py:131-147
+      return 4 + 2 * L + 2 * (A - 1) + 2 * ((A - nadv) - (i >= nadv ? 1 : 0));    // (the last term: the OTHER good agents)
+    case MPE_SCN_ADVERSARY:                                                       // simple_adversary.py:121-139
+      return (i < nadv ? 0 : 2) + 2 * L + 2 * (A - 1);
+    case MPE_SCN_PUSH:                                                            // simple_push.py:78-96
+      return i < nadv ? 2 + 2 * L + 2 * (A - 1) : 2 + 2 + 3 + 2 * L + 3 * L + 2 * (A - 1);
+    case MPE_SCN_SPEAKER_LISTENER: return i == 0 ? 3 : 2 + 2 * L + dim_c;         // simple_speaker_listener.py:69-92
+    case MPE_SCN_REFERENCE: return 2 + 2 * L + 3 + dim_c;                         // simple_reference.py:63-83
+    case MPE_SCN_CRYPTO: return i == 0 ? dim_c : 2 * dim_c;                       // simple_crypto.py:127-169
+    case MPE_SCN_WORLD_COMM:                                                      // simple_world_comm.py:231-289
+      return i < nadv ? 4 + 2 * L + 2 * (A - 1) + 2 * (A - nadv) + 2 + dim_c : 4 + 2 * L + 2 * (A - 1) + 2 + 2 * (A - nadv - 1);
+    default: return 0;
+  }
+}
+__host__ __device__ constexpr int obs_width_max(int kind, int A, int L, int nadv, int dim_c) {   // the widest agent's
+  int m = 0;
+  for (int i = 0; i < A; ++i) m = obs_width(kind, i, A, L, nadv, dim_c) > m ? obs_width(kind, i, A, L, nadv, dim_c) : m;
+  return m;
+}
+
 enum class NarrowOp { Step, Observe };
 
 // thread-per-world family (mpe_narrow.hip)

@@ -14,14 +14,10 @@ constexpr int kBlock = 256;
 
 template <int KIND, int A, int L, int NADV>
 struct ObsTile {  // LDS floats one wave needs for its widest observation row
+  // (this family has kernels for MPE_SCN_GENERIC, which has no rows, and for simple .. simple_push, whose World.dim_c is 2)
+  static_assert(KIND >= MPE_SCN_GENERIC && KIND <= MPE_SCN_PUSH, "ObsTile: the communication scenarios have another dim_c");
   static constexpr int DC = 2;  // World.dim_c of simple_spread / simple_tag
-  static constexpr int D =
-      KIND == MPE_SCN_SIMPLE   ? 2 + 2 * L
-      : KIND == MPE_SCN_SPREAD ? 4 + 2 * L + 2 * (A - 1) + DC * (A - 1)
-      : KIND == MPE_SCN_TAG    ? 4 + 2 * L + 2 * (A - 1) + 2 * (A - NADV)
-      : KIND == MPE_SCN_ADVERSARY ? 2 + 2 * L + 2 * (A - 1)
-      : KIND == MPE_SCN_PUSH   ? 7 + 5 * L + 2 * (A - 1)
-                               : 1;
+  static constexpr int D = obs_width_max(KIND, A, L, NADV, DC);   // (MPE_SCN_GENERIC has no rows: 0)
   static constexpr int floats = kWave * (D | 1);  // >= kWave * tile_stride<D>()
 };
 

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "mpe_internal.h"
+#include "mpe_split_scn.h"
 
 // ablation builds (tools/ab_build.sh): bit 0 skip the contact loop, bit 1 skip the reward stage, bit 2 skip the
 // observation rows, bit 3 skip the state stores -- what each stage of the step costs
@@ -101,372 +102,40 @@ namespace mpe {
 //   simple_spread N=3  4096 worlds 1.08 | 1.09 | 0.99      16 384 worlds 1.13 | 1.14 | 1.06      N=4, 16 384: 1.83 | 1.83 | 1.69
 //   simple_adversary  16 384 worlds 0.79 | 0.58 | 0.64     simple_push 16 384: 0.93 | 0.65 | 0.76     simple 16 384: 0.43 | 0.37 | 0.46
 //   simple_tag        16 384 worlds 1.31 | 1.01-1.15 | 1.09-1.10 (by box)
-#ifndef MPE_SPLIT_DUAL_OWN_DRAW
-#define MPE_SPLIT_DUAL_OWN_DRAW (1 << MPE_SCN_SPREAD)
+// The product's choice is each scenario's Scn::own_draw (mpe_split_scn.h: simple_spread alone); an A/B build's
+// -DMPE_SPLIT_DUAL_OWN_DRAW=<mask> overrides it for every kind.
+template <class SCN>
+constexpr bool dual_own_draw() {
+#ifdef MPE_SPLIT_DUAL_OWN_DRAW
+  return ((MPE_SPLIT_DUAL_OWN_DRAW) >> SCN::kind) & 1;
+#else
+  return SCN::own_draw;
 #endif
-template <int KIND>
-constexpr bool dual_own_draw() { return ((MPE_SPLIT_DUAL_OWN_DRAW) >> KIND) & 1; }
-
-template <int KIND>
-constexpr bool dual_kind() {   // the kinds that have a dual-role rollout kernel
-  return (MPE_SPLIT_DUAL) &&
-         (KIND == MPE_SCN_SIMPLE || KIND == MPE_SCN_SPREAD || KIND == MPE_SCN_TAG || KIND == MPE_SCN_ADVERSARY || KIND == MPE_SCN_PUSH);
 }
 
+template <class SCN>
+constexpr bool dual_kind() { return (MPE_SPLIT_DUAL) && SCN::dual; }   // the kinds that have a dual-role rollout kernel
+
+// The geometry of a workgroup, from what the scenario says of itself (mpe_split_scn.h)
 template <int KIND, int A, int L, int NADV>
 struct SplitShape {
+  using S = Scn<KIND, A, L, NADV>;
+  static_assert(scn_widths_agree<S, A, L, NADV>(), "the scenario's row widths: obs_width (mpe_internal.h) for every agent, DMAX their maximum");
   static constexpr int E = A + L;
-  // floats an agent publishes per world: pos, vel, then squared distances to the landmarks the reward needs
-  static constexpr int XW = KIND == MPE_SCN_SPREAD ? 4 + L
-                            : (KIND == MPE_SCN_SIMPLE || KIND == MPE_SCN_ADVERSARY || KIND == MPE_SCN_PUSH ||
-                               KIND == MPE_SCN_SPEAKER_LISTENER || KIND == MPE_SCN_REFERENCE) ? 5
-                            : KIND == MPE_SCN_WORLD_COMM ? 6 : 4;
-  // World.dim_c of the communication scenarios (make_world of each)
-  static constexpr int DC = KIND == MPE_SCN_SPEAKER_LISTENER ? 3 : KIND == MPE_SCN_REFERENCE ? 10
-                            : (KIND == MPE_SCN_CRYPTO || KIND == MPE_SCN_WORLD_COMM) ? 4 : 2;
-  // per-world picks this kernel reads (MpeBuffers.choice rows)
-  static constexpr int NCH = (KIND == MPE_SCN_ADVERSARY || KIND == MPE_SCN_PUSH || KIND == MPE_SCN_SPEAKER_LISTENER) ? 1
-                             : (KIND == MPE_SCN_REFERENCE || KIND == MPE_SCN_CRYPTO) ? 2 : 0;
-  static constexpr int DMAX = KIND == MPE_SCN_SIMPLE   ? 2 + 2 * L
-                              : KIND == MPE_SCN_SPREAD ? 4 + 2 * L + 4 * (A - 1)
-                              : KIND == MPE_SCN_TAG    ? 4 + 2 * L + 2 * (A - 1) + 2 * (A - NADV)
-                              : KIND == MPE_SCN_ADVERSARY ? 2 + 2 * L + 2 * (A - 1)
-                              : KIND == MPE_SCN_PUSH   ? 7 + 5 * L + 2 * (A - 1)
-                              : KIND == MPE_SCN_SPEAKER_LISTENER ? 2 + 2 * L + 3
-                              : KIND == MPE_SCN_REFERENCE ? 2 + 2 * L + 3 + 10
-                              : KIND == MPE_SCN_CRYPTO ? 8
-                              : KIND == MPE_SCN_WORLD_COMM ? 4 + 2 * L + 2 * (A - 1) + 2 * (A - NADV) + 2 + 4
-                                                       : 1;
-  // rows a wave's LDS tile holds: 64, except in simple_world_comm's ROLLOUT (six agent waves, 34-float rows, two exchange
-  // blocks: 72 KB per workgroup with 64-row tiles = two workgroups per CU).  With 32-row tiles (the wave's rows leave in
-  // two halves) it is 45 KB: three per CU -- measured 10.8 vs 13.4 us per step; the single step is NOT faster that way
-  // (19.4-19.7 vs 18.3-18.8 us) and keeps 64 rows.
-  static constexpr int trows(bool roll) { return (KIND == MPE_SCN_WORLD_COMM && roll) ? 32 : kWave; }
-  static constexpr int tile_floats(bool roll) { return trows(roll) * (DMAX | 1); }  // >= trows * tile_stride<D>() of every row width
+  static constexpr int trows(bool roll) { return S::trows(roll); }   // rows a wave's LDS tile holds
+  static constexpr int tile_floats(bool roll) { return trows(roll) * (S::DMAX | 1); }  // >= trows * tile_stride<D>() of every row width
   // A agent waves (+ A rows waves in the dual-role rollout) + the reward wave
   static constexpr int waves(bool dual) { return (dual ? 2 * A : A) + 1; }
   // rollout: + the moves of the next step, drawn by the reward wave for all agents (two buffers by step parity)
   static constexpr size_t lds_bytes(bool roll) {
-    return sizeof(float) * ((roll ? 2 : 1) * A * XW * kWave + A * tile_floats(roll) + (roll ? 2 * A * kWave : 0));
+    return sizeof(float) * ((roll ? 2 : 1) * A * S::XW * kWave + A * tile_floats(roll) + (roll ? 2 * A * kWave : 0));
   }
 };
 
-// Which agents speak in the communication scenarios (their make_world: `agent.silent = False`), bit a = agent a.
-template <int KIND>
-constexpr unsigned speakers_of() {
-  return KIND == MPE_SCN_SPEAKER_LISTENER ? 0x1u : KIND == MPE_SCN_REFERENCE ? 0x3u : KIND == MPE_SCN_CRYPTO ? 0x7u
-         : KIND == MPE_SCN_WORLD_COMM ? 0x1u : 0u;
-}
-// The utterance of one agent in one world at this step: a row of MpeBuffers.comm (what the caller passed), or -- in
-// the fused rollout -- the one-hot of the word mpe_random_comm draws for (world, step, agent), recomputed where used.
-// WM (word mode): 0 = the caller's row, 1 = drawn in the kernel (the rollout), 2 = the caller's row read at SYSTEM scope (the step
-// server: another kernel wrote the utterance ring while this one runs -- no cache of ours may serve it)
-constexpr int kWordRow = 0, kWordDrawn = 1, kWordRowSys = 2;
-template <int WM>
-struct Word {
-  const float *row;
-  int id;
-  __device__ __forceinline__ float operator[](int c) const {
-    if constexpr (WM == kWordDrawn) return c == id ? 1.f : 0.f;
-    else if constexpr (WM == kWordRowSys)
-      return __builtin_bit_cast(float, __hip_atomic_load(reinterpret_cast<const int *>(row) + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-    else return row[c];
-  }
-};
-template <int DC, int WM>
-__device__ __forceinline__ Word<WM> word_of(const MpeBuffers &b, size_t B, size_t w0, unsigned ln, int j, uint64_t seed,
-                                            uint64_t gw, uint64_t gt) {
-  Word<WM> wd;
-  wd.row = WM == kWordDrawn ? nullptr : b.comm + wave_off(((size_t)j * B + w0) * DC) + ln * DC;
-  wd.id = WM == kWordDrawn ? comm_draw(seed, gw, gt, j, DC) : 0;
-  return wd;
-}
-
-// ---- the reward wave: Scenario.reward / benchmark_data / done for all A agents of 64 worlds --------
-// X is the exchange block the agent waves filled: X[(a * XW + c) * 64 + lane], c = 0,1 pos, 2,3 vel, 4.. d2.
-// Cache policy of the 4- / 1-byte outputs (state, rewards, dones, counts): agent scope for simple_tag's SMALL launches (the
-// kernels built with agent-scope rows), ordinary stores everywhere else.  Measured (profiles/r2_ab_logs.txt session 40): tag at
-// 16 384 worlds 3.78 -> 3.47 us per step, 1.29 -> 1.25 per rollout step, at 4096 worlds 3.24 -> 3.18 -- but at 65 536 worlds
-// 6.52 -> 6.95, and simple_spread loses at both 4096 (2.98 -> 3.11) and 65 536 worlds (5.55 -> 5.94).
-template <int KIND, int RP>
-constexpr int aux_policy() { return (KIND == MPE_SCN_TAG && RP == kRowsSc1) ? kRowsSc1 : kRowsPlain; }
-
-template <int KIND, int A, int L, int NADV, bool ROLL, int AUX, int WM = (ROLL ? kWordDrawn : kWordRow)>
-__device__ __forceinline__ void reward_wave(const NarrowDesc &d, const float *const sz /* pinned sz[] */, const MpeBuffers &b, const float *X, int lane,
-                                            bool live, unsigned ln, size_t B, size_t w0 /* first world of the wave */,
-                                            size_t ro /* uniform: row 0 of this step + w0 */, uint64_t seed, uint64_t gw,
-                                            uint64_t gt, int goal_roll /* rollout: this world's pick 0 */,
-                                            const float (&food_roll)[4] /* rollout, world_comm: food x0 y0 x1 y1 */) {
-  constexpr int XW = SplitShape<KIND, A, L, NADV>::XW;
-  if (KIND == MPE_SCN_SIMPLE) {  // simple.py:41-43: -|pos - landmark 0|^2
-    if (live) {
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        if (b.rew) store_aux<AUX>(b.rew + wave_off(ro + (size_t)a * B) + ln, -X[(a * XW + 4) * kWave + lane]);
-        if (b.done) store_aux<AUX>(b.done + wave_off(ro + (size_t)a * B) + ln, 0);
-      }
-    }
-  }
-  if (KIND == MPE_SCN_SPREAD) {  // simple_spread.py:72-82, :47-63
-    if (b.rew || b.info_rew) {
-      float px[A], py[A];
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        px[a] = X[(a * XW + 0) * kWave + lane];
-        py[a] = X[(a * XW + 1) * kWave + lane];
-      }
-      // landmark term from the published SQUARED agent-landmark distances: min first, then one square
-      // root (monotone); contact counts from the new positions
-      float lm_term = 0.f, md = 0.f;
-      int occupied = 0;
-#pragma unroll
-      for (int l = 0; l < L; ++l) {
-        float m2 = X[(0 * XW + 4 + l) * kWave + lane];
-#pragma unroll
-        for (int a = 1; a < A; ++a) m2 = fminf(m2, X[(a * XW + 4 + l) * kWave + lane]);
-        const float m = fast_sqrt(m2);
-        lm_term = lm_term - m;
-        md = md + m;
-        if (b.info_rew) occupied += sqrt_lt(m2, 0.1f) ? 1 : 0;  // benchmark_data only (uniform); the integer output takes the exact test
-      }
-      int cnt[A];
-#pragma unroll
-      for (int a = 0; a < A; ++a) cnt[a] = (sz[a] + sz[a] > 0.f) ? 1 : 0;  // the agent against itself (Q1): 0 < 2r
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-#pragma unroll
-        for (int c = a + 1; c < A; ++c) {
-          const bool hit = sqrt_lt(sq2d(px[a] - px[c], py[a] - py[c]), sz[a] + sz[c]);
-          cnt[a] += hit ? 1 : 0;
-          cnt[c] += hit ? 1 : 0;
-        }
-      }
-      float r[A];
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        const int c = ((d.collide >> a) & 1u) ? cnt[a] : 0;
-        cnt[a] = c;
-        float ra_ = lm_term;
-#pragma unroll
-        for (int s = 0; s < A; ++s) ra_ = ra_ - (c > s ? 1.f : 0.f);  // rew -= 1 per contact, in sequence
-        r[a] = ra_;
-      }
-      // environment.py:100-102: reward = np.sum(reward_n) = r0 + (((0 + r1) + r2) + ...) for n < 9
-      float rest = 0.f;
-#pragma unroll
-      for (int a = 1; a < A; ++a) rest += r[a];
-      const float total = A > 1 ? r[0] + rest : r[0];
-      if (live) {
-#pragma unroll
-        for (int a = 0; a < A; ++a) {
-          const size_t o = ro + (size_t)a * B;
-          if (b.rew) store_aux<AUX>(b.rew + wave_off(o) + ln, d.collaborative ? total : r[a]);
-          if (b.info_rew) {
-            store_aux<AUX>(b.info_rew + wave_off(o) + ln, r[a]);
-            store_aux<AUX>(b.info_collisions + wave_off(o) + ln, cnt[a]);
-            store_aux<AUX>(b.info_min_dists + wave_off(o) + ln, md);
-            store_aux<AUX>(b.info_occupied + wave_off(o) + ln, occupied);
-          }
-        }
-      }
-    }
-    if (b.done && live) {
-#pragma unroll
-      for (int a = 0; a < A; ++a) store_aux<AUX>(b.done + wave_off(ro + (size_t)a * B) + ln, 0);
-    }
-  }
-  if (KIND == MPE_SCN_TAG) {  // simple_tag.py:84-129, :57-66
-    constexpr int NG = A - NADV;
-    if (b.rew || b.info_collisions) {
-      float px[A], py[A];
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        px[a] = X[(a * XW + 0) * kWave + lane];
-        py[a] = X[(a * XW + 1) * kWave + lane];
-      }
-      bool hit[NG][NADV];
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int v = 0; v < NADV; ++v)
-          hit[g][v] = sqrt_lt(sq2d(px[NADV + g] - px[v], py[NADV + g] - py[v]), sz[NADV + g] + sz[v]);
-      float adv_rew = 0.f;  // adversary_reward :115-129 -- same value for every adversary
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int v = 0; v < NADV; ++v) adv_rew += hit[g][v] ? 10.f : 0.f;
-      if (live) {
-#pragma unroll
-        for (int a = 0; a < A; ++a) {
-          float r;
-          int c = 0;
-          if (a < NADV) {
-            r = ((d.collide >> a) & 1u) ? adv_rew : 0.f;
-#pragma unroll
-            for (int g = 0; g < NG; ++g) c += hit[g][a < NADV ? a : 0] ? 1 : 0;
-          } else {  // agent_reward :89-113
-            r = 0.f;
-            if ((d.collide >> a) & 1u) {
-#pragma unroll
-              for (int v = 0; v < NADV; ++v) r -= hit[a >= NADV ? a - NADV : 0][v] ? 10.f : 0.f;
-            }
-            r -= tag_bound(fabsf(px[a]));
-            r -= tag_bound(fabsf(py[a]));
-          }
-          const size_t o = ro + (size_t)a * B;
-          if (b.rew) store_aux<AUX>(b.rew + wave_off(o) + ln, r);
-          if (b.info_collisions) store_aux<AUX>(b.info_collisions + wave_off(o) + ln, c);  // benchmark_data :57-66
-        }
-      }
-    }
-    if (b.done && live) {
-#pragma unroll
-      for (int a = 0; a < A; ++a) store_aux<AUX>(b.done + wave_off(ro + (size_t)a * B) + ln, 0);
-    }
-  }
-  if (KIND == MPE_SCN_ADVERSARY || KIND == MPE_SCN_PUSH) {
-    // each agent published the SQUARED distance to this world's goal landmark (column 4)
-    if (live) {
-      float d2g[A];
-#pragma unroll
-      for (int a = 0; a < A; ++a) d2g[a] = X[(a * XW + 4) * kWave + lane];
-      float m2 = d2g[NADV];   // the good agent nearest to the goal
-#pragma unroll
-      for (int a = NADV + 1; a < A; ++a) m2 = fminf(m2, d2g[a]);
-      float adv_sum = 0.f;    // simple_adversary.py:88: sum over adversaries of their distance to the goal
-#pragma unroll
-      for (int a = 0; a < NADV; ++a) adv_sum = adv_sum + fast_sqrt(d2g[a]);
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        float r;
-        if (KIND == MPE_SCN_ADVERSARY) r = a < NADV ? -d2g[a] : -fast_sqrt(m2) + adv_sum;            // :113 / :100-107
-        else                           r = a < NADV ? fast_sqrt(m2) - fast_sqrt(d2g[a]) : -fast_sqrt(d2g[a]);  // simple_push.py:68-76 / :64-66
-        const size_t o = ro + (size_t)a * B;
-        if (b.rew) store_aux<AUX>(b.rew + wave_off(o) + ln, r);
-        if (b.done) store_aux<AUX>(b.done + wave_off(o) + ln, 0);
-      }
-    }
-  }
-  if constexpr (KIND == MPE_SCN_SPEAKER_LISTENER) {  // simple_speaker_listener.py:63-67: -|listener - goal landmark|^2 for both
-    if (live) {
-      const float r = -X[(1 * XW + 4) * kWave + lane];
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        const size_t o = ro + (size_t)a * B;
-        if (b.rew) store_aux<AUX>(b.rew + wave_off(o) + ln, d.collaborative ? r + r : r);
-        if (b.done) store_aux<AUX>(b.done + wave_off(o) + ln, 0);
-      }
-    }
-  }
-  if constexpr (KIND == MPE_SCN_REFERENCE) {  // simple_reference.py:57-61: agent i wants the OTHER agent at i's goal landmark
-    if (live) {
-      const float r0 = -X[(1 * XW + 4) * kWave + lane];   // |pos_1 - landmark goal_0|^2, published by agent 1
-      const float r1 = -X[(0 * XW + 4) * kWave + lane];
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        const size_t o = ro + (size_t)a * B;
-        if (b.rew) store_aux<AUX>(b.rew + wave_off(o) + ln, d.collaborative ? r0 + r1 : (a == 0 ? r0 : r1));
-        if (b.done) store_aux<AUX>(b.done + wave_off(o) + ln, 0);
-      }
-    }
-  }
-  if constexpr (KIND == MPE_SCN_CRYPTO) {  // simple_crypto.py:97-124: squared error of what Bob / Eve say against the goal one-hot
-    constexpr int DC = SplitShape<KIND, A, L, NADV>::DC;
-    if (live) {
-      const int g = ROLL ? goal_roll : (b.choice + wave_off(w0))[ln];
-      float err[2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {   // a = 0: Eve (adversary), a = 1: Bob (good listener)
-        const Word<WM> c = word_of<DC, WM>(b, B, w0, ln, a, seed, gw, gt);
-        float e = 0.f;
-        bool silent = true;
-#pragma unroll
-        for (int k = 0; k < DC; ++k) {
-          const float v = c[k], dv = v - (k == g ? 1.f : 0.f);
-          silent = silent && (v == 0.f);
-          e = e + dv * dv;
-        }
-        err[a] = silent ? 0.f : e;   // `continue` on an all-zero utterance (:107, :112, :122)
-      }
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        const float r = a == 0 ? 0.f - err[0] : (0.f + err[0]) + (0.f - err[1]);
-        const size_t o = ro + (size_t)a * B;
-        if (b.rew) store_aux<AUX>(b.rew + wave_off(o) + ln, r);
-        if (b.done) store_aux<AUX>(b.done + wave_off(o) + ln, 0);
-      }
-    }
-  }
-  if constexpr (KIND == MPE_SCN_WORLD_COMM) {  // simple_world_comm.py:143-203
-    constexpr int NG = A - NADV;
-    float px[A], py[A];
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-      px[a] = X[(a * XW + 0) * kWave + lane];
-      py[a] = X[(a * XW + 1) * kWave + lane];
-    }
-    bool hit[NG][NADV];
-    float dmin[NADV];   // adversary v: distance to the nearest good agent
-#pragma unroll
-    for (int v = 0; v < NADV; ++v) dmin[v] = INFINITY;
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-      for (int v = 0; v < NADV; ++v) {
-        const float d2 = sq2d(px[NADV + g] - px[v], py[NADV + g] - py[v]);
-        hit[g][v] = sqrt_lt(d2, sz[NADV + g] + sz[v]);
-        dmin[v] = fminf(dmin[v], d2);
-      }
-    // food = landmarks 1, 2 (world.landmarks = [obstacle] + food + forests)
-    float fx[2], fy[2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {   // (the rollout's in-kernel resets move the landmarks: HBM holds them only at the end)
-      fx[f] = ROLL ? food_roll[2 * f] : (b.pos + wave_off((size_t)(2 * (A + 1 + f)) * B + w0))[ln];
-      fy[f] = ROLL ? food_roll[2 * f + 1] : (b.pos + wave_off((size_t)(2 * (A + 1 + f) + 1) * B + w0))[ln];
-    }
-    if (live) {
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        float r = 0.f;
-        if (a < NADV) {   // adversary_reward :188-203 (shape = True)
-          r = r - 0.1f * fast_sqrt(dmin[a < NADV ? a : 0]);
-          if ((d.collide >> a) & 1u) {
-#pragma unroll
-            for (int g = 0; g < NG; ++g)
-#pragma unroll
-              for (int v = 0; v < NADV; ++v) r = r + (hit[g][v] ? 5.f : 0.f);
-          }
-        } else {          // agent_reward :156-186
-          if ((d.collide >> a) & 1u) {
-#pragma unroll
-            for (int v = 0; v < NADV; ++v) r = r - (hit[a >= NADV ? a - NADV : 0][v] ? 5.f : 0.f);
-          }
-          r = r - 2.f * tag_bound(fabsf(px[a]));
-          r = r - 2.f * tag_bound(fabsf(py[a]));
-          float m2 = INFINITY;
-#pragma unroll
-          for (int f = 0; f < 2; ++f) {
-            const float d2 = sq2d(px[a] - fx[f], py[a] - fy[f]);
-            r = r + (sqrt_lt(d2, sz[a] + sz[A + 1 + f]) ? 2.f : 0.f);
-            m2 = fminf(m2, d2);
-          }
-          r = r + 0.05f * fast_sqrt(m2);
-        }
-        const size_t o = ro + (size_t)a * B;
-        if (b.rew) store_aux<AUX>(b.rew + wave_off(o) + ln, r);
-        if (b.done) store_aux<AUX>(b.done + wave_off(o) + ln, 0);
-        if (b.info_collisions) {   // benchmark_data, simple_world_comm.py:115-124: an adversary's contacts with good agents, 0 for the others
-          int c = 0;
-          if (a < NADV) {
-#pragma unroll
-            for (int g = 0; g < NG; ++g) c += hit[g][a < NADV ? a : 0] ? 1 : 0;
-          }
-          store_aux<AUX>(b.info_collisions + wave_off(o) + ln, c);
-        }
-      }
-    }
-  }
-}
+// Cache policy of the 4- / 1-byte outputs (state, rewards, dones, counts): agent scope for the SMALL launches (the kernels built
+// with agent-scope rows) of the scenarios that measured faster that way (Scn::aux_sc1_small), ordinary stores everywhere else.
+template <class SCN, int RP>
+constexpr int aux_policy() { return (SCN::aux_sc1_small && RP == kRowsSc1) ? kRowsSc1 : kRowsPlain; }
 
 // ---- the policy rollout (POL): agent i's MLP actor on its observation tile, one lane = one world -------------------------
 // The actor's weights are WAVE-UNIFORM (one agent per wave): read through the constant address space they are scalar loads
@@ -619,8 +288,8 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
                                            const PolArgs &pol) {
   static_assert(!SERVE || (ROLL && RP == kRowsSc1), "the step server: a rollout instantiation, write-through stores");
   static_assert(!POL || (ROLL && !SERVE && !DUALP), "the policy rollout: a single-role rollout instantiation");
-  static_assert(!POL || KIND == MPE_SCN_SIMPLE || KIND == MPE_SCN_SPREAD || KIND == MPE_SCN_ADVERSARY || KIND == MPE_SCN_PUSH,
-                "the policy rollout: scenarios whose observation rows read no other agent's velocity");
+  using SC = Scn<KIND, A, L, NADV>;   // what this scenario is (mpe_split_scn.h)
+  static_assert(!POL || SC::policy, "the policy rollout: scenarios whose observation rows read no other agent's velocity");
   // the agents' utterances: the caller's rows (a launched step), drawn in the kernel (the rollout), or the caller's rows of THIS step
   // out of the utterance ring, read at system scope (the step server)
   constexpr int WM = SERVE ? kWordRowSys : (ROLL ? kWordDrawn : kWordRow);
@@ -636,14 +305,14 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
   b.vel = g_vel;
   b.act = g_act;
   b.ids = g_ids;
-  constexpr int E = A + L, XW = S::XW;
-  constexpr int AUX = SERVE ? kRowsSc1 : aux_policy<KIND, RP>();   // (a served step's state / rewards / dones leave write-through)
+  constexpr int E = A + L, XW = SC::XW;
+  constexpr int AUX = SERVE ? kRowsSc1 : aux_policy<SC, RP>();   // (a served step's state / rewards / dones leave write-through)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & (kWave - 1);
   // uniform role of this wave: [0, A) the agent waves (in the dual-role rollout: the PHYSICS waves), then -- dual-role
   // rollout only -- [A, 2A) the ROWS waves, and last the reward wave
   constexpr bool DUAL = DUALP && ROLL;
-  constexpr bool OWN_DRAW = DUAL && dual_own_draw<KIND>();   // the physics waves draw their own moves
+  constexpr bool OWN_DRAW = DUAL && dual_own_draw<SC>();   // the physics waves draw their own moves
   constexpr int NAW = DUAL ? 2 * A : A;   // agent-side waves
   const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const bool is_agent = role < NAW;
@@ -694,7 +363,7 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
   auto with_words = [&](const int t) {      // the buffers with `comm` = the utterances of step t (served: tensor g mod ring)
     MpeBuffers q = b;
     if constexpr (SERVE)
-      q.comm = sv.comm_ring ? sv.comm_ring + (size_t)((mvt0 + t) % sv.ring) * ((size_t)A * B * SplitShape<KIND, A, L, NADV>::DC) : nullptr;
+      q.comm = sv.comm_ring ? sv.comm_ring + (size_t)((mvt0 + t) % sv.ring) * ((size_t)A * B * SC::DC) : nullptr;
     return q;
   };
   // wait_door: until step g = step0 + t is commanded.  -> false: gave up (timeout): the wave leaves the kernel.
@@ -748,17 +417,11 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
     // ---- the reward wave --------------------------------------------------------------------------
     // (what the reward needs besides the agents' published state follows the in-kernel resets of the rollout with the
     //  same countdown the agent waves run: simple_crypto's goal pick, simple_world_comm's food positions)
-    constexpr bool TRACK = ROLL && (KIND == MPE_SCN_CRYPTO || KIND == MPE_SCN_WORLD_COMM);
+    constexpr bool TRACK = ROLL && SC::tracks_resets;
     const uint64_t gw_r = ra.world_offset + w;
-    int goal_r = (ROLL && KIND == MPE_SCN_CRYPTO) ? (b.choice + wave_off(w0))[ln] : 0;
+    int goal_r = 0;
     float food[4] = {0.f, 0.f, 0.f, 0.f};
-    if (ROLL && KIND == MPE_SCN_WORLD_COMM) {
-#pragma unroll
-      for (int f = 0; f < 2; ++f) {
-        food[2 * f] = (b.pos + wave_off((size_t)(2 * (A + 1 + f)) * B + w0))[ln];
-        food[2 * f + 1] = (b.pos + wave_off((size_t)(2 * (A + 1 + f) + 1) * B + w0))[ln];
-      }
-    }
+    if (TRACK) SC::track_load(b, B, w0, ln, goal_r, food);
     float sz[E];   // every entity's size, in SGPRs before the barrier (the reward's strict-< tests sit behind it)
 #pragma unroll
     for (int e = 0; e < E; ++e) sz[e] = d.size[e];
@@ -778,11 +441,7 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
       }
       if (TRACK && cd >= 0) {
         if (cd == 0) {
-          if (KIND == MPE_SCN_CRYPTO) goal_r = choice_draw(ra.seed, gw_r, ep_r, 0, d.choice_pop[0]);
-          if (KIND == MPE_SCN_WORLD_COMM) {
-#pragma unroll
-            for (int f = 0; f < 2; ++f) reset_draw(ra.seed, gw_r, ep_r, A + 1 + f, ra.landmark_range, food[2 * f], food[2 * f + 1]);
-          }
+          SC::track_reset(d, ra, gw_r, ep_r, goal_r, food);
           ++ep_r;
           cd = ra.episode_len - 1;
         } else {
@@ -811,8 +470,8 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
       }
       MPE_STAMP(2);
       if (!(MPE_SPLIT_ABLATE & 2))
-      reward_wave<KIND, A, L, NADV, ROLL, AUX, WM>(d, sz, with_words(t), X, lane, live, ln, B, w0, (size_t)block_of(t) * row_stride + w0,
-                                                   ra.seed, gw_r, ra.step0 + (uint64_t)t, goal_r, food);
+      SC::template reward<ROLL, AUX, WM>(d, sz, with_words(t), X, lane, live, ln, B, w0, (size_t)block_of(t) * row_stride + w0,
+                                         ra.seed, gw_r, ra.step0 + (uint64_t)t, goal_r, food);
       MPE_STAMP(3);
     }
     if (SERVE) {   // the last step: every wave drains, then the workgroup says so
@@ -862,8 +521,8 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
     if (a == i) { mx = px[a]; my = py[a]; }
 
   const uint64_t gw = ra.world_offset + w;  // global world number (RNG streams)
-  constexpr bool HAS_GOAL = KIND == MPE_SCN_ADVERSARY || KIND == MPE_SCN_PUSH;
-  constexpr int NCH = S::NCH, DC = S::DC;
+  constexpr bool HAS_GOAL = SC::has_goal;
+  constexpr int NCH = SC::NCH, DC = SC::DC;
   // this world's picks of reset_world (np.random.choice: goal landmark, key ...)
   int goal = NCH >= 1 ? (b.choice + wave_off(w0))[ln] : 0;
   int pick1 = NCH >= 2 ? (b.choice + wave_off(B + w0))[ln] : 0;
@@ -972,6 +631,20 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
     asm volatile("" ::"v"(mx), "v"(my), "v"(mvx), "v"(mvy));   // World.step has finished here
 #endif
   };
+  // POL: where the decision observation sits in the tile -- row width, row stride and this lane's piece swizzle (flush_rows'
+  // layouts), noted by the view's emit
+  [[maybe_unused]] int pol_D = 0, pol_S = 0, pol_sw = 0;
+  // view: what the scenario's hooks (mpe_split_scn.h) read of this wave at step t
+  // (every member is evaluated at every call, publish's and behind_barrier's included: block_of and with_words -- a copy of
+  //  MpeBuffers and, when served, two 32-bit modulos -- have no side effect, and a hook that does not read obs_t or comm leaves
+  //  them to dead-code elimination after inlining.  A member with a side effect, or a hook that is not inlined, would put that
+  //  work on the step's chain.)
+  auto view = [&](const int t, const bool pre) {
+    return AgentView<A, L, RP, WM, ROLL, POL>{tile, lane, i, nvalid, live, ln, w0, B, obs_off_i, d.vec4, mx, my, mvx, mvy, px, py, gx, gy, goal, pick1,
+                                              size_i, size_e, xch + (ROLL ? (t & 1) * A * XW * kWave : 0),
+                                              b.obs + (size_t)block_of(t) * obs_stride, with_words(t).comm, ra.seed, gw,
+                                              ra.step0 + (uint64_t)t /* global step (the word stream of the rollout) */, pre, pol_D, pol_S, pol_sw};
+  };
   // publish: this agent's new state (and what the reward wave needs of it) into the exchange block of step t's parity
   auto publish = [&](const int t) {
     float *const X = xch + (ROLL ? (t & 1) * A * XW * kWave : 0);
@@ -979,25 +652,15 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
     X[(i * XW + 1) * kWave + lane] = my;
     X[(i * XW + 2) * kWave + lane] = mvx;
     X[(i * XW + 3) * kWave + lane] = mvy;
-    if (KIND == MPE_SCN_SPREAD) {
+    // (simple_spread's columns stay written out here in the POLICY kernels: through Scn::publish_extra -- the same stores, the same
+    //  dynamic instruction counts, only another block order and schedule around the actor -- the policy rollout of N = 3 at 65 536
+    //  worlds measured 404-411 vs 364-369 us per step, same box, three runs each; with this body in place 364.  The waves' wait
+    //  cycles carry the whole difference (SQ_WAIT_ANY +27 %); why they grow is not known.  Every other kernel takes the hook.)
+    if constexpr (POL && SC::kind == MPE_SCN_SPREAD) {
 #pragma unroll
       for (int l = 0; l < L; ++l) X[(i * XW + 4 + l) * kWave + lane] = sq2d(mx - px[A + l], my - py[A + l]);
-    }
-    if (KIND == MPE_SCN_SIMPLE) X[(i * XW + 4) * kWave + lane] = sq2d(mx - px[A], my - py[A]);
-    if (HAS_GOAL || KIND == MPE_SCN_SPEAKER_LISTENER) {
-      goal_pos<A, L>(px, py, goal, gx, gy);
-      X[(i * XW + 4) * kWave + lane] = sq2d(mx - gx, my - gy);
-    }
-    if constexpr (KIND == MPE_SCN_REFERENCE) {   // what the OTHER agent's reward needs: my distance to its goal landmark
-      goal_pos<A, L>(px, py, i == 0 ? pick1 : goal, gx, gy);
-      X[(i * XW + 4) * kWave + lane] = sq2d(mx - gx, my - gy);
-    }
-    if constexpr (KIND == MPE_SCN_WORLD_COMM) {  // am I inside forest 0 / forest 1 (landmarks 3, 4)?  strict dist < size + size
-#pragma unroll
-      for (int f = 0; f < 2; ++f)
-        X[(i * XW + 4 + f) * kWave + lane] =
-            sqrt_lt(sq2d(mx - px[A + 3 + f], my - py[A + 3 + f]), size_i + size_e[A + 3 + f]) ? 1.f : -1.f;
-    }
+    } else
+    SC::publish_extra(view(t, false), X);
   };
   // behind_barrier: the state store and the siblings' new positions
   auto behind_barrier = [&](const int t) {
@@ -1025,18 +688,7 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
       }
       did_reset = false;
     }
-    if constexpr (KIND == MPE_SCN_ADVERSARY && !ROLL) {
-      // benchmark_data (simple_adversary.py:57-67): the squared distance to the goal landmark (an adversary's datum, the
-      // last of a good agent's) and to every landmark (a good agent's first L) -- each agent wave writes its own
-      if (live && b.info_rew) {
-        store_aux<AUX>(b.info_rew + wave_off((size_t)i * B + w0) + ln, sq2d(mx - gx, my - gy));
-        if (b.info_min_dists) {
-#pragma unroll
-          for (int l = 0; l < L; ++l)
-            store_aux<AUX>(b.info_min_dists + wave_off(((size_t)l * A + i) * B + w0) + ln, sq2d(mx - px[A + l], my - py[A + l]));
-        }
-      }
-    }
+    if constexpr (!ROLL) SC::template benchmark_data<AUX>(view(t, false), b);   // (the per-agent info stores of a launched step)
     const float *const X = xch + (ROLL ? (t & 1) * A * XW * kWave : 0);
 #pragma unroll
     for (int a = 0; a < A; ++a) {
@@ -1049,271 +701,12 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
     for (int a = 0; a < A; ++a) asm volatile("" ::"v"(px[a]), "v"(py[a]));   // the siblings' positions have arrived
 #endif
   };
-  // POL: where the decision observation sits in the tile -- row width, row stride and this lane's piece swizzle (flush_rows'
-  // layouts)
-  [[maybe_unused]] int pol_D = 0, pol_S = 0, pol_sw = 0;
-  auto note_tile = [&](auto dc, auto pc) {
-    if constexpr (POL) {
-      constexpr int D = decltype(dc)::value;
-      constexpr bool P = decltype(pc)::value;
-      constexpr int NS = (P && row_vec4<D>()) ? D / 4 : 0;
-      pol_D = D;
-      pol_S = P ? pair_stride<D>() : tile_stride<D>();
-      pol_sw = NS ? swz4<NS>(lane) : 0;
-    }
-  };
   // rows: agent i's observation row of step t -- the 64 rows of the wave assembled in its LDS tile, streamed out.
   // pre (the policy rollout): the row of the state a step STARTS from (its first step, an episode start) is assembled in the
   // tile for the actor and not stored
   auto rows = [&](const int t, const bool pre) {
     if (MPE_SPLIT_ABLATE & 4) return;   // (no observation rows)
-    const float *const X = xch + (ROLL ? (t & 1) * A * XW * kWave : 0);
-    const uint64_t gt = ra.step0 + (uint64_t)t;   // global step (the word stream of the rollout)
-    float *const obs_t = b.obs + (size_t)block_of(t) * obs_stride;
-    [[maybe_unused]] const MpeBuffers bw = with_words(t);
-    if (KIND == MPE_SCN_SIMPLE) {  // simple.py:45-50
-      constexpr int D = 2 + 2 * L;
-      {
-        RowPairs<D> r(tile, lane);
-        r.put(0, mvx, mvy);
-#pragma unroll
-        for (int l = 0; l < L; ++l) r.put(2 + 2 * l, px[A + l] - mx, py[A + l] - my);
-      }
-      note_tile(std::integral_constant<int, D>{}, std::bool_constant<true>{});
-        if (!pre) flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
-    }
-    if (KIND == MPE_SCN_SPREAD) {  // simple_spread.py:84-100
-      constexpr int D = 4 + 2 * L + 4 * (A - 1);
-      {
-        RowPairs<D> r(tile, lane);
-        r.put(0, mvx, mvy);
-        r.put(2, mx, my);
-#pragma unroll
-        for (int l = 0; l < L; ++l) r.put(4 + 2 * l, px[A + l] - mx, py[A + l] - my);
-        int k = 4 + 2 * L;  // uniform running column
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-          if (j == i) continue;
-          r.put(k, px[j] - mx, py[j] - my);
-          k += 2;
-        }
-#pragma unroll
-        for (int z = 0; z < 2 * (A - 1); z += 2) r.put(k + z, 0.f, 0.f);  // silent agents' comm
-      }
-      note_tile(std::integral_constant<int, D>{}, std::bool_constant<true>{});
-        if (!pre) flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
-    }
-    if (KIND == MPE_SCN_TAG) {  // simple_tag.py:131-147
-      constexpr int NG = A - NADV;
-      constexpr int DA = 4 + 2 * L + 2 * (A - 1) + 2 * NG, DG = DA - 2;
-      const bool adv = i < NADV;
-      auto row = [&](auto dsel) {  // one observation row of width D (adversaries DA, good agents DG)
-        constexpr int D = decltype(dsel)::value;
-        {
-          RowPairs<D> r(tile, lane);
-          r.put(0, mvx, mvy);
-          r.put(2, mx, my);
-#pragma unroll
-          for (int l = 0; l < L; ++l) r.put(4 + 2 * l, px[A + l] - mx, py[A + l] - my);
-          int k = 4 + 2 * L;
-#pragma unroll
-          for (int j = 0; j < A; ++j) {
-            if (j == i) continue;
-            r.put(k, px[j] - mx, py[j] - my);
-            k += 2;
-          }
-#pragma unroll
-          for (int j = NADV; j < A; ++j) {
-            if (j == i) continue;
-            r.put(k, X[(j * XW + 2) * kWave + lane], X[(j * XW + 3) * kWave + lane]);
-            k += 2;
-          }
-        }
-        note_tile(std::integral_constant<int, D>{}, std::bool_constant<true>{});
-        if (!pre) flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
-      };
-      if (adv) row(std::integral_constant<int, DA>{});
-      else     row(std::integral_constant<int, DG>{});
-    }
-    if (KIND == MPE_SCN_ADVERSARY) {  // simple_adversary.py:121-139
-      constexpr int DG = 2 + 2 * L + 2 * (A - 1), DA = DG - 2;
-      const bool adv = i < NADV;
-      auto row = [&](auto dsel, auto good) {
-        constexpr int D = decltype(dsel)::value;
-        {
-          RowPairs<D> r(tile, lane);
-          int k = 0;
-          if (decltype(good)::value) { r.put(k, gx - mx, gy - my); k += 2; }
-#pragma unroll
-          for (int l = 0; l < L; ++l) { r.put(k, px[A + l] - mx, py[A + l] - my); k += 2; }
-#pragma unroll
-          for (int j = 0; j < A; ++j) {
-            if (j == i) continue;
-            r.put(k, px[j] - mx, py[j] - my);
-            k += 2;
-          }
-        }
-        note_tile(std::integral_constant<int, D>{}, std::bool_constant<true>{});
-        if (!pre) flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
-      };
-      if (adv) row(std::integral_constant<int, DA>{}, std::false_type{});
-      else     row(std::integral_constant<int, DG>{}, std::true_type{});
-    }
-    if constexpr (KIND == MPE_SCN_PUSH) {  // simple_push.py:78-96
-      constexpr int DG = 7 + 5 * L + 2 * (A - 1), DA = 2 + 2 * L + 2 * (A - 1);
-      const bool adv = i < NADV;
-      auto row = [&](auto dsel, auto good) {
-        constexpr int D = decltype(dsel)::value, RS = tile_stride<D>();
-        constexpr bool GOOD = decltype(good)::value;
-        int k = 0;
-        if (GOOD || (RS & 1)) { put1<RS>(tile, lane, k, mvx); put1<RS>(tile, lane, k + 1, mvy); }
-        else put2<RS>(tile, lane, k, mvx, mvy);
-        k += 2;
-        if (GOOD) {   // goal, own colour (0.25 grey, +0.5 on channel goal+1), later the landmark colours
-          put1<RS>(tile, lane, k, gx - mx); put1<RS>(tile, lane, k + 1, gy - my);
-          k += 2;
-#pragma unroll
-          for (int c = 0; c < 3; ++c) put1<RS>(tile, lane, k + c, (goal + 1 == c) ? 0.75f : 0.25f);
-          k += 3;
-        }
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-          if ((RS & 1) || (k & 1)) { put1<RS>(tile, lane, k, px[A + l] - mx); put1<RS>(tile, lane, k + 1, py[A + l] - my); }
-          else put2<RS>(tile, lane, k, px[A + l] - mx, py[A + l] - my);
-          k += 2;
-        }
-        if (GOOD) {
-#pragma unroll
-          for (int l = 0; l < L; ++l)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) put1<RS>(tile, lane, k + 3 * l + c, (l + 1 == c) ? (float)(0.1 + 0.8) : 0.1f);
-          k += 3 * L;
-        }
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-          if (j == i) continue;
-          if ((RS & 1) || (k & 1)) { put1<RS>(tile, lane, k, px[j] - mx); put1<RS>(tile, lane, k + 1, py[j] - my); }
-          else put2<RS>(tile, lane, k, px[j] - mx, py[j] - my);
-          k += 2;
-        }
-        note_tile(std::integral_constant<int, D>{}, std::bool_constant<false>{});
-        if (!pre) flush_rows<D, false, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
-      };
-      if (adv) row(std::integral_constant<int, DA>{}, std::false_type{});
-      else     row(std::integral_constant<int, DG>{}, std::true_type{});
-    }
-    if constexpr (KIND == MPE_SCN_SPEAKER_LISTENER) {  // simple_speaker_listener.py:69-92
-      if (i == 0) {   // speaker: the goal landmark's colour (0.65 on channel goal, 0.15 elsewhere)
-        constexpr int D = 3, RS = tile_stride<D>();
-#pragma unroll
-        for (int c = 0; c < 3; ++c) put1<RS>(tile, lane, c, goal == c ? 0.65f : 0.15f);
-        note_tile(std::integral_constant<int, D>{}, std::bool_constant<false>{});
-        if (!pre) flush_rows<D, false, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
-      } else {        // listener: vel, landmarks, what the speaker says
-        constexpr int D = 2 + 2 * L + DC, RS = tile_stride<D>();
-        put1<RS>(tile, lane, 0, mvx); put1<RS>(tile, lane, 1, mvy);
-#pragma unroll
-        for (int l = 0; l < L; ++l) { put1<RS>(tile, lane, 2 + 2 * l, px[A + l] - mx); put1<RS>(tile, lane, 3 + 2 * l, py[A + l] - my); }
-        const Word<WM> c0 = word_of<DC, WM>(bw, B, w0, ln, 0, ra.seed, gw, gt);
-#pragma unroll
-        for (int c = 0; c < DC; ++c) put1<RS>(tile, lane, 2 + 2 * L + c, c0[c]);
-        note_tile(std::integral_constant<int, D>{}, std::bool_constant<false>{});
-        if (!pre) flush_rows<D, false, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
-      }
-    }
-    if constexpr (KIND == MPE_SCN_REFERENCE) {  // simple_reference.py:63-83
-      constexpr int D = 2 + 2 * L + 3 + DC, RS = tile_stride<D>();
-      const int mine = i == 0 ? goal : pick1;   // agent.goal_b
-      put1<RS>(tile, lane, 0, mvx); put1<RS>(tile, lane, 1, mvy);
-#pragma unroll
-      for (int l = 0; l < L; ++l) { put1<RS>(tile, lane, 2 + 2 * l, px[A + l] - mx); put1<RS>(tile, lane, 3 + 2 * l, py[A + l] - my); }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) put1<RS>(tile, lane, 2 + 2 * L + c, mine == c ? 0.75f : 0.25f);   // goal_b.color
-      const Word<WM> co = word_of<DC, WM>(bw, B, w0, ln, 1 - i, ra.seed, gw, gt);
-#pragma unroll
-      for (int c = 0; c < DC; ++c) put1<RS>(tile, lane, 5 + 2 * L + c, co[c]);
-      note_tile(std::integral_constant<int, D>{}, std::bool_constant<false>{});
-        if (!pre) flush_rows<D, false, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
-    }
-    if constexpr (KIND == MPE_SCN_CRYPTO) {  // simple_crypto.py:127-169 (goal = pick 0, key = pick 1; colours are one-hots of width dim_c)
-      const Word<WM> cs = word_of<DC, WM>(bw, B, w0, ln, 2, ra.seed, gw, gt);   // the speaker's utterance
-      static_assert((DC & 1) == 0, "crypto rows are written as pairs");
-      if (i == 0) {          // Eve: what the speaker says
-        constexpr int D = DC;
-        RowPairs<D> r(tile, lane);
-#pragma unroll
-        for (int c = 0; c < DC; c += 2) r.put(c, cs[c], cs[c + 1]);
-        note_tile(std::integral_constant<int, D>{}, std::bool_constant<true>{});
-        if (!pre) flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
-      } else {
-        constexpr int D = 2 * DC;
-        RowPairs<D> r(tile, lane);
-        const int first = i == 1 ? pick1 : goal;   // Bob: key, utterance;  Alice: goal colour, key
-#pragma unroll
-        for (int c = 0; c < DC; c += 2) r.put(c, first == c ? 1.f : 0.f, first == c + 1 ? 1.f : 0.f);
-#pragma unroll
-        for (int c = 0; c < DC; c += 2) {
-          if (i == 1) r.put(DC + c, cs[c], cs[c + 1]);
-          else        r.put(DC + c, pick1 == c ? 1.f : 0.f, pick1 == c + 1 ? 1.f : 0.f);
-        }
-        note_tile(std::integral_constant<int, D>{}, std::bool_constant<true>{});
-        if (!pre) flush_rows<D, true, RP>(tile, obs_t + B * obs_off_i + w0 * D, nvalid, lane, d.vec4);
-      }
-    }
-    if constexpr (KIND == MPE_SCN_WORLD_COMM) {  // simple_world_comm.py:231-289
-      constexpr int NG = A - NADV;
-      constexpr int DA = 4 + 2 * L + 2 * (A - 1) + 2 * NG + 2 + DC, DGd = 4 + 2 * L + 2 * (A - 1) + 2 + 2 * (NG - 1);
-      const bool f1 = X[(i * XW + 4) * kWave + lane] > 0.f, f2 = X[(i * XW + 5) * kWave + lane] > 0.f;
-      bool vis[A];   // may agent i see agent j: same forest, or both in the open; the leader sees everybody (:253)
-#pragma unroll
-      for (int j = 0; j < A; ++j) {
-        const bool o1 = X[(j * XW + 4) * kWave + lane] > 0.f, o2 = X[(j * XW + 5) * kWave + lane] > 0.f;
-        vis[j] = i == 0 || (f1 && o1) || (f2 && o2) || (!f1 && !o1 && !f2 && !o2);
-      }
-      // (column-by-column 4-byte writes: building these rows from (x, y) pairs -- RowPairs, as the other scenarios do --
-      //  measured 1.5 us SLOWER here, 20.0 vs 18.6 us at B = 65536, same box)
-      auto row = [&](auto dsel, auto advt) {
-        constexpr int D = decltype(dsel)::value, RS = tile_stride<D>();
-        constexpr bool ADV = decltype(advt)::value;
-        constexpr bool HALF = S::trows(ROLL) == 32;   // 32-row tile: rows of worlds 0..31, then of worlds 32..63
-#pragma unroll
-        for (int h = 0; h < (HALF ? 2 : 1); ++h) {
-        const int r = HALF ? (lane & 31) : lane;
-        if (!HALF || (lane >> 5) == h) {
-        int k = 0;
-        put1<RS>(tile, r, 0, mvx); put1<RS>(tile, r, 1, mvy); put1<RS>(tile, r, 2, mx); put1<RS>(tile, r, 3, my);
-        k = 4;
-#pragma unroll
-        for (int l = 0; l < L; ++l) { put1<RS>(tile, r, k, px[A + l] - mx); put1<RS>(tile, r, k + 1, py[A + l] - my); k += 2; }
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-          if (j == i) continue;
-          put1<RS>(tile, r, k, vis[j] ? px[j] - mx : 0.f);
-          put1<RS>(tile, r, k + 1, vis[j] ? py[j] - my : 0.f);
-          k += 2;
-        }
-        if (!ADV) { put1<RS>(tile, r, k, f1 ? 1.f : -1.f); put1<RS>(tile, r, k + 1, f2 ? 1.f : -1.f); k += 2; }
-#pragma unroll
-        for (int j = NADV; j < A; ++j) {
-          if (j == i) continue;
-          put1<RS>(tile, r, k, vis[j] ? X[(j * XW + 2) * kWave + lane] : 0.f);
-          put1<RS>(tile, r, k + 1, vis[j] ? X[(j * XW + 3) * kWave + lane] : 0.f);
-          k += 2;
-        }
-        if (ADV) {
-          put1<RS>(tile, r, k, f1 ? 1.f : -1.f); put1<RS>(tile, r, k + 1, f2 ? 1.f : -1.f); k += 2;
-          const Word<WM> cl = word_of<DC, WM>(bw, B, w0, ln, 0, ra.seed, gw, gt);   // world.agents[0].state.c
-#pragma unroll
-          for (int c = 0; c < DC; ++c) put1<RS>(tile, r, k + c, cl[c]);
-        }
-        }
-        const int nv = HALF ? min(max(nvalid - 32 * h, 0), 32) : nvalid;   // uniform
-        if (nv > 0) flush_rows<D, false, RP>(tile, obs_t + B * obs_off_i + (w0 + (HALF ? 32 * h : 0)) * D, nv, lane, d.vec4);
-        }
-      };
-      if (i < NADV) row(std::integral_constant<int, DA>{}, std::true_type{});
-      else          row(std::integral_constant<int, DGd>{}, std::false_type{});
-    }
+    SC::rows(view(t, pre));
   };
   // decide (the policy rollout): step t's episode restart, then agent i's action row of step t from its actor.  The observation
   // of the state step t starts from is the tile's content -- the rows of step t - 1, still there -- except at the launch's first
@@ -1401,7 +794,7 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
           if (NCH >= 2) pick1 = choice_draw(ra.seed, gw, ep, 1, d.choice_pop[1]);
           ++ep;
         }
-        if (HAS_GOAL || KIND == MPE_SCN_SPEAKER_LISTENER) goal_pos<A, L>(px, py, goal, gx, gy);
+        if (HAS_GOAL) goal_pos<A, L>(px, py, goal, gx, gy);
         MPE_STAMP(2);
         __syncthreads();
         if (SERVE && aborted()) return;   // (step t was never commanded: its exchange block is stale)
@@ -1505,7 +898,7 @@ __device__ __forceinline__ void split_body(float *const g_pos, float *const g_ve
     store_aux<AUX>(b.choice + wave_off(w0) + ln, goal);
     if (NCH >= 2) store_aux<AUX>(b.choice + wave_off(B + w0) + ln, pick1);
   }
-  if (ROLL && ((speakers_of<KIND>() >> i) & 1u) && live && T > 0) {
+  if (ROLL && ((SC::speakers >> i) & 1u) && live && T > 0) {
     // update_agent_state (core.py:171-177): what agent i said at the last step is its comm state afterwards
     float *const mine = const_cast<float *>(b.comm) + wave_off(((size_t)i * B + w0) * DC) + ln * DC;
     const int id = comm_draw(ra.seed, gw, ra.step0 + (uint64_t)(T - 1), i, DC);
@@ -1565,13 +958,13 @@ template <int KIND, int A, int L, int NADV>
 constexpr SplitFn serve_fn() { return k_split<KIND, A, L, NADV, true, kRowsSc1, false, true>; }
 template <int KIND, int A, int L, int NADV>
 constexpr SplitFn serve_dual_fn() {
-  if constexpr (dual_kind<KIND>() && SplitShape<KIND, A, L, NADV>::waves(true) * kWave <= 1024)
+  if constexpr (dual_kind<Scn<KIND, A, L, NADV>>() && SplitShape<KIND, A, L, NADV>::waves(true) * kWave <= 1024)
     return k_split<KIND, A, L, NADV, true, kRowsSc1, true, true>;
   else return nullptr;
 }
 template <int KIND, int A, int L, int NADV, int RP>
 constexpr SplitFn dual_fn() {
-  if constexpr (dual_kind<KIND>() && SplitShape<KIND, A, L, NADV>::waves(true) * kWave <= 1024) return k_split<KIND, A, L, NADV, true, RP, true>;
+  if constexpr (dual_kind<Scn<KIND, A, L, NADV>>() && SplitShape<KIND, A, L, NADV>::waves(true) * kWave <= 1024) return k_split<KIND, A, L, NADV, true, RP, true>;
   else return nullptr;
 }
 #define MPE_SPLIT_ENTRY(KIND, A, L, NADV)                                                                         \
@@ -1676,8 +1069,12 @@ struct PolicyEntry {
   PolicyFn fn;
   size_t lds;
 };
-#define MPE_POLICY_ENTRY(KIND, A, L, NADV) \
-  { KIND, A, L, NADV, k_split_policy<KIND, A, L, NADV>, SplitShape<KIND, A, L, NADV>::lds_bytes(true) }
+template <int KIND, int A, int L, int NADV>
+constexpr PolicyEntry policy_entry() {
+  static_assert(Scn<KIND, A, L, NADV>::policy, "a policy rollout entry: a scenario whose rows read no other agent's velocity (Scn::policy)");
+  return {KIND, A, L, NADV, k_split_policy<KIND, A, L, NADV>, SplitShape<KIND, A, L, NADV>::lds_bytes(true)};
+}
+#define MPE_POLICY_ENTRY(KIND, A, L, NADV) policy_entry<KIND, A, L, NADV>()
 static const PolicyEntry kPolicyTable[] = {
     MPE_POLICY_ENTRY(MPE_SCN_SIMPLE, 1, 1, 0),
     MPE_POLICY_ENTRY(MPE_SCN_SPREAD, 1, 1, 0), MPE_POLICY_ENTRY(MPE_SCN_SPREAD, 2, 2, 0), MPE_POLICY_ENTRY(MPE_SCN_SPREAD, 3, 3, 0),
