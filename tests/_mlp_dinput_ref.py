@@ -20,9 +20,14 @@ CASES = [case("critics_M%d" % M, [CR, CRT], [0, 1], M, 100 + M) for M in (1, 63,
     case("wide_M65", [Net(256, (64, 64), 1, "relu", True)], [0], 65, 126),
 ]
 IDS = [c.name for c in CASES]
-# a block that walks two groups (host walk only): 514 groups in 257 blocks
+# a block that walks two groups: 514 groups in 257 blocks (the sanitizer host walk's own; the GPU runs SPAN2)
 WALK_EXTRA = case("span2_M32833", [Net(18, (64, 64), 1, "relu", True), Net(40, (), 3, "tanh", True)], [0, 1], ROWS * MAX_BLOCKS + 65, 131)
 KINDS = ["whole", "first", "last", "last5", "straddle"]
+# A block that walks two groups, on the GPU: the smallest M of span 2 -- 513 groups in 257 blocks, the last of one group holding one
+# row -- with a 256-wide net, whose output takes several rounds of the stage tile inside a multi-group block.  Not in CASES: the
+# host walk's sweep does not grow.  Windows: SPAN2_KINDS on the 16-byte path, SPAN2_SENTINEL_KINDS on the 4-byte path.
+SPAN2 = case("span2_M32769", [CR, CRT, Net(256, (64, 64), 1, "relu", True)], [0, 1, 2], ROWS * MAX_BLOCKS + 1, 141)
+SPAN2_KINDS, SPAN2_SENTINEL_KINDS = ["whole", "straddle"], ["last5"]
 
 
 def span(M):

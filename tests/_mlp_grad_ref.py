@@ -35,7 +35,16 @@ GPU_CASES = [case("M%d" % M, [ACTOR, ACTOR._replace(act="relu")], [0, 1], M, 10 
     case("spread_critics_M257", [CRITIC] * 3, [0, 1, 2], 257, 27, value=True),
 ]
 GPU_IDS = [c.name for c in GPU_CASES]
-# a span of 2 groups and the most chunks there are (host walk only)
+# Chunks of more than one group, on the GPU: the smallest M of span 2 and of span 3 whose last chunk is short and ends in a group of one
+# row (131 groups in 66 chunks, the last of one group; 257 groups in 86 chunks, the last of two), and a shared module at span 2 for the
+# fixed-order sum over 2 x 66 partials.  The sanitizer host walk does not take them (its span 2 is WALK_EXTRA).
+SPAN_CASES = [
+    case("span2_M8321", [ACTOR, ACTOR._replace(act="relu"), Net(40, (), 3, "relu", True)], [0, 1, 2], ROWS * MAX_CHUNKS + 2 * ROWS + 1, 41),
+    case("span3_M16385", [ACTOR, CRITIC, Net(33, (32,), 9, "relu", True)], [0, 1, 2], 2 * ROWS * MAX_CHUNKS + 1, 42),
+    case("shared_span2_M8321", [ACTOR._replace(act="relu")], [0, 0], ROWS * MAX_CHUNKS + 2 * ROWS + 1, 43),
+]
+SPAN_IDS = [c.name for c in SPAN_CASES]
+# a span of 2 groups and the most chunks there are: the sanitizer host walk's own (the GPU runs SPAN_CASES)
 WALK_EXTRA = case("span2_M8257", [Net(18, (64, 64), 5, "tanh", True), Net(40, (), 3, "relu", True)], [0, 1], 64 * MAX_CHUNKS + 65, 31)
 
 
@@ -137,6 +146,19 @@ def agent_grads64(net, params, x, dout):
         if l > 0:
             back = delta @ params[l][0].astype(F64).T
             delta = back * (1.0 - h_prev * h_prev) if net.act == "tanh" else np.where(h_prev > 0, back, 0.0)
+    return out
+
+
+def agent_deltas64(net, params, x, dout):
+    """-> [delta_l [M, out_l]] in float64: the rows that db_l is the column sum of (agent_grads64's own chain)"""
+    hs, _ = forward64(net, params, x)
+    L = len(net.hidden) + 1
+    delta, out = dout.astype(F64), [None] * L
+    for l in range(L - 1, -1, -1):
+        out[l] = delta
+        if l > 0:
+            back = delta @ params[l][0].astype(F64).T
+            delta = back * (1.0 - hs[l - 1] * hs[l - 1]) if net.act == "tanh" else np.where(hs[l - 1] > 0, back, 0.0)
     return out
 
 

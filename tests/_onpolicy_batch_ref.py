@@ -20,6 +20,10 @@ WIDE16 = [3, 1, 7, 257, 2, 5, 4, 9, 1, 6, 8, 2, 11, 3, 5, 4]
 SHAPES = [(1, 1, 1, [1], 0, 1), (2, 3, 7, [5, 1, 3], 0, 5), (25, 3, 65, [18, 18, 18], 0, 1625), (25, 3, 65, [18, 18, 18], 0, 400),
           (7, 16, 63, WIDE16, 4, 441), (3, 2, 1366, [16, 14], 0, 4098)]
 SHAPE_IDS = ["T%d_A%d_B%d_c%d_M%d" % (s[0], s[1], s[2], s[4], s[5]) for s in SHAPES]
+# the statistics alone, on the GPU: N = T * B = 1 048 578 is 257 chunks of 4096, which the second launch takes in pieces of 256 -- a
+# second piece of one chunk of two elements.  Not in SHAPES: the batch sweep and the host walk do not take it.
+STATS_SHAPES = [(2, 2, 524289, [1, 1], 0, 1)]
+STATS_IDS = ["T%d_A%d_B%d_stats_only" % s[:3] for s in STATS_SHAPES]
 SEED = 0x1234567800000055      # (a non-zero high word)
 
 
@@ -145,6 +149,13 @@ def make_traj(shape, seed=0):
     tr["val"] = rs.standard_normal((T, A, B)).astype(np.float32)
     tr["ret"] = (tr["adv"] + tr["val"]).astype(np.float32)
     return tr
+
+
+def make_adv(shape, seed=0):
+    """-> adv [T, A, B] float32 alone, drawn as make_traj draws it (what the statistics read)"""
+    T, A, B = shape[:3]
+    rs = np.random.RandomState(200 + seed + T + 7 * A + 13 * B)
+    return (0.3 + 2.0 * rs.standard_normal((T, A, B))).astype(np.float32)
 
 
 def batch(tr, shape, idx, stats=None):

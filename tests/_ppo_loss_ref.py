@@ -44,6 +44,17 @@ GPU_CASES = [
     _PAIR.but("pair_value_clip_off_ent_0", value_clip=None, ent_coef=0.0),
 ]
 GPU_IDS = [c.name for c in GPU_CASES]
+# The second launch's loops past their first trip, on the GPU (the float64 torch comparison and the host walk do not take them).  It
+# stages the chunks' partials in pieces of 6144 / (6 A) chunks and loads a piece of one agent, 6 x chunks doubles, 8 x 256 at a trip:
+# 16 movers, 65 chunks in pieces of 64 -- a second piece of one chunk of one row; the pair at 342 chunks, ONE piece of 2052 doubles
+# per agent -- a second trip of the load; one mover, 1025 chunks in pieces of 1024 -- three trips and a second piece of one chunk of
+# one row.  With these seeds the band holds 9, 7 and 6 agent-rows (test_band_rows_are_at_most_a_thousandth).
+PIECE_CASES = [
+    Case("A16_M16385", [MOVER] * 16, 0, 64 * BLOCK + 1, 41),
+    Case("pair_A2_M87297", [SPEAKER, MOVER], 3, 341 * BLOCK + 1, 44),
+    Case("A1_M262145", [MOVER], 0, 1024 * BLOCK + 1, 42),
+]
+PIECE_IDS = [c.name for c in PIECE_CASES]
 
 # the host walk's sweep: every M x the three head layouts x A in (1, 3)
 WALK_M = [1, 63, 64, 65, 255, 256, 257, 513]

@@ -4,6 +4,9 @@ inside, sentinels behind row M; mpe_policy_rows_grad, ActorLoss and the losses w
 autograd's deviation from the float64 restatement on this GPU, floor 2 ulps); the prioritized buffer's wiring; a whole MADDPG update
 captured as ONE HIP graph; and the example's --device-update mode.
 
+mpe_td_loss also runs where its second launch (k_ddpg_finish, the PPO head's two loops over the chunks' partials) takes a second piece
+and a second trip of a piece's load: (L32, 16385), (L22, 87297) and (L22, 131073), bit-equal like every other shape.
+
 Recorded on an MI355X: profiles/ddpg_parity.json (tools/ddpg_parity.py)."""
 import copy
 import json
@@ -71,8 +74,14 @@ def _parity_out():
 
 
 # ---- THE TD LOSS RULE ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", LAYOUT_IDS)
-@pytest.mark.parametrize("M", R.ROWS)
+# The second launch (k_ddpg_finish: the PPO head's loops over the chunks' partials) past each loop's first trip: pieces of 6144 / (6 A)
+# chunks, a piece of one agent loaded 8 x 256 doubles at a trip.  A = 16, 65 chunks in pieces of 64: a second piece of one chunk of
+# one row; A = 2, 342 chunks in one piece of 2052 doubles per agent: a second trip of the load; A = 2, 513 chunks in pieces of 512: a
+# second piece.
+TD_SECOND_TRIPS = [(16385, "L32"), (87297, "L22"), (131073, "L22")]
+
+
+@pytest.mark.parametrize("M,name", [(M, name) for M in R.ROWS for name in LAYOUT_IDS] + TD_SECOND_TRIPS)
 def test_td_loss_bit_equal_to_the_restatement(M, name):
     """with and without the weights; the A [M] blocks at their own addresses; a second run gives the same bits"""
     lay = R.LAYOUTS[name]

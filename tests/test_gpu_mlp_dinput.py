@@ -4,7 +4,14 @@ sentinels around and between the rows of every output on the 4-byte store path, 
 function of that row alone (bit for bit: alone, at another position, permuted, as part of a wider window), MADDPG's actor loss on a
 real env through Trainable(Actors) -> softmax -> Trainable(Critics, input_grad=True, weight_grad=False), and the actor update's
 device half inside one HIP graph.  Every index of the launch was walked on the host first (tests/test_mlp_dinput_cpu.py, whose
-docstring also says why the rule adds a hidden unit's bias last and cuts its sums into four chains)."""
+docstring also says why the rule adds a hidden unit's bias last and cuts its sums into four chains).
+
+A block of two groups runs on the device too (_mlp_dinput_ref.SPAN2: M = 32769, 257 blocks, the last of one group holding one row,
+with a 256-wide net whose output takes several rounds of the stage tile): the second group's P2 writes the tile the first group's last
+round was stored from, with one barrier between them.  It takes the parity and the sentinel checks on three windows, and the one
+launch is held, bit for bit, against rows [0, 32768) (span 1) and row 32768 run as launches of their own.  Measured on an MI355X
+(profiles/mlp_dinput_parity.json): the identity holds, and the closest window stands at 0.16 of its bound (window (30, 6), agent 0:
+5.2e-13, torch 8.3e-13)."""
 import copy
 import ctypes as C
 import json
@@ -93,7 +100,11 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
-@pytest.mark.parametrize("case,kind", D.runs(), ids=[D.run_id(r) for r in D.runs()])
+SPAN2_RUNS = [(D.SPAN2, k) for k in D.SPAN2_KINDS]
+SPAN2_SENTINEL_RUNS = [(D.SPAN2, k) for k in D.SPAN2_SENTINEL_KINDS]
+
+
+@pytest.mark.parametrize("case,kind", D.runs() + SPAN2_RUNS, ids=[D.run_id(r) for r in D.runs() + SPAN2_RUNS])
 def test_parity_with_the_float64_restatement(case, kind):
     """Every agent's window: |kernel - float64| <= max(4 x |float32 torch autograd on this GPU - float64|, 2 ulps of the window's
     largest magnitude).  tail_bias3_M65 is the test of the tail rows and of saturated Tanh units; mixed_M65 of D = 1, 31, 32, 33, 256
@@ -118,7 +129,7 @@ def test_parity_with_the_float64_restatement(case, kind):
         assert np.array_equal(_bits(g), _bits(wh[:, c0:c0 + nc])), (case.name, kind)
 
 
-@pytest.mark.parametrize("case,kind", D.runs(), ids=[D.run_id(r) for r in D.runs()])
+@pytest.mark.parametrize("case,kind", D.runs() + SPAN2_SENTINEL_RUNS, ids=[D.run_id(r) for r in D.runs() + SPAN2_SENTINEL_RUNS])
 def test_sentinels_and_a_second_run_on_the_four_byte_path(case, kind):
     """ld = ncol + 3, 64 sentinel floats around every din, two sentinel rows behind row M - 1, in and dout 4 bytes into their
     allocations: nothing outside the windows changes, the inputs are only read, two runs are bit-equal, and the values are those of
@@ -151,6 +162,21 @@ def test_a_row_depends_on_that_row_alone_bit_for_bit():
     perm = np.random.RandomState(3).permutation(case.M)
     got, ok = _launch(case, run["x"], win, rows=perm)
     assert ok and all(np.array_equal(_bits(g), _bits(wh[perm])) for g, wh in zip(got, run["whole"]))
+
+
+def test_a_block_of_two_groups_is_its_groups_run_apart_bit_for_bit():
+    """span2_M32769, the whole row: 257 blocks of two groups, the last of one group holding one row.  A row's result depends on that
+    row alone, so the one launch equals, bit for bit, rows [0, 32768) run as a launch of their own (span 1, 512 blocks of one group)
+    followed by row 32768 run alone -- unless a block's second group meets what its first left in the tiles."""
+    case = D.SPAN2
+    assert (D.span(case.M), D.blocks(case.M), D.span(case.M - 1), D.blocks(case.M - 1)) == (2, 257, 1, 512)
+    run = _case_run(case)
+    win = D.windows(case, "whole")
+    head, ok_h = _launch(case, run["x"], win, rows=np.arange(case.M - 1))
+    tail, ok_t = _launch(case, run["x"], win, rows=[case.M - 1])
+    assert run["intact"] and ok_h and ok_t
+    for i in range(len(case.agents)):
+        assert np.array_equal(_bits(run["whole"][i]), _bits(np.concatenate([head[i], tail[i]]))), i
 
 
 # ---- behind torch autograd, on a real env ---------------------------------------------------------------------------------------------

@@ -5,6 +5,15 @@ biases of +-3, shared modules as the fixed-order sum of the per-agent partials, 
 whole minibatch update's device half inside one HIP graph.  Every index of both launches was walked on the host first
 (tests/test_mlp_grad_cpu.py).
 
+Chunks of more than one group run on the device too (_mlp_grad_ref.SPAN_CASES: M = 8321, span 2, and M = 16385, span 3, each with a
+short last chunk that ends in a group of one row): a workgroup's second and third trip through its group loop reuse the three LDS
+tiles with one barrier between the trips and carry the dW accumulators and the float64 bias sums across it, which a sequential host
+walk cannot get wrong.  They take every check above, and a chunk's partial is held, bit for bit, against the ordered float32 sum of
+its groups' partials from launches of their own; mlp_grad_tensors at span 2 against the ABI launch's bits.  Measured on an
+MI355X (profiles/mlp_grad_parity.json): every identity holds, and the closest block of the three cases stands at 0.22 of its bound
+(span2_M8321, db_0 of module 0: 4.2e-10, torch 4.8e-10; span3_M16385 0.22, shared_span2_M8321 0.18) -- the float32 carry over a
+chunk's groups costs nothing that shows.
+
 Recorded miss (before any GPU run, on the host walk, which uses libm's exp2f and an exact divide -- more accurate than the hardware's):
 with the forward's Tanh, 1 - 2 / (exp2(x * 2 log2 e) + 1), in the recompute, the case tail_bias3_M65 missed the bound on block db0 of
 the 18-33-5 Tanh net -- deviation 8.5e-09 against a bound of 7.4e-09 (4 x torch's 1.86e-09; largest magnitude 2.2e-03) -- and over
@@ -37,20 +46,22 @@ def _dev():
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def _launch(case, x, agents=None):
+def _launch(case, x, agents=None, rows=None):
     """mpe_mlp_grad at the ABI on sentinel-padded grad and work -> (grad, work as NumPy; the padding is intact and all of work was
-    written).  agents: run only these agents of the case, as a set of their own (same packed weights, same offsets)."""
+    written).  agents: run only these agents of the case, as a set of their own (same packed weights, same offsets).  rows: run
+    these rows of the case's inputs (an index array) in place of all M."""
     dev = _dev()
-    sub = case if agents is None else case._replace(agents=tuple(case.agents[i] for i in agents))
+    sel = np.arange(case.M) if rows is None else np.asarray(rows)
+    sub = case._replace(M=len(sel)) if agents is None else case._replace(agents=tuple(case.agents[i] for i in agents), M=len(sel))
     idx = list(range(len(case.agents))) if agents is None else list(agents)
-    A, M = len(idx), case.M
+    A, M = len(idx), len(sel)
     _, total = R.offsets(case)
     w = torch.tensor(R.pack(case, x), device=dev)
     assert w.data_ptr() % 16 == 0
     shift = 1 if case.shift else 0
     held, ins, douts = [], [], []
     for i in idx:
-        for src, dst in ((x["in"][i], ins), (x["dout"][i], douts)):
+        for src, dst in ((x["in"][i] if rows is None else x["in"][i][sel], ins), (x["dout"][i] if rows is None else x["dout"][i][sel], douts)):
             flat = torch.full((src.size + shift,), SENTINEL, dtype=torch.float32, device=dev)
             flat[shift:] = torch.tensor(src, device=dev).reshape(-1)
             held.append(flat)
@@ -87,7 +98,7 @@ def _case_run(case):
     return hit
 
 
-@pytest.mark.parametrize("case", R.GPU_CASES, ids=R.GPU_IDS)
+@pytest.mark.parametrize("case", R.GPU_CASES + R.SPAN_CASES, ids=R.GPU_IDS + R.SPAN_IDS)
 def test_parity_with_the_float64_restatement(case):
     """Every block of every module: |kernel - float64| <= max(4 x |float32 torch on this GPU - float64|, 2 ulps of the block's largest
     magnitude).  tail_bias3_M65 is the test of the tail rows: row 65's group has 63 rows beyond M whose hidden activations are
@@ -107,7 +118,7 @@ def test_parity_with_the_float64_restatement(case):
         assert mag > 0 and dev <= b[key], (case.name, key, dev, dt[key][0], b[key], mag)
 
 
-@pytest.mark.parametrize("case", R.GPU_CASES, ids=R.GPU_IDS)
+@pytest.mark.parametrize("case", R.GPU_CASES + R.SPAN_CASES, ids=R.GPU_IDS + R.SPAN_IDS)
 def test_deterministic_padding_zero_and_nothing_written_out_of_range(case):
     """64 sentinel floats in front of and behind grad and work are intact, every float of work was written, every padding entry of
     the packed gradient is bit-equal to +0.0f, and a second launch writes the same bits to grad and to work."""
@@ -131,7 +142,7 @@ def _bias_slots(net):
     return out
 
 
-@pytest.mark.parametrize("case", [c for c in R.GPU_CASES if c.name.startswith("shared")], ids=lambda c: c.name)
+@pytest.mark.parametrize("case", [c for c in R.GPU_CASES + R.SPAN_CASES if c.name.startswith("shared")], ids=lambda c: c.name)
 def test_shared_module_is_the_fixed_order_sum_of_the_per_agent_partials(case):
     """Each agent run alone leaves its chunks' partials in work; the shared run's block of grad is, bit for bit, their sum in
     float64 -- agents ascending, each agent's chunks ascending, a bias entry's high halves and then its low halves -- rounded once."""
@@ -158,6 +169,91 @@ def test_shared_module_is_the_fixed_order_sum_of_the_per_agent_partials(case):
         got = run["grad"][off[m]:off[m] + size]
         mask = got.view(np.uint32) != 0      # (a padding entry is +0.0f whatever the partials hold)
         assert mask.sum() > size // 4 and np.array_equal(got[mask].view(np.uint32), want[mask].view(np.uint32)), (case.name, m)
+
+
+# ---- a chunk of several groups ------------------------------------------------------------------------------------------------------
+def _layer_of_slot(net):
+    """(layer, unit) of every entry of _bias_slots(net), in its order"""
+    L = len(net.hidden) + 1
+    return [(l, j) for l in range(L) for j in range(R.LW if l == L - 1 else R.HW)]
+
+
+@pytest.mark.parametrize("case", R.SPAN_CASES[:2], ids=R.SPAN_IDS[:2])
+def test_a_chunks_partial_is_the_ordered_sum_of_its_groups_partials(case):
+    """Chunk c of a span >= 2 launch against its groups launched alone (rows [64 g, min(64 g + 64, M)), one agent: span 1, one chunk,
+    the launch the M = 1, 63 and 64 cases hold against float64), for every chunk of every agent, the short last chunk included.
+
+    dW (every entry of the partial that is no bias entry): bit for bit ((+0 + p_g0) + p_g1) [+ p_g2] in float32 -- the chunk's
+    accumulator starts at +0 and takes each group's four-chain sum whole, and so does a group's own launch.
+
+    db: the chunk adds its 64 span tile values t_r ascending in float64 and splits once; the groups add 64 each and split each.  With
+    u = 2^-53 and S = sum over the chunk's rows of |t_r|: the chunk's sum is off the exact one by at most 64 span u S, the groups'
+    sums together by 64 u S; a split (hi = fl32(d), lo = fl32(d - hi)) returns d within 2^-48 |d| <= 2^-48 S, the chunk's and the
+    groups' together 2 x 2^-48 S = 128 u S; hi + lo is exact in float64 (53 bits span both halves) and adding the groups' pairs here
+    rounds span - 1 times, below span u S.  Together (65 span + 192) u S.  S is taken from the float64 restatement's delta rows and
+    doubled, which covers the kernel's float32 t_r beside them (they agree to parts in 1e6 wherever the parity test holds):
+    |(hi + lo)_chunk - sum_g (hi_g + lo_g)| <= 2 (65 span + 192) 2^-53 S_64, at span 3 8.6e-14 S_64 -- against a float32 ulp of a value of
+    S's size, >= 6e-8 S: five orders of magnitude below it, which the test asserts.  Against an ulp of the ENTRY it depends on how far
+    the chunk's rows cancel: the test asserts the bound of every bias block below a hundredth of a float32 ulp of the block's largest
+    entry in that chunk and prints the largest such fraction (the float64 restatement alone gives 3.2e-05 and 3.4e-03 for the two cases)."""
+    run = _case_run(case)
+    x, M, span, chunks = run["x"], case.M, R.span(case.M), R.chunks(case.M)
+    assert span >= 2 and M - (chunks - 1) * span * R.ROWS <= (span - 1) * R.ROWS and (M - 1) % R.ROWS == 0      # a short last chunk, one last row
+    at, worst = 0, 0.0
+    for i, m in enumerate(case.agents):
+        net, size = case.nets[m], R.module_size(case.nets[m])
+        ps = size + R.BIAS_SLOTS
+        whole = run["work"][at:at + chunks * ps].reshape(chunks, ps)
+        at += chunks * ps
+        slots, where = _bias_slots(net), _layer_of_slot(net)
+        hi_at, lo_at = [e for e, _ in slots], [size + s for _, s in slots]
+        is_dw = np.ones(size, bool)
+        is_dw[hi_at] = False
+        w = R.widths(net)
+        live = sum(w[l] * w[l + 1] for l in range(len(w) - 1))
+        deltas = [np.abs(d) for d in R.agent_deltas64(net, x["params"][m], x["in"][i], x["dout"][i])]
+        for c in range(chunks):
+            g0, g1 = c * span, min((c + 1) * span, R.groups(M))
+            acc, pairs = np.zeros(size, np.float32), np.zeros(len(slots), np.float64)
+            for g in range(g0, g1):
+                _, part, intact = _launch(case, x, agents=[i], rows=np.arange(g * R.ROWS, min((g + 1) * R.ROWS, M)))
+                assert intact and part.size == ps
+                acc = acc + part[:size]      # float32, groups ascending
+                pairs = pairs + (part[hi_at].astype(np.float64) + part[lo_at].astype(np.float64))
+            assert acc.dtype == np.float32
+            assert np.array_equal(whole[c, :size][is_dw].view(np.uint32), acc[is_dw].view(np.uint32)), (case.name, i, c)
+            assert np.count_nonzero(acc[is_dw]) >= live // 8      # (a ReLU net's one-row chunk leaves the dead units' entries at zero)
+            got = whole[c, hi_at].astype(np.float64) + whole[c, lo_at].astype(np.float64)
+            r0, r1 = g0 * R.ROWS, min(g1 * R.ROWS, M)
+            sums = [d[r0:r1].sum(axis=0) for d in deltas]
+            S = np.array([sums[l][j] if j < sums[l].size else 0.0 for l, j in where])
+            bound = 2.0 * (65 * span + 192) * 2.0 ** -53 * S
+            assert np.all(np.abs(got - pairs) <= bound), (case.name, i, c, float(np.abs(got - pairs).max()))
+            for l in range(len(deltas)):
+                blk = np.array([w[0] == l for w in where])
+                ulp = float(np.spacing(np.float32(np.abs(got[blk]).max())))
+                assert bound[blk].max() <= 1e-5 * float(np.spacing(np.float32(S[blk].max())))
+                assert ulp > 0 and bound[blk].max() <= 1e-2 * ulp, (case.name, i, c, l, float(bound[blk].max()), ulp)
+                worst = max(worst, float(bound[blk].max()) / ulp)
+    assert at == run["work"].size
+    print("%s: %d chunks; the largest db bound is %.2e of a float32 ulp of its block's largest entry" % (case.name, chunks, worst))
+
+
+def test_mlp_grad_tensors_at_span_2_is_the_abi_launch():
+    """mlp_grad_tensors at M = 8321 (66 chunks of 2 groups: the Python side's workspace size at span 2): the packed gradient and the
+    workspace are the ABI launch's bits."""
+    case = R.case("tensors_span2_M8321", [R.ACTOR] * 3, [0, 1, 2], R.SPAN_CASES[0].M, 44)
+    assert (R.span(case.M), R.chunks(case.M)) == (2, 66)
+    x = R.make_inputs(case)
+    grad, work, intact = _launch(case, x)
+    assert intact
+    env = mpe.make_env("simple_spread", batch_size=4, seed=2)
+    net = Actors(env, R.torch_modules(case, x, torch.float32, device=_dev()), mode="softmax", logits=True)
+    res = mlp_grad_tensors(net, [torch.tensor(a, device=_dev()) for a in x["in"]], [torch.tensor(a, device=_dev()) for a in x["dout"]])
+    torch.cuda.synchronize()
+    assert res.work.numel() == work.size == R.work_floats(case)
+    assert np.array_equal(res.packed.cpu().numpy().view(np.uint32), grad.view(np.uint32))
+    assert np.array_equal(res.work.cpu().numpy().view(np.uint32), work.view(np.uint32))
 
 
 # ---- behind torch autograd ----------------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """On-policy minibatches on the device: mpe_adv_stats and mpe_onpolicy_batch bit-equal to the NumPy restatements of
 THE ADVANTAGE STATISTICS RULE and THE MINIBATCH RULE (tests/_onpolicy_batch_ref.py) over the sweep's shapes, Minibatches end to end
-behind PolicyLoop.run(values=) and gae, and {adv_stats, batch} inside a HIP graph with a device epoch counter.  Every index of
+behind PolicyLoop.run(values=) and gae, and {adv_stats, batch} inside a HIP graph with a device epoch counter.  mpe_adv_stats also
+runs at N = T * B = 1 048 578 (257 chunks): its second launch stages the chunks' partials 256 at a time, and this is the one shape
+that takes a second piece.  Every index of
 both kernels was walked on the CPU under AddressSanitizer first
 (tests/test_onpolicy_batch_cpu.py::test_host_walk_every_block_job_and_lane_under_the_sanitizers)."""
 import numpy as np
@@ -24,7 +26,7 @@ def _case(shape):
     """the synthetic trajectory and the restatement's statistics, computed once per shape and left unchanged"""
     key = (shape[0], shape[1], shape[2], tuple(shape[3]), shape[4])
     if key not in _REF:
-        tr = R.make_traj(shape)
+        tr = {"adv": R.make_adv(shape)} if shape in R.STATS_SHAPES else R.make_traj(shape)
         stats = R.adv_stats(tr["adv"])
         for x in list(tr.values()) + [stats]:
             if x is not None:
@@ -34,8 +36,10 @@ def _case(shape):
 
 
 # ---- the kernel sweep at the ABI --------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", R.SHAPES, ids=R.SHAPE_IDS)
+@pytest.mark.parametrize("shape", R.SHAPES + R.STATS_SHAPES, ids=R.SHAPE_IDS + R.STATS_IDS)
 def test_adv_stats_kernel_sweep(shape):
+    """the workspace zeroed and poisoned.  The last shape has N = T * B = 1 048 578, 257 chunks: k_adv_finish stages a second piece --
+    one chunk of two elements -- into the LDS arrays its lanes have just added from."""
     tr, stats = _case(shape)
     dt = R.device_traj({"adv": tr["adv"]})
     for poison in (False, True):

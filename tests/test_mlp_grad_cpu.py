@@ -142,7 +142,8 @@ def test_mlp_grad_work_refusal_ladder_and_counts():
         s["M"] = M
         assert (R.chunks(M), R.span(M) * 64) == (chunks, per)
         assert L_.mpe_mlp_grad_work(C.byref(_set(s)), M) == 3 * (size + 144) * chunks      # (weights NULL: host only, not read)
-    for c in R.GPU_CASES + [R.WALK_EXTRA]:
+    assert [(R.groups(c.M), R.span(c.M), R.chunks(c.M)) for c in R.SPAN_CASES] == [(131, 2, 66), (257, 3, 86), (131, 2, 66)]
+    for c in R.GPU_CASES + R.SPAN_CASES + [R.WALK_EXTRA]:
         a = R.fill_set(_abi.MpeActorSet(), c, None, _abi.MPE_POLICY_VALUE if c.value else _abi.MPE_POLICY_GREEDY)
         assert L_.mpe_mlp_grad_work(C.byref(a), c.M) == R.work_floats(c), c.name
 
@@ -259,7 +260,7 @@ def test_host_walk_most_chunks_and_a_span_of_two_groups(host_walk, tmp_path):
 
 
 # ---- the fixture condition of the ReLU cases --------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", R.GPU_CASES, ids=R.GPU_IDS)
+@pytest.mark.parametrize("case", R.GPU_CASES + R.SPAN_CASES, ids=R.GPU_IDS + R.SPAN_IDS)
 def test_no_relu_row_is_in_the_band(case):
     """A ReLU unit whose pre-activation lies within 1e-4 of 0 can flip between float32 and float64 and change the gradient by its
     whole contribution: make_inputs redraws such rows, and none is left."""

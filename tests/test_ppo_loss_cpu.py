@@ -285,7 +285,7 @@ def test_host_walk_every_block_wave_and_lane_under_the_sanitizers(M, layout, A, 
 
 
 # ---- the band condition of the GPU test's fixed inputs ------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", R.GPU_CASES, ids=R.GPU_IDS)
+@pytest.mark.parametrize("case", R.GPU_CASES + R.PIECE_CASES, ids=R.GPU_IDS + R.PIECE_IDS)
 def test_band_rows_are_at_most_a_thousandth(case):
     """Rows whose ratio lies within 1e-5 (relative) of 1 +- clip, whose |v - val_old| lies within 1e-6 of value_clip, or whose two
     value branches lie within 1e-6 (relative) of each other outside the clip may take the other side of a select in float32: the
