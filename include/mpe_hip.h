@@ -406,6 +406,18 @@ int mpe_actor_supported(const MpeActorSet *set, int64_t B);
  * outputs of the last layer, zero beyond n_out.                                                                             */
 int mpe_actor_act(const MpeActorSet *set, const float *const *obs_ptrs, int64_t B, uint64_t step, int64_t world_offset,
                   float *moves, float *utter, int32_t *ids, float *logp, float *logits, void *stream);
+/* mpe_actor_act_explore: mpe_actor_act of a MPE_POLICY_GREEDY set whose heads explore (epsilon-greedy).
+ *   THE EXPLORATION RULE (all integer).  E = min(65536, floor(epsilon * 65536 + 0.5)), computed on the host.  A head of n logits
+ *   draws 32 bits b: the move head policy_bits(seed, world, step, agent), the utterance head policy_comm_bits(...) -- the SAMPLE
+ *   draws' own counters and streams (MPE_STREAM_POLICY / MPE_STREAM_POLICY_COMM; world = world_offset + the world's index).  The
+ *   head explores iff (b >> 16) < E, and then the chosen index is ((b & 0xffff) * n) >> 16; otherwise it plays GREEDY's choice
+ *   (the argmax, ties to the lowest index).  The heads of one agent decide independently.  moves / utter carry the one-hot row of
+ *   the index actually chosen, and ids and logp are GREEDY's for that index (logp = log softmax(z)[chosen]).  E == 0 draws nothing
+ *   and is bit-equal in every output to mpe_actor_act; E == 65536 explores everywhere.
+ * Refused by name: everything mpe_actor_act refuses of a set; a set whose mode is not MPE_POLICY_GREEDY; an epsilon that is not
+ * finite or lies outside [0, 1]; then mpe_actor_act's checks of B, the weights, obs_ptrs, moves and logits.                    */
+int mpe_actor_act_explore(const MpeActorSet *set, const float *const *obs_ptrs, int64_t B, uint64_t step, int64_t world_offset,
+                          double epsilon, float *moves, float *utter, int32_t *ids, float *logp, float *logits, void *stream);
 
 /* ---- TD targets: target actors and target critics over M sampled rows, two launches of the kernel above ------
  * mpe_actor_act_rows is mpe_actor_act over M rows of any origin (a sampled minibatch's next observations): B reads M, and row m
@@ -846,6 +858,54 @@ int64_t mpe_policy_rows_grad_work(int32_t A, int64_t M);
 int mpe_policy_rows_grad(const MpePolicyRows *cfg, const float *const *logits_ptrs, const float *const *g_ptrs, int64_t M,
                          float *const *dlogits_ptrs, const float *q, double *work, float *stats, float *loss, void *stream);
 int mpe_polyak(const MpePolyak *cfg, void *stream);
+
+/* ---- the value-based learners' loss head: independent Q-learning and VDN, plain and double-Q targets (csrc/mpe_qloss.hip) --------
+ * A Q-network is an actor set whose logits are action values: agent i's n_i = 5 * movable + dim_c * speaks logits, the move head
+ * first.  mpe_q_loss goes from the logits to dL/dlogits in two launches.  Inputs: q_ptrs[i]: agent i's online
+ * logits of the batch's observations, contiguous [M][n_i] (a HOST array of A device pointers); next_target [A][M][16]: the TARGET
+ * net's logits of the next observations, as mpe_actor_act_rows writes `logits`; next_online [A][M][16] or NULL: the ONLINE net's
+ * (double-Q); act [A][M][5] and utter [A][M][dim_c]: the batch's action rows -- the chosen index of a head is the lowest index of
+ * its row's maximum (np.argmax), so one-hot and softmax rows both serve; td: the MpeTdTarget of mpe_critic_q (ret [A][M], done
+ * [A][M], discount [M] or gamma); weights [M] or NULL; cfg: A, dim_c, movable[], speaks[] (speaks counts only with dim_c > 0) and
+ * mix.  Mf = (float) M; d_m = discount ? discount[m] : gamma.
+ *
+ * THE Q LOSS RULE.  All of it float32, each operation rounded on its own in the order written (no fused multiply-add), no
+ * transcendental.  Per agent i and row m, with z the row of q_ptrs[i], T the row of next_target and S the row of next_online
+ * (S = T when it is NULL):
+ *   q_i = the sum over the agent's heads, the move head first, of z[chosen index of the head];
+ *   v_i = the sum over the heads, the move head first, of T[k], k the lowest index of the head's maximum of S.
+ * MPE_Q_INDEPENDENT, per agent (THE TD-TARGET RULE and THE TD LOSS RULE):
+ *   y_i = done_i ? ret_i : ret_i + d_m * v_i;  d = q_i - y_i;  wd = w_m * d (weights NULL: wd = d);  sq = wd * d;  g = (2 * wd) / Mf
+ *   td_abs[m] = the largest |d_i| over the agents in ascending i as a select (a NaN |d_i| stays); loss = the sum of the L_i.
+ * MPE_Q_VDN, per row: Q = ((q_0 + q_1) + ..) and V likewise in ascending i; r = ((ret_0 + ret_1) + ..) * (1.0f / (float) A);
+ *   done = any done_i;  y = done ? r : r + d_m * V;  d = Q - y;  wd, sq, g as above;  td_abs[m] = |d|;
+ *   every agent's row of y holds the team's y, and the loss is the team's L = mean sq.
+ * dq_ptrs[i] [M][n_i] = dL/dlogits: g at the chosen column of each head and +0.0 everywhere else; every float is stored exactly
+ * once, the rows leave through the wave's LDS tile as mpe_ppo_loss's do (16-byte pieces where dq_ptrs[i] is 16-byte aligned).
+ * q_taken [A][M] = q_i; y [A][M].  Per agent sq, |d|, q_i and y (VDN: the team's sq, |d| and y in every agent's sums) are summed
+ * in THE PPO LOSS RULE's order; stats [A][8] = mean sq (= L_i), mean |d|, mean q_i, mean y, 0, 0, L_i, 0; loss [1]; work:
+ * mpe_q_loss_work(A, M) doubles, 8-byte aligned, every one written before it is read.  No atomics, no host synchronisation, no
+ * scratch; the results are a function of the inputs alone, bit-equal to a NumPy restatement (tests/_q_loss_ref.py), and a row's
+ * q_taken, y, td_abs and dq depend on that row alone.  M == 0 returns 0 without a launch.
+ * Refused by name before any launch, in this order: cfg, q_ptrs, next_target, td, dq_ptrs, q_taken, y, work, stats or loss NULL; A
+ * outside 1..MPE_ACTOR_MAX_AGENTS; dim_c outside 0..MPE_ACTOR_MAX_OUT; an unknown mix; an agent with no head, or with more than
+ * MPE_ACTOR_MAX_OUT logits; act NULL where an agent moves, utter NULL where one speaks; M < 0; td->ret or td->done NULL; a
+ * non-finite td->gamma when td->discount is NULL; a NULL q_ptrs[i] or dq_ptrs[i]; a float pointer not 4-byte or work not 8-byte
+ * aligned; A * M >= 2^31.  mpe_q_loss_work (host only) applies the A, M and size checks and returns the count, or a negative code. */
+enum { MPE_Q_INDEPENDENT = 0, MPE_Q_VDN = 1 };
+typedef struct MpeQLoss {
+  int32_t n_agents;                               /* A, 1..MPE_ACTOR_MAX_AGENTS                                             */
+  int32_t dim_c;
+  int32_t mix;                                    /* MPE_Q_INDEPENDENT / MPE_Q_VDN                                          */
+  int32_t reserved_;
+  uint8_t movable[MPE_ACTOR_MAX_AGENTS], speaks[MPE_ACTOR_MAX_AGENTS];
+} MpeQLoss;
+size_t mpe_sizeof_q_loss(void);
+int64_t mpe_q_loss_work(int32_t A, int64_t M);
+int mpe_q_loss(const MpeQLoss *cfg, const float *const *q_ptrs, const float *next_target, const float *next_online,
+               const float *act, const float *utter, const MpeTdTarget *td, const float *weights, int64_t M,
+               float *const *dq_ptrs, float *q_taken, float *y, float *td_abs, double *work, float *stats, float *loss,
+               void *stream);
 
 /* ---- the replay buffer: the last S steps of all B worlds in device memory (csrc/mpe_replay.hip) ------------------------------
  * What an off-policy learner keeps beside the loop above: a ring of transitions (obs, action, reward, done, next obs) of every

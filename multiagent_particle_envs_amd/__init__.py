@@ -10,6 +10,7 @@ from .policy import Actors, PolicyLoop  # noqa: F401
 from .learner import Critics, TdTargets  # noqa: F401
 from .learner import (TdLoss, TdLossResult, td_loss_tensors, ActorLoss, RowsLayout, PolicyRowsGradResult,  # noqa: F401
                       policy_rows_tensors, policy_rows_grad_tensors)
+from .learner import QLoss, QLossResult, QTargets, q_loss_tensors  # noqa: F401
 from .onpolicy import Values, GaeResult, gae, gae_tensors, adv_stats, Minibatches, OnPolicyBatch  # noqa: F401
 from .onpolicy import PpoLoss, PpoLossResult, ppo_loss_tensors  # noqa: F401
 from .train import Trainable, MlpGradResult, mlp_grad_tensors, mlp_dinput_tensors  # noqa: F401
@@ -22,6 +23,6 @@ __all__ = ["make_env", "MultiAgentEnv", "BatchMultiAgentEnv", "GraphedStep", "Ba
            "adv_stats", "Minibatches", "OnPolicyBatch", "PpoLoss", "PpoLossResult", "ppo_loss_tensors",
            "Trainable", "MlpGradResult", "mlp_grad_tensors", "mlp_dinput_tensors", "DeviceAdam",
            "TdLoss", "TdLossResult", "td_loss_tensors", "ActorLoss", "RowsLayout", "PolicyRowsGradResult", "policy_rows_tensors",
-           "policy_rows_grad_tensors", "PolyakTargets",
+           "policy_rows_grad_tensors", "PolyakTargets", "QLoss", "QLossResult", "QTargets", "q_loss_tensors",
            "ReplayBuffer", "ReplayBatch",
            "PrioritizedReplayBuffer", "PrioritizedReplayBatch", "NStepReplayBatch", "PrioritizedNStepReplayBatch"]

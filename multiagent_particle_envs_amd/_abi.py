@@ -128,6 +128,14 @@ class MpePolyak(C.Structure):          # include/mpe_hip.h: THE POLYAK RULE's ta
                 ("set", MpePolyakSet * MPE_ADAM_MAX_SETS)]
 
 
+MPE_Q_INDEPENDENT, MPE_Q_VDN = 0, 1
+
+
+class MpeQLoss(C.Structure):           # include/mpe_hip.h: the heads and the mix of THE Q LOSS RULE (mpe_q_loss)
+    _fields_ = [("n_agents", C.c_int32), ("dim_c", C.c_int32), ("mix", C.c_int32), ("reserved_", C.c_int32),
+                ("movable", C.c_uint8 * 16), ("speaks", C.c_uint8 * 16)]
+
+
 MPE_REPLAY_MAX_AGENTS, MPE_REPLAY_MAX_WIDTH = 16, 4096
 MPE_STREAM_REPLAY = 0x5245504C
 
@@ -261,6 +269,8 @@ EXPORTS = {
     "mpe_actor_supported": (C.c_int, [C.POINTER(MpeActorSet), C.c_int64]),
     "mpe_actor_act": (C.c_int, [C.POINTER(MpeActorSet), C.POINTER(C.c_void_p), C.c_int64, C.c_uint64, C.c_int64, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mpe_actor_act_explore": (C.c_int, [C.POINTER(MpeActorSet), C.POINTER(C.c_void_p), C.c_int64, C.c_uint64, C.c_int64, C.c_double,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mpe_actor_act_rows": (C.c_int, [C.POINTER(MpeActorSet), C.POINTER(C.c_void_p), C.c_int64, C.c_uint64, C.c_int64, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mpe_sizeof_td_target": (C.c_size_t, []),
@@ -296,6 +306,10 @@ EXPORTS = {
     "mpe_policy_rows_grad": (C.c_int, [C.POINTER(MpePolicyRows), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int64,
                                        C.POINTER(C.c_void_p)] + [C.c_void_p] * 5),
     "mpe_polyak": (C.c_int, [C.POINTER(MpePolyak), C.c_void_p]),
+    "mpe_sizeof_q_loss": (C.c_size_t, []),
+    "mpe_q_loss_work": (C.c_int64, [C.c_int32, C.c_int64]),
+    "mpe_q_loss": (C.c_int, [C.POINTER(MpeQLoss), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.POINTER(MpeTdTarget), C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)] + [C.c_void_p] * 7),
     "mpe_sizeof_replay": (C.c_size_t, []),
     "mpe_replay_supported": (C.c_int, [C.POINTER(MpeReplay)]),
     "mpe_replay_push": (C.c_int, [C.POINTER(MpeReplay), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
@@ -352,6 +366,7 @@ def lib():
             handle.mpe_sizeof_ppo_loss() != C.sizeof(MpePpoLoss) or \
             handle.mpe_sizeof_adam() != C.sizeof(MpeAdam) or \
             handle.mpe_sizeof_mlp_dinput() != C.sizeof(MpeMlpDinput) or \
+            handle.mpe_sizeof_q_loss() != C.sizeof(MpeQLoss) or \
             handle.mpe_sizeof_policy_rows() != C.sizeof(MpePolicyRows) or handle.mpe_sizeof_polyak() != C.sizeof(MpePolyak) or \
             handle.mpe_sizeof_replay_nstep() != C.sizeof(MpeReplayNStep):
         raise MpeError("struct layout mismatch between include/mpe_hip.h and _abi.py")

@@ -18,8 +18,8 @@ OBJ = os.path.join(HERE, "build")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmpe_hip.so")
 SOURCES = ["mpe_abi.hip", "mpe_narrow.hip", "mpe_split.hip", "mpe_wide.hip", "mpe_rng.hip", "mpe_rows.hip", "mpe_render.hip", "mpe_policy.hip", "mpe_replay.hip",
-           "mpe_replay_prio.hip", "mpe_gae.hip", "mpe_onpolicy.hip", "mpe_ppo_loss.hip", "mpe_mlp_grad.hip", "mpe_mlp_dinput.hip", "mpe_adam.hip", "mpe_ddpg.hip"]
-HEADERS = ["mpe_device.h", "mpe_internal.h", "mpe_split_scn.h", "mpe_gae.h", "mpe_gather.h", "mpe_onpolicy.h", "mpe_ppo_loss.h", "mpe_mlp_grad.h", "mpe_mlp_device.h", "mpe_mlp_dinput.h", "mpe_adam.h", "mpe_ddpg.h", os.path.join("..", "..", "include", "mpe_hip.h")]
+           "mpe_replay_prio.hip", "mpe_gae.hip", "mpe_onpolicy.hip", "mpe_ppo_loss.hip", "mpe_mlp_grad.hip", "mpe_mlp_dinput.hip", "mpe_adam.hip", "mpe_ddpg.hip", "mpe_qloss.hip"]
+HEADERS = ["mpe_device.h", "mpe_internal.h", "mpe_split_scn.h", "mpe_gae.h", "mpe_gather.h", "mpe_onpolicy.h", "mpe_ppo_loss.h", "mpe_mlp_grad.h", "mpe_mlp_device.h", "mpe_mlp_dinput.h", "mpe_adam.h", "mpe_ddpg.h", "mpe_qloss.h", os.path.join("..", "..", "include", "mpe_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function",
          # kernarg preload (gfx94x/gfx950): the CP writes the first dwords of the kernarg segment into user SGPRs at wave

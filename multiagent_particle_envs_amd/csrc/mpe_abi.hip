@@ -1296,6 +1296,28 @@ int mpe_actor_act(const MpeActorSet *s, const float *const *obs_ptrs, int64_t B,
   if (B == 0) return 0;
   return hip_result(mpe::launch_actor(a, static_cast<hipStream_t>(stream)), what);
 }
+// mpe_actor_act with THE EXPLORATION RULE: a GREEDY set whose heads explore with probability E / 65536
+int mpe_actor_act_explore(const MpeActorSet *s, const float *const *obs_ptrs, int64_t B, uint64_t step, int64_t world_offset, double epsilon,
+                          float *moves, float *utter, int32_t *ids, float *logp, float *logits, void *stream) {
+  const char *what = "mpe_actor_act_explore";
+  if (int rc = check_actor_set(s, what)) return rc;
+  if (s->mode != MPE_POLICY_GREEDY)
+    return fail(MPE_EINVAL, "%s: mode %d (%s; exploration replaces the choice of a MPE_POLICY_GREEDY set)", what, s->mode,
+                s->mode == MPE_POLICY_SAMPLE ? "MPE_POLICY_SAMPLE" : "MPE_POLICY_SOFTMAX");
+  if (!std::isfinite(epsilon) || epsilon < 0.0 || epsilon > 1.0) return fail(MPE_EINVAL, "%s: epsilon = %g (need 0 <= epsilon <= 1)", what, epsilon);
+  if (int rc = check_actor_call(s, obs_ptrs, B, "B", "obs_ptrs", what)) return rc;
+  if (!moves) return fail(MPE_EINVAL, "%s: moves is NULL", what);
+  if (logits && ((uintptr_t)logits & 15)) return fail(MPE_EINVAL, "%s: logits is not 16-byte aligned", what);
+  mpe::ActorArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (int rc = fill_actor_args(s, obs_ptrs, B, "obs_ptrs", what, a)) return rc;
+  a.moves = moves, a.utter = utter, a.ids = ids, a.logp = logp, a.logits = logits;
+  a.step = step, a.world_offset = (uint64_t)world_offset;
+  const double e = std::floor(epsilon * 65536.0 + 0.5);
+  a.explore = e > 65536.0 ? 65536u : (uint32_t)e;
+  if (B == 0) return 0;
+  return hip_result(mpe::launch_actor(a, static_cast<hipStream_t>(stream)), what);
+}
 int mpe_actor_act_rows(const MpeActorSet *s, const float *const *obs_ptrs, int64_t M, uint64_t step, int64_t row_offset, float *moves,
                        float *utter, int32_t *ids, float *logp, float *logits, float *joint, int64_t joint_stride, void *stream) {
   const char *what = "mpe_actor_act_rows";
@@ -1952,6 +1974,59 @@ int mpe_polyak(const MpePolyak *c, void *stream) {
   mpe::polyak_tiling(a);
   a.tau = c->tau_ptr ? 0.f : (float)c->tau, a.tau_ptr = c->tau_ptr;
   return hip_result(mpe::launch_polyak(a, static_cast<hipStream_t>(stream)), what);
+}
+
+// ---- the value-based learners' loss head (mpe_qloss.hip) ------------------------------------------------------------------------
+size_t mpe_sizeof_q_loss(void) { return sizeof(MpeQLoss); }
+int64_t mpe_q_loss_work(int32_t A, int64_t M) { return ddpg_work(A, M, "mpe_q_loss_work"); }
+int mpe_q_loss(const MpeQLoss *cfg, const float *const *q_ptrs, const float *next_target, const float *next_online, const float *act,
+               const float *utter, const MpeTdTarget *td, const float *weights, int64_t M, float *const *dq_ptrs, float *q_taken, float *y,
+               float *td_abs, double *work, float *stats, float *loss, void *stream) {
+  const char *what = "mpe_q_loss";
+  const struct { const void *p; const char *name; } need[] = {{cfg, "cfg"}, {q_ptrs, "q_ptrs"}, {next_target, "next_target"}, {td, "td"},
+                                                              {dq_ptrs, "dq_ptrs"}, {q_taken, "q_taken"}, {y, "y"}, {work, "work"},
+                                                              {stats, "stats"}, {loss, "loss"}};
+  for (const auto &f : need)
+    if (!f.p) return fail(MPE_EINVAL, "%s: %s is NULL", what, f.name);
+  const int32_t A = cfg->n_agents;
+  if (int rc = check_ppo_agents(A, what)) return rc;
+  if (cfg->dim_c < 0 || cfg->dim_c > MPE_ACTOR_MAX_OUT) return fail(MPE_EINVAL, "%s: dim_c = %d (0..%d)", what, cfg->dim_c, MPE_ACTOR_MAX_OUT);
+  if (cfg->mix != MPE_Q_INDEPENDENT && cfg->mix != MPE_Q_VDN) return fail(MPE_EINVAL, "%s: mix = %d (MPE_Q_INDEPENDENT / MPE_Q_VDN)", what, cfg->mix);
+  mpe::QLossArgs a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  bool moves = false, speaks = false;
+  for (int i = 0; i < A; ++i) {
+    const bool mv = cfg->movable[i] != 0, sp = cfg->speaks[i] != 0 && cfg->dim_c > 0;
+    const int n = MPE_ACTION_DIM * mv + cfg->dim_c * sp;
+    if (n < 1) return fail(MPE_EINVAL, "%s: agent %d has no head (neither movable nor speaking with dim_c > 0)", what, i);
+    if (n > MPE_ACTOR_MAX_OUT)
+      return fail(MPE_EUNSUPPORTED, "%s: agent %d: %d logits (5 * movable + dim_c * speaks) > MPE_ACTOR_MAX_OUT = %d", what, i, n, MPE_ACTOR_MAX_OUT);
+    a.movable[i] = mv, a.speaks[i] = sp;
+    moves |= mv, speaks |= sp;
+  }
+  if (moves && !act) return fail(MPE_EINVAL, "%s: act is NULL and an agent moves", what);
+  if (speaks && !utter) return fail(MPE_EINVAL, "%s: utter is NULL and an agent speaks", what);
+  if (int rc = check_ppo_rows(M, what)) return rc;
+  if (!td->ret) return fail(MPE_EINVAL, "%s: td->ret is NULL", what);
+  if (!td->done) return fail(MPE_EINVAL, "%s: td->done is NULL", what);
+  if (!td->discount && !std::isfinite(td->gamma))
+    return fail(MPE_EINVAL, "%s: td->gamma = %g is not finite (and td->discount is NULL)", what, (double)td->gamma);
+  uintptr_t f4 = (uintptr_t)next_target | (uintptr_t)next_online | (uintptr_t)act | (uintptr_t)utter | (uintptr_t)td->ret |
+                 (uintptr_t)td->discount | (uintptr_t)weights | (uintptr_t)q_taken | (uintptr_t)y | (uintptr_t)td_abs | (uintptr_t)stats |
+                 (uintptr_t)loss;
+  for (int i = 0; i < A; ++i) {
+    if (!q_ptrs[i]) return fail(MPE_EINVAL, "%s: q_ptrs[%d] is NULL", what, i);
+    if (!dq_ptrs[i]) return fail(MPE_EINVAL, "%s: dq_ptrs[%d] is NULL", what, i);
+    f4 |= (uintptr_t)q_ptrs[i] | (uintptr_t)dq_ptrs[i];
+    a.q[i] = q_ptrs[i], a.dq[i] = dq_ptrs[i];
+  }
+  if ((f4 & 3) || ((uintptr_t)work & 7)) return fail(MPE_EINVAL, "%s: every float tensor must be 4-byte and work 8-byte aligned", what);
+  if (int rc = check_ppo_size(A, M, what)) return rc;
+  if (M == 0) return 0;
+  a.nt = next_target, a.no = next_online, a.act = act, a.utter = utter, a.ret = td->ret, a.discount = td->discount, a.w = weights;
+  a.done = td->done, a.q_taken = q_taken, a.y = y, a.td_abs = td_abs, a.work = work, a.stats = stats, a.loss = loss;
+  a.M = (uint64_t)M, a.A = A, a.dim_c = cfg->dim_c, a.mix = cfg->mix, a.gamma = td->gamma;
+  return hip_result(mpe::launch_q_loss(a, static_cast<hipStream_t>(stream)), what);
 }
 
 // ---- the replay buffer (mpe_replay.hip) ---------------------------------------------------------------------------------------

@@ -405,8 +405,11 @@ __device__ __forceinline__ float pol_act(float x, bool tnh) {
 // the chosen index (argmax in SOFTMAX mode) and log softmax(z)[chosen].  argmax ties go to the lowest index (np.argmax); softmax
 // in fp32 is e_j = exp(z_j - max z), s = ((e_0 + e_1) + ...) + e_{n-1}, p_j = e_j / s; SAMPLE picks the first j <= n - 2 with
 // u < c_j, c_0 = p_0, c_j = c_{j-1} + p_j (fp32, in that order), else n - 1, with u = (bits >> 8) * 2^-24.
+// E (THE EXPLORATION RULE of include/mpe_hip.h, GREEDY sets only; 0: none): the head explores iff (bits >> 16) < E, and then
+// chooses ((bits & 0xffff) * n) >> 16 in place of the argmax; its row and logp are GREEDY's for the index chosen.
 template <int N>
-__device__ __forceinline__ int pol_head(const float (&z)[N], int n, int mode, uint32_t bits, float (&r)[N], float &logp) {
+__device__ __forceinline__ int pol_head(const float (&z)[N], int n, int mode, uint32_t bits, float (&r)[N], float &logp,
+                                        uint32_t E = 0u) {
   float zm = z[0];
   int am = 0;
 #pragma unroll
@@ -439,6 +442,7 @@ __device__ __forceinline__ int pol_head(const float (&z)[N], int n, int mode, ui
       for (int j = N - 2; j >= 0; --j)   // (descending: the last hit is the first j with u < c_j)
         if (j < n - 1 && u < cj[j]) m = j;
     }
+    if (E != 0u && (bits >> 16) < E) m = (int)(((bits & 0xffffu) * (uint32_t)n) >> 16);
 #pragma unroll
     for (int j = 0; j < N; ++j) r[j] = j == m ? 1.f : 0.f;
   }

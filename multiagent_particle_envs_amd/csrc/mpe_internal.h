@@ -9,6 +9,7 @@
 #include "mpe_mlp_dinput.h"
 #include "mpe_adam.h"
 #include "mpe_ddpg.h"
+#include "mpe_qloss.h"
 
 namespace mpe {
 
@@ -147,6 +148,7 @@ struct ActorArgs {
   uint64_t seed, step, world_offset;
   uint64_t B;
   int32_t n_agents, mode, dim_c;
+  uint32_t explore;                            // E of THE EXPLORATION RULE, 0..65536 (mpe_actor_act_explore; 0: no draw)
   int32_t off[MPE_ACTOR_MAX_AGENTS];           // float offset of agent i's packed actor
   int16_t width[MPE_ACTOR_MAX_AGENTS][4];      // input width, then each layer's output width
   uint8_t nl[MPE_ACTOR_MAX_AGENTS], act[MPE_ACTOR_MAX_AGENTS], movable[MPE_ACTOR_MAX_AGENTS], speaks[MPE_ACTOR_MAX_AGENTS];
@@ -214,6 +216,10 @@ int launch_td_loss(const TdArgs &a, hipStream_t stream);                    // t
 int launch_policy_rows(const PolRowsArgs &a, hipStream_t stream);           // one launch, M > 0
 int launch_policy_rows_grad(const PolRowsArgs &a, double reg_coef, float *stats, float *loss, hipStream_t stream);      // one launch; two with stats
 int launch_polyak(const PolyakArgs &a, hipStream_t stream);                 // one launch
+
+// the value-based learners' loss head (mpe_qloss.hip; QLossArgs, every index and the rows' arithmetic: mpe_qloss.h), checked by the caller
+static_assert(kQIndependent == MPE_Q_INDEPENDENT && kQVdn == MPE_Q_VDN && kQRow == MPE_ACTOR_MAX_OUT, "mpe_qloss.h restates them");
+int launch_q_loss(const QLossArgs &a, hipStream_t stream);                  // two launches: the rows and chunk sums, then the ordered final pass
 
 // the replay buffer (mpe_replay.hip): both launches' arguments, checked and filled by the caller (mpe_replay_push / _sample)
 constexpr int kReplayMaxSegs = 2 * MPE_REPLAY_MAX_AGENTS + 4;     // obs and next obs per agent, act, utter, rew, done

@@ -19,7 +19,8 @@
 //
 // The kernel is a template over what follows the logits: the heads (mpe_actor_act), the heads plus the critic's
 // joint rows over M rows of any origin (mpe_actor_act_rows), or no head at all -- a one-output last layer read as q, and the TD
-// target y (mpe_critic_q).  The layers and the logits staging are the same code in all three.
+// target y (mpe_critic_q).  The layers and the logits staging are the same code in all three.  mpe_actor_act_explore is the heads
+// launch with ActorArgs.explore > 0: one more branch of pol_head (THE EXPLORATION RULE); 0 draws nothing.
 #include "mpe_device.h"
 #include "mpe_internal.h"
 
@@ -244,9 +245,9 @@ k_actor(const Args p) {
   int id_m = -1;
   if (movable) {
     const float z5[MPE_ACTION_DIM] = {lg[0], lg[1], lg[2], lg[3], lg[4]};
-    const uint32_t bits = p.mode == MPE_POLICY_SAMPLE ? policy_bits(p.seed, gw, p.step, ag) : 0u;
+    const uint32_t bits = p.mode == MPE_POLICY_SAMPLE || p.explore ? policy_bits(p.seed, gw, p.step, ag) : 0u;
     float lp;
-    id_m = pol_head<MPE_ACTION_DIM>(z5, MPE_ACTION_DIM, p.mode, bits, mv, lp);
+    id_m = pol_head<MPE_ACTION_DIM>(z5, MPE_ACTION_DIM, p.mode, bits, mv, lp, p.explore);
     logp = lp;
   }
   float *gmoves = p.moves + row * MPE_ACTION_DIM;
@@ -277,9 +278,9 @@ k_actor(const Args p) {
       float zc[kLW];
 #pragma unroll
       for (int j = 0; j < kLW; ++j) zc[j] = movable ? (j + MPE_ACTION_DIM < kLW ? lg[(j + MPE_ACTION_DIM) % kLW] : 0.f) : lg[j];
-      const uint32_t bits = p.mode == MPE_POLICY_SAMPLE ? policy_comm_bits(p.seed, gw, p.step, ag) : 0u;
+      const uint32_t bits = p.mode == MPE_POLICY_SAMPLE || p.explore ? policy_comm_bits(p.seed, gw, p.step, ag) : 0u;
       float lp;
-      id_c = pol_head<kLW>(zc, p.dim_c, p.mode, bits, ut, lp);
+      id_c = pol_head<kLW>(zc, p.dim_c, p.mode, bits, ut, lp, p.explore);
       logp = movable ? logp + lp : lp;
     }
     store_rows_n<kLW>(stage, ut, p.dim_c, p.utter ? p.utter + row * (size_t)p.dim_c : nullptr, nlive, lane);

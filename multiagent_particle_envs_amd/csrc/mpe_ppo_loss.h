@@ -26,6 +26,10 @@
 // the ratio's exponential is the accurate expf on both sides: __expf multiplies its argument by log2 e first, and the rounding of
 // that product grows with |lr| -- on rows far outside the clip it alone cost more than the parity bound allows
 #define MPE_PPO_EXP_RATIO(x) expf(x)
+// a host walk counts the stores of ppo_stage_out through this hook (p: the first float, n: how many)
+#ifndef MPE_PPO_STORED
+#define MPE_PPO_STORED(p, n)
+#endif
 
 namespace mpe {
 
@@ -122,10 +126,14 @@ MPE_PPO_HD void ppo_stage_out(float *g, uint32_t count, uint32_t n, const float 
         v.w = tile[ppo_tile_at(4 * q + 3, n, magic)];
       }
       reinterpret_cast<PpoF4 *>(g)[q] = v;
+      MPE_PPO_STORED(g + 4 * q, 4);
     }
     done = 4 * nv;
   }
-  for (uint32_t idx = done + lane; idx < count; idx += kPpoWave) g[idx] = tile[ppo_tile_at(idx, n, magic)];
+  for (uint32_t idx = done + lane; idx < count; idx += kPpoWave) {
+    g[idx] = tile[ppo_tile_at(idx, n, magic)];
+    MPE_PPO_STORED(g + idx, 1);
+  }
 }
 
 // ---- one head -------------------------------------------------------------------------------------------------------------------

@@ -5,7 +5,9 @@ input rows (Actors.act_rows, joint=True), the target critics read those rows and
 (joint rows, y) are stated in include/mpe_hip.h.  The loss heads of the update are here too: `TdLoss` (the critics'
 weighted squared TD error and its gradient, mpe_td_loss) and `ActorLoss` (the relaxed action rows, the critics on them, their input
 gradient and the softmax Jacobian: mpe_policy_rows, mpe_critic_q, mpe_mlp_dinput, mpe_policy_rows_grad), both behind torch autograd
-with a one-multiply backward; the networks' own backward passes are train.py's.
+with a one-multiply backward; the networks' own backward passes are train.py's.  The value-based learners (independent Q-learning,
+VDN) have `QTargets` (the target and, for double-Q, the online networks' logits of the next observations) and `QLoss`
+(mpe_q_loss: from the logits to dL/dlogits in two launches).
 
     mu_t, q_t = Actors(env, target_actor_modules, mode="softmax"), Critics(env, target_critic_modules)
     td = TdTargets(mu_t, q_t)
@@ -450,5 +452,207 @@ class ActorLoss(object):
         if not torch.is_tensor(joint) or joint.requires_grad:
             raise _abi.MpeError("%s: joint is the batch's joint rows, a tensor that does not require grad" % who)
         loss = _ActorLossFn.apply(self, joint, *logits_n)
+        loss.stats = self.last.stats
+        return loss
+
+
+# ---- the value-based learners: next-state logits and the Q-loss head (mpe_q_loss) ------------------------------------
+_Q_MIXES = {"independent": _abi.MPE_Q_INDEPENDENT, "vdn": _abi.MPE_Q_VDN}
+
+
+class QTargets(object):
+    """The next-state action values of a sampled batch: compute(batch) runs target_actors.act_rows(batch.next_obs_n) and, with
+    online_actors (double-Q), online_actors.act_rows(batch.next_obs_n) -- one launch each -- and returns (next_target,
+    next_online or None), the [A, M, 16] logits tensors q_loss_tensors / QLoss take.  Both sets are Actors(env, modules,
+    mode="greedy", logits=True) of the batch's env; next_target is the target set's own tensor, next_online a copy kept here (the
+    online set's next launch over M rows rewrites its own); both cached per M.  act_rows never explores."""
+
+    def __init__(self, target_actors, online_actors=None):
+        for name, a in (("target_actors", target_actors), ("online_actors", online_actors)):
+            if a is None and name == "online_actors":
+                continue
+            if not isinstance(a, Actors):
+                raise _abi.MpeError("QTargets: %s is an Actors(env, modules, mode=\"greedy\", logits=True)" % name)
+            if not a._want[2]:
+                raise _abi.MpeError("QTargets: %s was built without logits=True (the launch writes no logits)" % name)
+        if online_actors is not None and online_actors.env is not target_actors.env:
+            raise _abi.MpeError("QTargets: online_actors and target_actors were built for different envs")
+        self.target, self.online = target_actors, online_actors
+        self.next_target = self.next_online = None
+        self._keep = Cache()
+
+    def compute(self, batch):
+        if not isinstance(batch, ReplayBatch):
+            raise _abi.MpeError("QTargets.compute: batch is a ReplayBatch (ReplayBuffer.sample / gather)")
+        obs = batch.next_obs_n
+        if len(obs) != self.target.A or any(int(o.shape[1]) != d for o, d in zip(obs, self.target.obs_widths)) or \
+                obs[0].device != self.target.world.device:
+            raise _abi.MpeError("QTargets.compute: batch was sampled from another env's buffer (its next_obs_n are not the actors' "
+                                "observation blocks)")
+        self.target.act_rows(obs)
+        self.next_target = self.target.rows.logits
+        self.next_online = None
+        if self.online is not None:
+            # a copy of this object's: the online set's next act_rows of this M (a Trainable's forward on batch.obs_n) rewrites its own
+            self.online.act_rows(obs)
+            z = self.online.rows.logits
+            self.next_online = self._keep.get(int(z.shape[1]), lambda: torch.empty_like(z))
+            self.next_online.copy_(z)
+        return self.next_target, self.next_online
+
+
+class QLossResult(object):
+    """What q_loss_tensors wrote: loss [1]; stats [A, 8] (TdLossResult.STATS, q the agent's mean utility of the actions taken; under
+    VDN the error columns are the team's in every row); dq_n, A views [M, n_i] of ONE flat float32 buffer `grads` (every block
+    starts at a multiple of 4 floats) = dL/dlogits; q_taken [A, M]; y [A, M] (VDN: the team's target in every row); td_abs [M]
+    (what PrioritizedReplayBuffer.update_td takes); work, the launches' workspace."""
+    __slots__ = ("A", "M", "n", "mix", "loss", "stats", "grads", "dq_n", "q_taken", "y", "td_abs", "work")
+
+    STATS = TdLossResult.STATS
+
+
+def _q_result(n, M, mix, dev):
+    r = QLossResult()
+    g = _rows_grad_result(n, M, dev)
+    r.A, r.M, r.n, r.mix = len(n), M, list(n), mix
+    r.grads, r.dq_n, r.stats, r.loss = g.grads, g.dlogits_n, g.stats, g.loss
+    r.q_taken = torch.zeros((r.A, M), dtype=torch.float32, device=dev)
+    r.y = torch.zeros((r.A, M), dtype=torch.float32, device=dev)
+    r.td_abs = torch.zeros((M,), dtype=torch.float32, device=dev)
+    r.work = _work("mpe_q_loss_work", r.A, M, dev)
+    return r
+
+
+def q_loss_tensors(layout, q_n, batch, next_target, next_online=None, gamma=None, mix="independent", weights=None, out=None):
+    """THE Q LOSS RULE in two launches for every agent, no host synchronisation (captures into a HIP graph).  layout: an Actors (the
+    Q-networks: its heads) or a RowsLayout; q_n[i]: agent i's online logits [M, n_i] (what Trainable(actors)(batch.obs_n)
+    returns); batch: a ReplayBatch -- its act / utter rows choose, its rew (one-step, with gamma) or ret and discount (n-step:
+    gamma is refused) and its done make the target; next_target, next_online: QTargets.compute's [A, M, 16] tensors (next_online
+    None: the plain max-Q target, else double-Q); mix: "independent" or "vdn"; weights [M]: the importance weights of a
+    prioritized batch (None: 1).  out: a QLossResult to rewrite.  -> QLossResult."""
+    who = "q_loss_tensors"
+    lay = RowsLayout.of(layout, who)
+    if mix not in _Q_MIXES:
+        raise _abi.MpeError("%s: mix is one of %s (got %r)" % (who, sorted(_Q_MIXES), mix))
+    if not isinstance(q_n, (list, tuple)) or len(q_n) != lay.A:
+        raise _abi.MpeError("%s: q_n is a list of %d tensors, one per agent" % (who, lay.A))
+    q0 = q_n[0]
+    if not torch.is_tensor(q0) or q0.dim() != 2:
+        raise _abi.MpeError("%s: q_n[0] is a contiguous float32 [M, %d] tensor on a GPU" % (who, lay.n[0]))
+    M, dev, A = int(q0.shape[0]), q0.device, lay.A
+    for i, q in enumerate(q_n):
+        check_tensor(who, q, "q_n[%d]" % i, [(M, lay.n[i])], "q_n[0]'s device", dev)
+    if not isinstance(batch, ReplayBatch):
+        raise _abi.MpeError("%s: batch is a ReplayBatch (ReplayBuffer.sample / gather)" % who)
+    td = _abi.MpeTdTarget()
+    if getattr(batch, "ret", None) is not None:
+        if gamma is not None:
+            raise _abi.MpeError("%s: an n-step batch carries its own discount (gamma^m per row); gamma is not taken" % who)
+        check_tensor(who, batch.ret, "batch.ret", [(A, M)], "q_n[0]'s device", dev)
+        check_tensor(who, batch.discount, "batch.discount", [(M,)], "q_n[0]'s device", dev)
+        td.ret, td.discount = batch.ret.data_ptr(), batch.discount.data_ptr()
+    else:
+        if gamma is None:
+            raise _abi.MpeError("%s: gamma is required for a one-step batch" % who)
+        if not math.isfinite(float(gamma)):
+            raise _abi.MpeError("%s: gamma = %r is not finite" % (who, gamma))
+        check_tensor(who, batch.rew, "batch.rew", [(A, M)], "q_n[0]'s device", dev)
+        td.ret, td.discount, td.gamma = batch.rew.data_ptr(), None, float(gamma)
+    if not torch.is_tensor(batch._done_u8) or batch._done_u8.dtype != torch.uint8 or tuple(batch._done_u8.shape) != (A, M) or \
+            not batch._done_u8.is_contiguous() or batch._done_u8.device != dev:
+        raise _abi.MpeError("%s: batch.done is a contiguous [%d, %d] tensor on q_n[0]'s device" % (who, A, M))
+    td.done = batch._done_u8.data_ptr()
+    if any(lay.movable):
+        check_tensor(who, batch.act, "batch.act", [(A, M, _abi.MPE_ACTION_DIM)], "q_n[0]'s device", dev)
+    if any(lay.speaks):
+        check_tensor(who, batch.utter, "batch.utter", [(A, M, lay.dim_c)], "q_n[0]'s device", dev)
+    check_tensor(who, next_target, "next_target", [(A, M, _abi.MPE_ACTOR_MAX_OUT)], "q_n[0]'s device", dev)
+    if next_online is not None:
+        check_tensor(who, next_online, "next_online", [(A, M, _abi.MPE_ACTOR_MAX_OUT)], "q_n[0]'s device", dev)
+    if weights is not None:
+        check_tensor(who, weights, "weights", [(M,)], "q_n[0]'s device", dev)
+    code = _Q_MIXES[mix]
+    if out is not None and (not isinstance(out, QLossResult) or out.M != M or out.n != lay.n or out.mix != code or out.grads.device != dev):
+        raise _abi.MpeError("%s: out is a QLossResult of the same heads, mix and M = %d (what an earlier call returned)" % (who, M))
+    if not q0.is_cuda:
+        raise _abi.MpeError("%s: q_n[0] is on %s (the tensors live on a GPU: there is no CPU path)" % (who, dev))
+    if out is None:
+        out = _q_result(lay.n, M, code, dev)
+    cfg = _abi.MpeQLoss()
+    cfg.n_agents, cfg.dim_c, cfg.mix = A, lay.dim_c, code
+    for i in range(A):
+        cfg.movable[i], cfg.speaks[i] = int(lay.movable[i]), int(lay.speaks[i])
+    _abi.check(_abi.lib().mpe_q_loss(
+        C.byref(cfg), _ptrs(q_n), next_target.data_ptr(), next_online.data_ptr() if next_online is not None else None,
+        batch.act.data_ptr() if any(lay.movable) else None, batch.utter.data_ptr() if any(lay.speaks) else None, C.byref(td),
+        weights.data_ptr() if weights is not None else None, M, _ptrs(out.dq_n), out.q_taken.data_ptr(), out.y.data_ptr(),
+        out.td_abs.data_ptr(), out.work.data_ptr(), out.stats.data_ptr(), out.loss.data_ptr(), _abi.raw_stream(dev)), "mpe_q_loss")
+    return out
+
+
+class _QLossFn(torch.autograd.Function):
+    """forward: the two launches; backward: grad_output * the gradients the forward wrote (ONE multiply)"""
+
+    @staticmethod
+    def forward(ctx, head, batch, next_target, next_online, gamma, weights, *q_n):
+        qs = [q.detach() for q in q_n]
+        M = int(qs[0].shape[0]) if qs[0].dim() == 2 else -1
+        key = (M, qs[0].device)
+        res = q_loss_tensors(head.layout, qs, batch, next_target, next_online, gamma, head.mix, weights, out=head._out.get(key))
+        head._out.get(key, lambda: res)
+        ctx.res, ctx.shapes, ctx.owner = res, [tuple(q.shape) for q in q_n], (head, key, head._generation.next(key))
+        head.last = res
+        return res.loss.view(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        res = ctx.res
+        head, key, generation = ctx.owner
+        if head._generation.stale(key, generation) or head._out.get(key) is not res:
+            raise _abi.MpeError("QLoss: backward() of a loss whose buffers a later forward with the same M has rewritten (the "
+                                "buffers are cached per M: call backward() before the next forward)")
+        g = grad_output * res.grads      # out of place: the buffer is rewritten by the next forward of the same M
+        at, grads = 0, []
+        for k, shape in zip(res.n, ctx.shapes):
+            grads.append(g[at:at + res.M * k].view(shape))
+            at += (res.M * k + 3) // 4 * 4
+        return (None,) * 6 + tuple(grads)
+
+
+class QLoss(object):
+    """The Q-loss head behind torch autograd: loss = QLoss(actors, mix="independent", double=True)(q_n, batch, next_target,
+    next_online, gamma=None, weights=None) with q_n = Trainable(actors)(batch.obs_n) and (next_target, next_online) =
+    QTargets(target_actors, actors).compute(batch).  mix="independent": the sum over the agents of mean(weights * (Q_i(s)[a_i] -
+    y_i)^2), y_i = ret_i + discount * (1 - done_i) * Q'_i(s')[argmax Q_i(s')]; mix="vdn": mean(weights * (sum_i Q_i(s)[a_i] - y)^2)
+    with the team's reward, any-agent done and the summed bootstrap.  double=False takes the plain max of the target net
+    (next_online is refused); double=True requires next_online.  The forward is mpe_q_loss's two launches for all agents, the
+    backward ONE multiply of grad_output with the gradients the forward wrote; no host read anywhere.  loss.stats [A, 8] (device)
+    carries QLossResult.STATS; .last is the QLossResult of the last call (its td_abs [M] is what a prioritized buffer's update_td
+    takes).  The buffers are cached per M and rewritten by the next call with the same M: call backward() before the next
+    forward; a backward() behind such a forward is refused.  Once differentiable."""
+
+    def __init__(self, actors, mix="independent", double=True):
+        self.layout = RowsLayout.of(actors, "QLoss")
+        if mix not in _Q_MIXES:
+            raise _abi.MpeError("QLoss: mix is one of %s (got %r)" % (sorted(_Q_MIXES), mix))
+        self.mix, self.double = mix, bool(double)
+        self._out, self._generation, self.last = Cache(), Generations(), None
+
+    def __call__(self, q_n, batch, next_target, next_online=None, gamma=None, weights=None):
+        who = "QLoss"
+        if not isinstance(q_n, (list, tuple)) or len(q_n) != self.layout.A:
+            raise _abi.MpeError("%s: q_n is a list of %d tensors, one per agent" % (who, self.layout.A))
+        for i, t in enumerate(q_n):
+            if not torch.is_tensor(t):
+                raise _abi.MpeError("%s: q_n[%d] is not a tensor" % (who, i))
+        if self.double and next_online is None:
+            raise _abi.MpeError("%s: double=True needs next_online (QTargets(target_actors, online_actors).compute)" % who)
+        if not self.double and next_online is not None:
+            raise _abi.MpeError("%s: double=False takes the target net's own maximum; next_online is not taken" % who)
+        for name, t in (("next_target", next_target), ("next_online", next_online), ("weights", weights)):
+            if torch.is_tensor(t) and t.requires_grad:
+                raise _abi.MpeError("%s: %s requires grad (it is a constant of the loss)" % (who, name))
+        loss = _QLossFn.apply(self, batch, next_target, next_online, gamma, weights, *q_n)
         loss.stats = self.last.stats
         return loss

@@ -81,13 +81,20 @@ class Actors(NetSet):
     logp / ids / logits = True: the same launch also fills pi.logp [A,B] (sum over the heads of log p[chosen]), pi.ids [2,A,B]
     int32 (move head, utterance head; -1 where an agent has no such head) and pi.logits [A,B,16] (raw last-layer outputs).
     The weights are packed again at every act() unless freeze() was called, so in-place optimiser updates are seen; agents
-    handed the SAME module object share one packed copy."""
+    handed the SAME module object share one packed copy.
+    epsilon (mode="greedy" only): act() plays epsilon-greedy in the same launch (mpe_actor_act_explore, THE
+    EXPLORATION RULE of include/mpe_hip.h: each head explores with probability E / 65536, E = round(epsilon * 65536), on the
+    sample draws' own bits of (seed, world, t, agent)).  pi.epsilon is a plain attribute read at every act(), so a schedule is one
+    assignment per step; 0 is mpe_actor_act itself.  act_rows never explores: a target is greedy.  Inside PolicyLoop.capture()
+    the value is FROZEN at capture (a launch argument of the captured graph): re-capture to change it."""
     who, noun = "Actors", "actors"
 
-    def __init__(self, env, modules, mode="sample", seed=0, logp=False, ids=False, logits=False):
+    def __init__(self, env, modules, mode="sample", seed=0, logp=False, ids=False, logits=False, epsilon=0.0):
         if mode not in _POLICY_MODES:
             raise _abi.MpeError("Actors: mode is one of %s (got %r)" % (sorted(_POLICY_MODES), mode))
         self.mode, self.seed = mode, int(seed) & (2 ** 64 - 1)
+        self.epsilon = epsilon
+        self._epsilon("Actors")
         NetSet.__init__(self, env, modules)
         self.B = self.world.batch_size
         self._want = (bool(logp), bool(ids), bool(logits))
@@ -142,6 +149,19 @@ class Actors(NetSet):
     def _ptr_array(self, ptrs):
         return (C.c_void_p * self.A)(*ptrs)
 
+    def _epsilon(self, who):
+        """self.epsilon, checked -> a float in [0, 1]"""
+        try:
+            eps = float(self.epsilon)
+        except (TypeError, ValueError):
+            eps = float("nan")
+        if not 0.0 <= eps <= 1.0:      # (a NaN fails both)
+            raise _abi.MpeError("%s: epsilon = %r (a number in [0, 1])" % (who, self.epsilon))
+        if eps > 0.0 and self.mode != "greedy":
+            raise _abi.MpeError("%s: epsilon = %r with mode %r (exploration replaces the choice of a mode=\"greedy\" set)"
+                                % (who, self.epsilon, self.mode))
+        return eps
+
     def act(self, obs_n, t=0, moves=None, logp=None):
         """One launch: every agent's rows for the observations obs_n (a list of [B, D_i] device tensors: env.step's / env.reset's
         own output qualifies) at global step t (the sample draws' key) -> the [A,B,5] move tensor, or (moves, utterances
@@ -151,11 +171,16 @@ class Actors(NetSet):
         wts, aset = self.packed()
         mv = self.moves if moves is None else moves
         lp = self.logp if logp is None else logp
-        _abi.check(_abi.lib().mpe_actor_act(
-            C.byref(aset), _obs_blocks(self, obs_n, "Actors.act", self._ptr_array, self.B)[1], self.B, int(t), int(self.world.world_offset), mv.data_ptr(),
-            self.utter.data_ptr() if self.utter is not None else None, self.ids.data_ptr() if self.ids is not None else None,
-            lp.data_ptr() if lp is not None else None, self.logits.data_ptr() if self.logits is not None else None,
-            _abi.raw_stream(self.world.device)), "mpe_actor_act")
+        eps = self._epsilon("Actors.act")
+        arr = _obs_blocks(self, obs_n, "Actors.act", self._ptr_array, self.B)[1]
+        out = (mv.data_ptr(), self.utter.data_ptr() if self.utter is not None else None,
+               self.ids.data_ptr() if self.ids is not None else None, lp.data_ptr() if lp is not None else None,
+               self.logits.data_ptr() if self.logits is not None else None, _abi.raw_stream(self.world.device))
+        if eps > 0.0:
+            _abi.check(_abi.lib().mpe_actor_act_explore(C.byref(aset), arr, self.B, int(t), int(self.world.world_offset), eps, *out),
+                       "mpe_actor_act_explore")
+        else:
+            _abi.check(_abi.lib().mpe_actor_act(C.byref(aset), arr, self.B, int(t), int(self.world.world_offset), *out), "mpe_actor_act")
         del wts      # (stream-ordered: the caching allocator reuses the block only behind the launch)
         if moves is None:
             return self._action
